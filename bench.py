@@ -1,17 +1,24 @@
 #!/usr/bin/env python3
-"""bench.py — depth frames/s integrated at 640x480 (BASELINE.json metric) on N MI355X, with the HBM-roofline
+"""bench.py — depth frames/s integrated at 640x480 (BASELINE.json metric) on N MI355X; with --full, the HBM-roofline
 fraction of the integrate kernel and the CPU restatement timed beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
       N > 1 without WORLD_SIZE in the environment: starts N copies of itself, one rank per GPU (RANK / LOCAL_RANK / WORLD_SIZE set)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up (W steps), times K steps, writes the outputs if asked and prints ONE JSON line: `metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step) and the workload's `config`; the fields the
+other legs fill are null.  --full runs every leg listed below as well.  --dump-outputs DIR (N = 1) writes the map the timed loop
+left after its last step as DIR/<name>.npy (dump_outputs: float32 / float64, a seeded sample of the voxels, 64 MiB at most);
+with the same arguments the inputs are the same frames in every run.
 
 N = 1 — workload BASELINE.json configs[1]: "Replica room0" stand-in — analytic 6x3x4 m box room, orbit trajectory,
 Replica intrinsics rescaled to 640x480, depth quantised to 1/6553.5 m, replica.cfg parameters (1 cm voxels, 7 cm
 truncation, GC every frame, starve every 100th).  One step = one frame through the whole VoxelContainer::integrate
 chain (allocate along rays -> frustum compaction -> depth->TSDF integrate -> GC).  `value` = frames/s with the frames
-resident in HBM before the timed region starts.  Beside it, in the same JSON line:
+resident in HBM before the timed region starts.  The orbit is 200 frames round; when W + K exceeds that, the run goes round
+again over the same 200 frames.  Beside it, in the same JSON line with --full:
   roofline            k_back (integrate + GC) on that workload: algorithmic bytes / HIP-event time of the launch; `traffic`
                       = HBM bytes per launch from rocprofv3 PMC passes of THIS workload run as sub-processes (null if
                       rocprofv3 is not available)
@@ -30,8 +37,11 @@ N > 1 — workload BASELINE.json configs[3]: "ScanNet scene0000" stand-in (furni
   `merge`: the sub-maps are folded into ONE tile-sharded map (mrh_comm_merge_submaps: all-to-all of blocks to
            their tile owner over RCCL + weighted merge on the device) and the boundary blocks exchanged
            (mrh_comm_exchange_halo): times, bytes and per-phase HIP-event times (pack, counts, collective, unpack) of both.
+  With --full, beside it:
   `tile_sharded`: the result-identical mode on the same K frames (rank 0's segment, seen by every rank; starve frames
            run their MIN all-reduce inside mrh_integrate): frames/s = K / max-over-ranks time (strong scaling).
+  `full_stream`: configs[3] whole (the 500-pose walk in N segments, one merge + one halo exchange); `roofline`: the
+           integrate kernel on rank 0's segment.
 
 No torch on this path: device buffers through mrhash_amd.hipmem (hipMalloc on the runtime the library is bound to), the
 communicator through include/mrhash_comm.h (RCCL on the library's own stream) — one HIP runtime per rank.  The only
@@ -81,16 +91,20 @@ def free_port() -> int:
     return p
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--blocks", type=int, default=262144, help="SDF block pool capacity (1.6 GB at 262144)")
-    ap.add_argument("--cpu-frames", type=int, default=64, help="frames of the same stream timed on the CPU oracle (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC sub-process passes (roofline.traffic = null)")
-    ap.add_argument("--no-extras", action="store_true", help="N=1: only the headline pass and its roofline (no mc / hbm / pcie legs)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure as well: rooflines, PMC traffic, the other legs, "
+                                                        "the CPU baseline and its parity check (N = 1); roofline, tile-sharded and full-stream legs (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="N = 1: write the map the timed loop produced (after its last step) "
+                                                                      "to DIR/<name>.npy (float32 / float64, a seeded sample of the voxels)")
+    ap.add_argument("--cpu-frames", type=int, default=64, help="with --full: frames of the same stream timed on the CPU oracle (rank 0, N=1)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 PMC sub-process passes (roofline.traffic = null)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N=1: only the headline pass and its roofline (no mc / hbm / pcie legs)")
     ap.add_argument("--pmc-inner", action="store_true", help=argparse.SUPPRESS)  # the workload alone, under rocprofv3
     ap.add_argument("--pmc-inner-big", action="store_true", help=argparse.SUPPRESS)  # the roofline_hbm workload alone
     ap.add_argument("--pmc-inner-mc", action="store_true", help=argparse.SUPPRESS)  # the multi-resolution map + two extractions
@@ -99,7 +113,12 @@ def parse_args():
     ap.add_argument("--frames-cache", default="", help=argparse.SUPPRESS)
     ap.add_argument("--multi", action="store_true", help="--gpus 1 through the N-rank function (one rank, RCCL communicator of size 1): its value must "
                                                          "equal the N = 1 line's, which is what makes value(N) / (N x value(1)) meaningful")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.multi):
+        ap.error("--dump-outputs applies to the N = 1 line (--gpus 1 without --multi)")
+    return args
 
 
 # ---- workload helpers --------------------------------------------------------------------------------------------
@@ -120,15 +139,29 @@ def render_stream(kind: str, n: int, start: int = 0, cache: str = ""):
         scene, K, poses, scaling = synth.scannet_room(), synth.SCANNET, synth.walk_poses(start + n, seed=0)[start:], 5000.0
     else:
         raise ValueError(kind)
-    frames = [synth.render(scene, K, t, q, depth_scaling=scaling) for t, q in poses]
+    # frames are independent and numpy releases the GIL inside them: a few threads render the same frames 3x faster
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0))))) as pool:
+        frames = list(pool.map(lambda p: synth.render(scene, K, p[0], p[1], depth_scaling=scaling), poses))
     if cache:
         np.savez(cache, t=np.stack([f.t for f in frames]), q=np.stack([f.q for f in frames]), R=np.stack([f.R for f in frames]),
                  depth=np.stack([f.depth for f in frames]), rgb=np.stack([f.rgb for f in frames]))
     return frames
 
 
+ORBIT_FRAMES = 200  # one revolution of synth.orbit_poses (1.8 degrees per frame)
+
+
+def replica_orbit(total: int, cache: str = ""):
+    """The N = 1 line's frames for `total` steps: the orbit's first min(total, ORBIT_FRAMES) frames.  A longer run goes round the
+    room again over the same frames (Resident.run indexes them modulo their number), so that the time and memory spent on
+    frames before the timed loop do not grow with --steps."""
+    return render_stream("replica", min(total, ORBIT_FRAMES), cache=cache)
+
+
 class Resident:
-    """A stream uploaded to HBM once; `run` feeds frames [lo, hi) through the zero-copy setters."""
+    """A stream uploaded to HBM once; `run` feeds frames [lo, hi) through the zero-copy setters (frame i is frames[i % len(frames)])."""
 
     def __init__(self, frames, K):
         from mrhash_amd import hipmem
@@ -140,8 +173,9 @@ class Resident:
         self.ds, self.rs = K.rows * K.cols * 4, K.rows * K.cols * 3
 
     def run(self, engine, lo, hi, integrate=None):
-        K = self.K
-        for i in range(lo, hi):
+        K, n = self.K, len(self.frames)
+        for g in range(lo, hi):
+            i = g % n
             f = self.frames[i]
             engine.set_pose(f.R, f.t)
             engine.set_depth_device(self.depth.ptr + i * self.ds, K.rows, K.cols)
@@ -158,6 +192,46 @@ def make_engine(hip, params, K):
     e = capi.Engine(hip, params)
     e.set_camera(K.fx, K.fy, K.cx, K.cy, K.rows, K.cols, params.min_depth, params.max_depth)
     return e
+
+
+DUMP_SAMPLE_BLOCKS = 2048  # 12 KiB of voxel fields per block: 24 MiB at most
+DUMP_MAX_BLOCKS = 1 << 19  # the per-block arrays (40 B per block): 20 MiB at most; a larger map is sampled
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, descs: np.ndarray, voxels: np.ndarray) -> dict:
+    """What a caller of the timed path receives after its last step: the map (Engine.dump_blocks, blocks in canonical (x, y, z)
+    order), as float32 / float64 arrays in out_dir/<name>.npy.  Every block's coordinates and per-block sums; the voxels of a fixed
+    sample of blocks (seeded choice of rows of the canonical order).  Returns {name: bytes}."""
+    n = len(descs)
+    rng = np.random.default_rng(0)
+
+    def pick(m):
+        return slice(None) if n <= m else np.sort(rng.choice(n, size=m, replace=False))
+
+    rows = pick(DUMP_MAX_BLOCKS)
+    d, v = descs[rows], voxels[rows]
+    seen = v["weight"] > 0
+    arrays = {
+        "block_coords": np.stack([d["x"], d["y"], d["z"]], axis=1).astype(np.float64),
+        "block_weight_sum": v["weight"].sum(axis=1, dtype=np.float64),
+        "block_sdf_sum": np.where(seen, v["sdf"], 0.0).sum(axis=1, dtype=np.float64),
+    }
+    s = pick(DUMP_SAMPLE_BLOCKS)
+    sv = voxels[s]
+    arrays.update({
+        "sample_coords": np.stack([descs["x"][s], descs["y"][s], descs["z"][s]], axis=1).astype(np.float64),
+        "sample_sdf": sv["sdf"].astype(np.float32),
+        "sample_sum_squared": sv["sum_squared"].astype(np.float32),
+        "sample_weight": sv["weight"].astype(np.float32),
+        "sample_rgb": sv["rgb"].astype(np.float32),
+    })
+    sizes = {k: int(a.nbytes) for k, a in arrays.items()}
+    assert sum(sizes.values()) <= DUMP_LIMIT_BYTES, sizes
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sizes
 
 
 def profiled_roofline(eng, res: Resident, W: int, total: int, label: str):
@@ -312,7 +386,9 @@ def bench_single(args):
     hip = capi.load_hip()  # no fallback: raises if the HIP library is missing
     Kc = synth.REPLICA_640
     params = capi.Params(num_sdf_blocks=args.blocks, device_id=0, **synth.REPLICA_PARAMS)
-    cache = args.frames_cache or os.path.join(tempfile.gettempdir(), f"mrh_bench_replica_{total}.npz")
+    # the frames of a --full run are kept in a file for its rocprofv3 sub-processes; a plain run renders them
+    inner = args.pmc_inner or args.pmc_inner_big or args.pmc_inner_mc or args.pmc_inner_lidar or args.pmc_inner_sph
+    cache = args.frames_cache or (os.path.join(tempfile.gettempdir(), f"mrh_bench_replica_{min(total, ORBIT_FRAMES)}.npz") if args.full or inner else "")
     if args.pmc_inner_big:  # the roofline_hbm workload alone (under rocprofv3 --pmc)
         big = render_stream("replica_big", total, cache=cache)
         rb = Resident(big, Kc)
@@ -333,7 +409,7 @@ def bench_single(args):
         le.sync()
         le.close()
         return
-    frames = render_stream("replica", total, cache=cache)
+    frames = replica_orbit(total, cache=cache)
     res = Resident(frames, Kc)
 
     if args.pmc_inner_mc:  # configs[2]: the multi-resolution map, then two extractions (under rocprofv3 --pmc)
@@ -367,9 +443,32 @@ def bench_single(args):
     occupied = int(st.occupied_fine)
     table = {"hash_slots": int(st.hash_slots), "tombstones": int(st.tombstones), "max_probe_length": int(st.max_probe_length), "rehash_count": int(st.rehash_count)}
     # the map the timed loop produced, kept for the check against the oracle in the cpu_baseline leg (which runs the oracle over
-    # the same frames anyway): taken now, before the profiled pass resets the engine
-    want_check = not args.no_cpu and args.cpu_frames > 0
-    timed_map = eng.dump_blocks() if want_check and min(args.cpu_frames, total) == total else None
+    # the same frames anyway) and for --dump-outputs: taken now, before the profiled pass resets the engine
+    want_check = args.full and not args.no_cpu and args.cpu_frames > 0
+    keep_map = want_check and min(args.cpu_frames, total) == total
+    timed_map = eng.dump_blocks() if keep_map or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *timed_map)
+        if not keep_map:
+            timed_map = None
+
+    out = {
+        "metric": "depth frames/sec integrated (640x480)",
+        "value": K / elapsed, "unit": "frames/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "replica-room0 stand-in 640x480, single-resolution hash TSDF integrate (alloc+compact+integrate+GC per frame, "
+                               "replica.cfg params), frames resident in HBM",
+                   "frames_per_gpu": K, "voxel_size_m": 0.01, "truncation_m": 0.07, "parallelism": "single GPU", "live_blocks_end": occupied,
+                   "hash_table": table, "distinct_frames": len(frames)},
+        "roofline": None, "roofline_hbm": None, "mc": None, "cpu_baseline": None, "parity_checked": False, "blocks": None,
+        "lidar": None, "splat": None, "pcie_inclusive_frames_per_s": None, "pcie_inclusive_frames_timed": None,
+        "h2d_link_gbs": None, "h2d_link": None, "pcie_inclusive_frac_of_link": None, "h2d_link_gbs_under_load": None,
+        "pcie_inclusive_frac_of_link_under_load": None, "periodic_frames": None, "spherical_images": None,
+    }
+    if not args.full:  # a plain run: the headline figure and nothing else
+        eng.close()
+        emit(out)
+        return
 
     # ---- the boundary as the reference uses it: host buffers -> mrh_upload_depth / mrh_upload_rgb each frame.  Runs BEFORE
     # any profiled pass: launches that carry start / stop events switch the queue to profiling mode, which slows every
@@ -379,7 +478,7 @@ def bench_single(args):
     if not args.no_extras:
         pe = make_engine(hip, params, Kc)
         for i in range(W):
-            f = frames[i]
+            f = frames[i % len(frames)]
             pe.set_pose(f.R, f.t); pe.upload_depth(f.depth); pe.upload_rgb(f.rgb); pe.integrate()
         pe.sync()
         # at least 100 frames (the timed frames again and again when --steps is smaller): a host-fed loop needs a few frames to
@@ -388,7 +487,7 @@ def bench_single(args):
         t2 = time.perf_counter()
         for _ in range(pcie_passes):
             for i in range(W, total):
-                f = frames[i]
+                f = frames[i % len(frames)]
                 pe.set_pose(f.R, f.t); pe.upload_depth(f.depth); pe.upload_rgb(f.rgb); pe.integrate()
         pe.sync()
         pcie_fps = pcie_passes * K / (time.perf_counter() - t2)
@@ -723,7 +822,7 @@ def bench_single(args):
         n_cpu = min(args.cpu_frames, total)
         tc = 0.0
         for i in range(n_cpu):
-            f = frames[i]
+            f = frames[i % len(frames)]
             ce.set_pose(f.R, f.t)
             ce.upload_depth(f.depth)
             ce.upload_rgb(f.rgb)
@@ -757,14 +856,7 @@ def bench_single(args):
                "sample": f"first {n_cpu} frames of the same 640x480 stream through the test oracle (oracle/mrh_oracle.c, gcc -O2 -fopenmp, "
                          f"allocation single-threaded: a restatement for checking results, not a tuned CPU implementation), time of mrh_integrate only"}
 
-    out = {
-        "metric": "depth frames/sec integrated (640x480)",
-        "value": K / elapsed, "unit": "frames/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "replica-room0 stand-in 640x480, single-resolution hash TSDF integrate (alloc+compact+integrate+GC per frame, "
-                               "replica.cfg params), frames resident in HBM",
-                   "frames_per_gpu": K, "voxel_size_m": 0.01, "truncation_m": 0.07, "parallelism": "single GPU", "live_blocks_end": occupied,
-                   "hash_table": table},
+    out.update({
         "roofline": roof, "roofline_hbm": roof_hbm, "mc": mc, "cpu_baseline": cpu,
         "parity_checked": bool(cpu and cpu["parity"]["ok"]), "blocks": (cpu["parity"]["blocks"] if cpu else None),
         "lidar": lidar, "splat": splat, "pcie_inclusive_frames_per_s": pcie_fps, "pcie_inclusive_frames_timed": (max(1, -(-100 // K)) * K) if pcie_fps else None,
@@ -773,7 +865,7 @@ def bench_single(args):
         "h2d_link_gbs_under_load": link.get("gbs_next_to_resident_frames") if link else None,
         "pcie_inclusive_frac_of_link_under_load": (pcie_fps * link["bytes_per_frame"] / 1e9 / link["gbs_next_to_resident_frames"]) if link and pcie_fps and link.get("gbs_next_to_resident_frames") else None,
         "periodic_frames": periodic, "spherical_images": spherical,
-    }
+    })
     emit(out)
 
 
@@ -1096,7 +1188,7 @@ def bench_multi_phases(args, grp, eng, mine, hip, params, Kc, chunk_log2, device
 
     # ---- roofline of the integrate kernel on rank 0's own segment (profiled pass on a second context; the other ranks wait)
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         pe = make_engine(hip, params, Kc)
         roof = profiled_roofline(pe, mine, W, total, f"rank 0's segment of the frame-sharded stream ({K} frames; the N = 1 line's workload)")
         roof["cache_note"] = "per-frame working set inside the 256 MiB Infinity Cache (see the N = 1 line's roofline_hbm for the kernel outside it)"
@@ -1105,7 +1197,7 @@ def bench_multi_phases(args, grp, eng, mine, hip, params, Kc, chunk_log2, device
     grp.barrier()
 
     # ---- tile-sharded fusion of ONE stream (rank 0's segment) by all ranks
-    if grp.exchanges:
+    if grp.exchanges and args.full:
         shared = mine if rank == 0 else Resident(render_stream("replica", total, start=0), Kc)
         tp = capi.Params(num_sdf_blocks=args.blocks, device_id=device_index, shard_rank=rank, shard_count=world, shard_chunk_log2=chunk_log2,
                          **synth.REPLICA_PARAMS)
@@ -1137,7 +1229,7 @@ def bench_multi_phases(args, grp, eng, mine, hip, params, Kc, chunk_log2, device
     # fuses its 500 / world frames, then ONE merge + ONE boundary-block exchange.  (`value` above amortises the same exchange over
     # --steps frames per rank: with the driver's 20 steps the all-to-all of whole sub-maps dominates it.)
     full_n = int(os.environ.get("MRH_BENCH_FULL_STREAM", "500"))
-    if grp.exchanges and full_n >= world:
+    if args.full and grp.exchanges and full_n >= world:
         per = full_n // world
         Ks = synth.SCANNET
         seg = Resident(render_stream("scannet", per, start=rank * per), Ks)

@@ -1,9 +1,11 @@
-"""bench.py keeps its contract: ONE JSON line on stdout with the driver's keys, the roofline and (when asked) the CPU baseline."""
+"""bench.py keeps its contract: ONE JSON line on stdout with the driver's keys; with --full the roofline and (when asked) the CPU
+baseline."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,7 +33,7 @@ def _single_line(steps, warmup, extra=()):
     """The N = 1 line at the given step counts, run once per module (the N > 1 tests compare their rank 0 with it)."""
     key = (steps, warmup, tuple(extra))
     if key not in _SINGLE:
-        _SINGLE[key] = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-pmc"] + list(extra))
+        _SINGLE[key] = _run(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-pmc"] + list(extra))
     return _SINGLE[key]
 
 
@@ -57,6 +59,53 @@ def test_single_gpu_line():
     assert d["parity_checked"] is True and c["parity"]["frames"] == 2 and c["parity"]["sdf_bit_exact"] and d["blocks"] == c["parity"]["oracle_blocks"] > 1000
 
 
+def _outputs(d):
+    return {fn[:-4]: np.load(os.path.join(d, fn)) for fn in sorted(os.listdir(d)) if fn.endswith(".npy")}
+
+
+def test_plain_line_is_the_headline_and_its_outputs_are_the_timed_map(tmp_path):
+    """A plain run (no --full) times the K steps and prints the line with the headline fields and null legs; --dump-outputs writes
+    the map the timed loop left, the same bits in two runs, and that map is the oracle's after the same W + K frames."""
+    W, K = 2, 4
+    lines = []
+    for tag in ("a", "b"):
+        lines.append(_run(["--gpus", "1", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path / tag)]))
+    d = lines[0]
+    assert all(k in d for k in KEYS)
+    assert d["steps"] == K and d["warmup"] == W and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 1000 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["mc"] is None and d["parity_checked"] is False
+    a, b = _outputs(tmp_path / "a"), _outputs(tmp_path / "b")
+    assert set(a) == set(b) and {"block_coords", "sample_sdf", "sample_weight"} <= set(a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert all(a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes() for k in a)
+    assert len(a["block_coords"]) == d["config"]["live_blocks_end"]
+
+    sys.path.insert(0, ROOT)
+    import bench
+    import parity_utils as pu
+    from mrhash_amd import synth
+
+    orc = pu.oracle_lib()
+    e = pu.make_engine(orc, synth.REPLICA_640, synth.REPLICA_PARAMS, 131072)
+    for f in bench.render_stream("replica", W + K):
+        pu.feed(e, f)
+    bench.dump_outputs(str(tmp_path / "oracle"), *e.dump_blocks())
+    e.close()
+    o = _outputs(tmp_path / "oracle")
+    assert np.array_equal(a["block_coords"], o["block_coords"]) and np.array_equal(a["sample_coords"], o["sample_coords"])
+    for k in ("sample_weight", "sample_rgb", "block_weight_sum"):
+        assert np.array_equal(a[k], o[k]), k
+    assert np.array_equal(a["sample_sdf"].view(np.uint32), o["sample_sdf"].view(np.uint32))
+
+
+def test_a_plain_run_longer_than_the_orbit_goes_round_it_again():
+    """--steps sets the number of timed steps whatever it is; past one revolution (200 frames) the frames repeat."""
+    d = _run(["--gpus", "1", "--steps", "230", "--warmup", "0"])
+    assert d["steps"] == 230 and d["config"]["frames_per_gpu"] == 230 and d["config"]["distinct_frames"] == 200
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6 and d["roofline"] is None
+
+
 @pytest.mark.parametrize("ranks", [2, 8])
 def test_n_ranks_on_one_device_line(ranks):
     """The N > 1 code path (self-spawned ranks, frame-sharded value, merge, tile-sharded mode) with all ranks on device 0 over
@@ -66,7 +115,7 @@ def test_n_ranks_on_one_device_line(ranks):
 
     first = None
     for attempt in range(2):
-        d = _run(["--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--blocks", "65536"],
+        d = _run(["--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--blocks", "65536", "--full"],
                  env={"MRH_BENCH_SHARE_DEVICE": "1", "MRH_BENCH_FULL_STREAM": str(6 * ranks)}, timeout=900)  # full-stream leg: 6 frames per rank here, 500 / N in a real run
         assert all(k in d for k in KEYS)
         err = d.get("phases_error")  # an exception inside the exchange phases is reported in the line, not as an exit code
@@ -109,7 +158,7 @@ def test_n_ranks_on_one_device_line(ranks):
 
 
 def _multi_one_rank(steps, warmup, env=None, full=40):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--multi", "--steps", str(steps), "--warmup", str(warmup), "--blocks", "65536"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--multi", "--steps", str(steps), "--warmup", str(warmup), "--blocks", "65536", "--full"],
                        capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MRH_BENCH_FULL_STREAM=str(full), **(env or {})))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -143,7 +192,7 @@ def test_one_rank_multi_line_agrees_with_the_single_gpu_line():
     nothing to exchange — within 5 % at the driver's step counts (best of three pairs: both sides are 0.7 ms samples)."""
     best = None
     for _ in range(3):
-        one = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-pmc", "--no-cpu", "--no-extras"])
+        one = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-pmc", "--no-cpu", "--no-extras"])
         d = _multi_one_rank(20, 5, full=0)
         assert d["ranks"] == 1 and d["rccl"]["rccl_ranks"] == 1 and d["value_definition"].startswith("one rank")
         assert d["value"] == d["fuse_only_frames_per_s"] and d["config"]["workload"].startswith("replica-room0 stand-in 640x480")
@@ -160,7 +209,7 @@ def test_value_survives_without_a_communicator():
     """The measured value must not depend on the exchange phases: with the file-based host group (what bench.py falls back to
     when the RCCL communicator cannot be created) two ranks report the frame-sharded value, the roofline of rank 0's
     segment, and say that the exchange phases were left out."""
-    d = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--blocks", "65536"], env={"MRH_BENCH_SHARE_DEVICE": "1", "MRH_BENCH_BACKEND": "host"}, timeout=900)
+    d = _run(["--gpus", "2", "--steps", "6", "--warmup", "2", "--blocks", "65536", "--full"], env={"MRH_BENCH_SHARE_DEVICE": "1", "MRH_BENCH_BACKEND": "host"}, timeout=900)
     assert all(k in d for k in KEYS)
     assert d["ranks"] == 2 and d["value"] > 1000 and d["backend"] == "host" and d["value_definition"].startswith("fuse only")
     assert d["merge"] is None and d["tile_sharded"] is None and d["roofline"]["launches"] == 6

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"; OUT=gpurun_out/$TAG; mkdir -p $OUT
 for rep in 1 2; do
   i=0
   for v in "" "$@"; do
-    env $v timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 ${AB_ARGS:-} > $OUT/line_${i}_$rep.json 2> $OUT/err_${i}_$rep.txt
+    env $v timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ${AB_ARGS:-} > $OUT/line_${i}_$rep.json 2> $OUT/err_${i}_$rep.txt
     python - <<PY
 import json
 d=json.load(open('$OUT/line_${i}_$rep.json'))

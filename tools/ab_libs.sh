@@ -13,7 +13,7 @@ for sp in "${SPECS[@]}"; do
 done
 one() {  # spec steps warmup [extra env]
   local n="${1%%@*}"
-  env $(envof $1) $4 python tools/bench_with_lib.py mrhash_amd/csrc/libmrhash_$n.so --steps $2 --warmup $3 --no-cpu --no-pmc --no-extras 2>/dev/null | grep '^{"metric' | \
+  env $(envof $1) $4 python tools/bench_with_lib.py mrhash_amd/csrc/libmrhash_$n.so --steps $2 --warmup $3 --full --no-cpu --no-pmc --no-extras 2>/dev/null | grep '^{"metric' | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-28s %-10s steps %3d: %6d fps  k_back %.2f us frac %.4f  k_front %.2f us' % ('$1', '$4', d['steps'], round(d['value']), r['kernel_ms_avg']*1000, r['frac'], r['k_front_ms_avg']*1000))"
 }
 for i in $(seq 1 $R); do

@@ -29,7 +29,7 @@ if has suite; then
   tail -32 $OUT/gpu_suite.txt
 fi
 if has bench; then
-  timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line_driver_command.json 2> $OUT/bench_driver.err
+  timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_line_driver_command.json 2> $OUT/bench_driver.err
   python - <<PY
 import json
 d=json.load(open('$OUT/bench_line_driver_command.json'))
@@ -40,9 +40,9 @@ print('lidar us', li.get('us_per_scan'), 'traffic', (li.get('roofline') or {}).g
 PY
 fi
 if has default; then  # the bench with no flags (100 steps, 10 warm-up: census and starve frames inside)
-  timeout 1200 python bench.py > $OUT/bench_line_default_run.json 2> $OUT/bench_default.err
+  timeout 1200 python bench.py --full > $OUT/bench_line_default_run.json 2> $OUT/bench_default.err
   python -c "import json; d=json.load(open('$OUT/bench_line_default_run.json')); print('default run: value', round(d['value']), 'steps', d['steps'], 'parity', d.get('parity_checked'))"
-  MRH_PIPE=0 timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-pmc --no-cpu --no-extras > $OUT/bench_line_driver_command_serial.json 2>/dev/null
+  MRH_PIPE=0 timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-pmc --no-cpu --no-extras > $OUT/bench_line_driver_command_serial.json 2>/dev/null
 fi
 if has stats; then
   stats_leg driver_cmd python bench.py --pmc-inner --steps 20 --warmup 5
@@ -115,12 +115,12 @@ PY
   cat $OUT/big_map.txt
 fi
 if has multi; then
-  MRH_BENCH_SHARE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 30 --warmup 5 --blocks 65536 > $OUT/bench_8ranks_one_device_gloo.json 2> $OUT/bench_8ranks.err
+  MRH_BENCH_SHARE_DEVICE=1 timeout 900 python bench.py --gpus 8 --steps 30 --warmup 5 --blocks 65536 --full > $OUT/bench_8ranks_one_device_gloo.json 2> $OUT/bench_8ranks.err
   head -c 600 $OUT/bench_8ranks_one_device_gloo.json; echo
   gcc -std=c11 -O1 -Iinclude examples/comm_smoke.c -o /tmp/comm_smoke -Lmrhash_amd/csrc -lmrhash_hip -Wl,-rpath,$PWD/mrhash_amd/csrc -lm
   MRH_COMM_SELF_LOOP=1 /tmp/comm_smoke 1 > $OUT/comm_smoke_1rank_self_loop.txt 2>&1; tail -3 $OUT/comm_smoke_1rank_self_loop.txt
   # one rank through the N-rank function over RCCL: its value is the N = 1 line's
-  RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 timeout 600 python bench.py --gpus 1 --multi --steps 20 --warmup 5 > $OUT/bench_1rank_rccl_multi.json 2> $OUT/bench_1rank.err
+  RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 timeout 600 python bench.py --gpus 1 --multi --steps 20 --warmup 5 --full > $OUT/bench_1rank_rccl_multi.json 2> $OUT/bench_1rank.err
   python -c "import json; d=json.load(open('$OUT/bench_1rank_rccl_multi.json')); print('one rank through bench_multi: value', round(d['value']), d['value_definition'][:80])"
 fi
 rm -f $OUT/*.log
