@@ -221,6 +221,7 @@ struct mrh_ctx {
   size_t zfused_clean_npix = 0;  // the image size the clean pairs were cleared for (a pair holds zbuf0 | zbuf1 at THAT size)
   int zfused_next = 0;
   bool starve_fused = true;  // MRH_STARVE_FUSED=0: the eight launches of rounds 1-5 (k_starve<0,1,2>, k_summarize_visible, k_free_lists)
+  bool starve_serial = false;  // MRH_STARVE_SERIAL=1: starve frames leave the pipeline (and keep the three fused launches)
   uint64_t n_starve_fused = 0;
   int4* d_realloc = nullptr;
   int4* d_reint = nullptr;
@@ -229,9 +230,7 @@ struct mrh_ctx {
   u32* d_misc = nullptr;  // 4 words for k_get_voxel
   float* d_rcp_w = nullptr;  // Fast::rcp_w
   Fast fast;              // fast path buffers
-  size_t fast_npix = 0;
-  uint2* dcx_buf = nullptr;  // {cleaned depth, packed colour} of the current frame (written by k_front)
-  // ---- pipelined frames (integrate_lazy; MRH_PIPE=0 keeps the two serial launches on one stream) ----
+  // ---- pipelined frames (integrate_single_res_frame; MRH_PIPE=0: every frame serial, the two launches on the main stream) ----
   // The front half of a frame (k_front<..., LAZY>) is launched on `stream_front`, its integration (k_back<..., LZ = 2>) on the
   // main stream behind one event; the front stream never waits for the main one, so the front half of frame g + 1 runs next to
   // the integration of frame g.  Up to kPipeRing - 1 frames are in flight, each with its own {depth, colour} image, lists,
@@ -244,14 +243,17 @@ struct mrh_ctx {
   int pipe_period = 64;                     // the reclaim (and one serial frame) every so many pipelined frames; MRH_PIPE_PERIOD.  (32 until
                                             // round 6: a period boundary costs the pipeline ~60 us, the zombies it bounds are also bounded by the
                                             // pool test below (zombies <= pool / 8); 64 — the census period — gave +4 % at 100 steps, 128 no more)
+  bool pipe_always_wait = false;            // MRH_PIPE_ALWAYS_WAIT=1: a pipelined integration always carries its wait packet (A/B)
+  // the pipelining state (ensure_pipe_state: a context with `pipe` set, at its first single-resolution frame) — the front stream,
+  // its events, ring slots 1 .. kPipeRing - 1, the want stamps, h_levels and Fast::zlist
   hipStream_t stream_front = nullptr;
   hipEvent_t ev_front[kPipeRing] = {};
-  uint2* pipe_dcx[kPipeRing] = {};
-  size_t pipe_npix = 0;
-  int4* ring_vis[kPipeRing] = {}; int4* ring_bbox[kPipeRing] = {}; int4* ring_cfree[kPipeRing] = {}; float* ring_zmin[kPipeRing] = {};  // [0] = the context's own
+  uint2* pipe_dcx[kPipeRing] = {};          // {cleaned depth, packed colour} of a frame (written by k_front), per ring slot; without the pipelining
+  size_t pipe_npix = 0;                     // state [0] alone, which every serial frame uses (ensure_frame_dcx)
+  int4* ring_vis[kPipeRing] = {}; int4* ring_bbox[kPipeRing] = {}; int4* ring_cfree[kPipeRing] = {}; float* ring_zmin[kPipeRing] = {};  // [0]: unused (ring_lists)
   u32* want_ring = nullptr;                 // kPipeRing x slots stamps
   int* h_levels = nullptr;                  // pinned {fine free-list level, zombies, sequence number of the last integration that started}
-  uint64_t pipe_seq = 0;                    // frames issued by integrate_lazy (pipelined or not)
+  uint64_t pipe_seq = 0;                    // single-resolution frames issued (pipelined or not)
   uint64_t pipe_base = 0;                   // every frame below this sequence number is known complete (host synchronised)
   int lazy_run = 0;                         // pipelined frames since the last reclaim
   bool zombies_possible = false;
@@ -280,7 +282,7 @@ struct mrh_ctx {
   int npend = 0;
   int pipe_defer = 1;                     // integrations kept back (MRH_PIPE_DEFER, 1 .. kPendMax - 1): the older a front half, the surer it has finished
   uint64_t dbg_waits = 0;
-  double dbg_spin_us = 0, dbg_api_us = 0; uint64_t dbg_lazy_frames = 0;  // MRH_DEBUG: where the host's time in integrate_lazy goes
+  double dbg_spin_us = 0, dbg_api_us = 0; uint64_t dbg_lazy_frames = 0;  // MRH_DEBUG: where the host's time in a pipelined frame goes
   int4* d_cfree = nullptr;
   // LiDAR scan of the current frame (mrh_lidar.h)
   float* d_cloud = nullptr; size_t cloud_n = 0;  // spherical camera: getDepth(cloud) image of the current frame (k_cloud_depth)
@@ -466,7 +468,7 @@ void free_all(mrh_ctx* c) {
   if (c->stream_front) (void) hipStreamSynchronize(c->stream_front);
   if (c->stream) (void) hipStreamSynchronize(c->stream);
   auto F = [](void* p) { if (p) (void) hipFree(p); };
-  F(c->dcx_buf); F(c->want_ring); F(c->fast.zlist);
+  F(c->want_ring); F(c->fast.zlist);
   for (int i = 0; i < kPipeRing; i++) { F(c->pipe_dcx[i]); if (i) { F(c->ring_vis[i]); F(c->ring_bbox[i]); F(c->ring_cfree[i]); F(c->ring_zmin[i]); } if (c->ev_front[i]) (void) hipEventDestroy(c->ev_front[i]); }
   if (c->h_levels) (void) hipHostFree(c->h_levels);
   if (c->stream_front) { (void) hipStreamSynchronize(c->stream_front); (void) hipStreamDestroy(c->stream_front); }
@@ -1402,6 +1404,8 @@ int mrh_create(const mrh_params* p, mrh_ctx** out) {
   if (const char* g = getenv("MRH_DEFER_UPLOADS")) c->defer_uploads = atoi(g) ? 1 : 0;
   if (const char* g = getenv("MRH_PIPE")) c->pipe = atoi(g) ? 1 : 0;
   if (const char* g = getenv("MRH_STARVE_FUSED")) c->starve_fused = atoi(g) != 0;
+  c->starve_serial = getenv("MRH_STARVE_SERIAL") != nullptr;
+  c->pipe_always_wait = getenv("MRH_PIPE_ALWAYS_WAIT") != nullptr;
   if (const char* g = getenv("MRH_PREWARM")) c->prewarm_on = atoi(g) != 0;
   if (const char* g = getenv("MRH_PIPE_GRID")) { const int v = atoi(g); if (v > 0 && v <= 32768) c->pipe_grid = v; }
   if (const char* g = getenv("MRH_PIPE_DEFER")) { const int v = atoi(g); if (v >= 1 && v < mrh_ctx::kPendMax) c->pipe_defer = v; }
@@ -2063,22 +2067,95 @@ int take_event_pair(mrh_ctx* c, EvPair& e) {
   return MRH_OK;
 }
 
+// the lists of ring slot i; slot 0's are the context's own (serial frames, the starve passes, frame_tail)
 Lists ring_lists(const mrh_ctx* c, const int i) {
+  if (i == 0) return Lists{c->tab.compact, c->fast.bbox, c->d_cfree, c->d_zmin, (u32) c->num_blocks};
   return Lists{c->ring_vis[i], c->ring_bbox[i], c->ring_cfree[i], c->ring_zmin[i], (u32) c->num_blocks};
 }
 
-// Behind the pipelined frames issued so far (their integrations are all on the main stream, each behind its front half), the
-// zombies nobody wanted leave the table: k_reclaim runs alone on the main stream — the front stream is idle once the last
-// integration has started, and nothing is enqueued on it before the host has seen the main stream drain (front_needs_sync).
-// the integration of the newest pipelined frame, behind its front half
+// k_back's and k_front's arguments, in the kernels' parameter order (mrh_fast2.h)
+struct BackArgs {
+  Cam c; Map m; Tab t; Fast f; Lists L;
+  int set, zero_set;
+  float thr;
+  const float* depth_raw; const uint8_t* rgb_raw; u32* deferred;  // the fused multi-resolution frame's re-integration
+  u32 want_stamp; int seq;
+};
+struct FrontArgs {
+  Cam c; Map m; Tab t; Fast f; Lists L;
+  const float* depth; const uint8_t* rgb;
+  int tiles_x, n_tiles; u32 stamp; int set, gc_on; float thr;
+  int n_refill, low_blocks_to_allocate; const int* refill_flag;  // the fused multi-resolution frame's coarse-list refill
+};
+
+// Profile mode (`ev` given): the event pair is attached to the launch itself (hipExtLaunchKernelGGL), so it holds the kernel's own
+// begin / end timestamps — the duration rocprofv3 reports — instead of a hipEventRecord bracket, which adds the dispatch latency of
+// a dependent launch (~3.5 us here) to every sample.
+template <bool FREE, bool PROFILE, bool MULTI, bool SAFEDIV, int LZ, bool SPH>
+void back_as(const int grid, hipStream_t s, const EvPair* ev, const BackArgs& a) {
+  const size_t lds = (size_t) 4 * kTileMaxPx * sizeof(uint2);  // one tile per wave
+  if (ev) hipExtLaunchKernelGGL((k_back<FREE, PROFILE, MULTI, SAFEDIV, LZ, SPH>), dim3(grid), dim3(256), (uint32_t) lds, s, ev->a, ev->b, 0u,
+                                a.c, a.m, a.t, a.f, a.L, a.set, a.zero_set, a.thr, a.depth_raw, a.rgb_raw, a.deferred, a.want_stamp, a.seq);
+  else k_back<FREE, PROFILE, MULTI, SAFEDIV, LZ, SPH><<<grid, 256, lds, s>>>(a.c, a.m, a.t, a.f, a.L, a.set, a.zero_set, a.thr, a.depth_raw, a.rgb_raw,
+                                                                             a.deferred, a.want_stamp, a.seq);
+}
+template <bool FREE, bool PROFILE, int LZ>
+void back_single_res(const bool safe_div, const bool sph, const int grid, hipStream_t s, const EvPair* ev, const BackArgs& a) {
+  if (safe_div && sph) back_as<FREE, PROFILE, false, true, LZ, true>(grid, s, ev, a);
+  else if (safe_div) back_as<FREE, PROFILE, false, true, LZ, false>(grid, s, ev, a);
+  else if (sph) back_as<FREE, PROFILE, false, false, LZ, true>(grid, s, ev, a);
+  else back_as<FREE, PROFILE, false, false, LZ, false>(grid, s, ev, a);
+}
+// The one launch site of k_back.  The runtime flags, in the kernel's template order, pick one of the instantiations the library
+// builds: single-resolution frames FREE x SAFEDIV x LZ (0: serial, 2: pipelined) x SPH, with the roofline counters (PROFILE) on
+// the profile launches of the frames that collect inline — a starve frame's profile launch carries its event pair only —; the
+// fused multi-resolution frame FREE, MULTI x SAFEDIV (never profiled, pipelined or spherical).
+void launch_back(const bool free_, const bool multi, const bool safe_div, const int lz, const bool sph, const int grid, hipStream_t s, const EvPair* ev,
+                 const BackArgs& a) {
+  if (multi) {
+    if (safe_div) back_as<true, false, true, true, 0, false>(grid, s, ev, a);
+    else back_as<true, false, true, false, 0, false>(grid, s, ev, a);
+  } else if (lz == 2) {
+    if (free_ && ev) back_single_res<true, true, 2>(safe_div, sph, grid, s, ev, a);
+    else if (free_) back_single_res<true, false, 2>(safe_div, sph, grid, s, ev, a);
+    else back_single_res<false, false, 2>(safe_div, sph, grid, s, ev, a);
+  } else {
+    if (free_ && ev) back_single_res<true, true, 0>(safe_div, sph, grid, s, ev, a);
+    else if (free_) back_single_res<true, false, 0>(safe_div, sph, grid, s, ev, a);
+    else back_single_res<false, false, 0>(safe_div, sph, grid, s, ev, a);
+  }
+}
+
+template <bool PROFILE, bool MULTI, bool LAZY, bool SPH>
+void front_as(const int grid, hipStream_t s, const EvPair* ev, const FrontArgs& a) {
+  if (ev) hipExtLaunchKernelGGL((k_front<PROFILE, MULTI, LAZY, SPH>), dim3(grid), dim3(256), 0, s, ev->a, ev->b, 0u, a.c, a.m, a.t, a.f, a.L, a.depth, a.rgb,
+                                a.tiles_x, a.n_tiles, a.stamp, a.set, a.gc_on, a.thr, a.n_refill, a.low_blocks_to_allocate, a.refill_flag);
+  else k_front<PROFILE, MULTI, LAZY, SPH><<<grid, 256, 0, s>>>(a.c, a.m, a.t, a.f, a.L, a.depth, a.rgb, a.tiles_x, a.n_tiles, a.stamp, a.set, a.gc_on, a.thr,
+                                                               a.n_refill, a.low_blocks_to_allocate, a.refill_flag);
+}
+template <bool PROFILE>
+void front_single_res(const bool lazy, const bool sph, const int grid, hipStream_t s, const EvPair* ev, const FrontArgs& a) {
+  if (lazy && sph) front_as<PROFILE, false, true, true>(grid, s, ev, a);
+  else if (lazy) front_as<PROFILE, false, true, false>(grid, s, ev, a);
+  else if (sph) front_as<PROFILE, false, false, true>(grid, s, ev, a);
+  else front_as<PROFILE, false, false, false>(grid, s, ev, a);
+}
+// The one launch site of k_front: single-resolution frames PROFILE (= a profile launch, `ev` given) x LAZY x SPH, the fused
+// multi-resolution frame MULTI alone.
+void launch_front(const bool multi, const bool lazy, const bool sph, const int grid, hipStream_t s, const EvPair* ev, const FrontArgs& a) {
+  if (multi) front_as<false, true, false, false>(grid, s, nullptr, a);
+  else if (ev) front_single_res<true>(lazy, sph, grid, s, ev, a);
+  else front_single_res<false>(lazy, sph, grid, s, nullptr, a);
+}
+
+// the integration of the oldest pending pipelined frame, behind its front half
 int launch_pending(mrh_ctx* c, const bool count_skips = false) {
   if (!c->npend) return MRH_OK;
   const mrh_ctx::PendingBack pb = c->pendq[0];  // the oldest
   for (int i = 1; i < c->npend; i++) c->pendq[i - 1] = c->pendq[i];
   c->npend--;
   hipStream_t s = c->stream;
-  static const bool always_wait = getenv("MRH_PIPE_ALWAYS_WAIT") != nullptr;  // A/B: the wait packet whatever the query says
-  const hipError_t q = always_wait ? hipErrorNotReady : hipEventQuery(c->ev_front[pb.ring]);
+  const hipError_t q = c->pipe_always_wait ? hipErrorNotReady : hipEventQuery(c->ev_front[pb.ring]);
   if (q == hipErrorNotReady) {
     (void) hipGetLastError();
     HIP_TRY(c, hipStreamWaitEvent(s, c->ev_front[pb.ring], 0));
@@ -2088,24 +2165,11 @@ int launch_pending(mrh_ctx* c, const bool count_skips = false) {
   }
   const Map& m = c->map;
   const Tab& t = c->tab;
-  const size_t lds = (size_t) 4 * kTileMaxPx * sizeof(uint2);
   if (count_skips) HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_ZSKIP], 0, sizeof(int), s));  // mrh_get_stats: M of the last frame, exactly
   if (pb.profile)  // U and M of the frame (device-side counters of the roofline numerator): after its front half, before its integration
     k_count_updates<<<c->fused_grid, 256, 0, s>>>(pb.cam, m, t, pb.f, c->d_cnt_partials, CTR_SET0 + 4 * pb.set, pb.L.vis, pb.L.cfree, pb.stamp, pb.count_zombies ? 1 : 0);
-#define MRH_KB(FREE, PROF, SAFE, SPH)                                                                                                                 \
-  do {                                                                                                                                                \
-    if (pb.profile) hipExtLaunchKernelGGL((k_back<FREE, PROF, false, SAFE, 2, SPH>), dim3(c->pipe_grid), dim3(256), (uint32_t) lds, s, pb.ev.a, pb.ev.b, 0u, pb.cam, m, t, pb.f, \
-                                          pb.L, pb.set, pb.zero_set, pb.thr, (const float*) nullptr, (const uint8_t*) nullptr, (u32*) nullptr, pb.stamp, pb.seq); \
-    else k_back<FREE, PROF, false, SAFE, 2, SPH><<<c->pipe_grid, 256, lds, s>>>(pb.cam, m, t, pb.f, pb.L, pb.set, pb.zero_set, pb.thr, nullptr, nullptr, nullptr, pb.stamp, pb.seq); \
-  } while (0)
-#define MRH_KB3(FREE, PROF, SAFE) do { if (pb.sph) MRH_KB(FREE, PROF, SAFE, true); else MRH_KB(FREE, PROF, SAFE, false); } while (0)
-#define MRH_KB2(FREE, PROF) do { if (pb.safe_div) MRH_KB3(FREE, PROF, true); else MRH_KB3(FREE, PROF, false); } while (0)
-  if (pb.free_ && pb.profile) MRH_KB2(true, true);
-  else if (pb.free_) MRH_KB2(true, false);
-  else MRH_KB2(false, false);
-#undef MRH_KB2
-#undef MRH_KB3
-#undef MRH_KB
+  launch_back(pb.free_, false, pb.safe_div, 2, pb.sph, c->pipe_grid, s, pb.profile ? &pb.ev : nullptr,
+              {pb.cam, m, t, pb.f, pb.L, pb.set, pb.zero_set, pb.thr, nullptr, nullptr, nullptr, pb.stamp, pb.seq});
   if (pb.profile) c->ev_pending.push_back(pb.ev);
   if (pb.free_) c->zombies_possible = true;
   if (pb.starve) {
@@ -2122,6 +2186,9 @@ int launch_pending(mrh_ctx* c, const bool count_skips = false) {
   return MRH_OK;
 }
 
+// Behind the pipelined frames issued so far (their integrations are all on the main stream, each behind its front half), the
+// zombies nobody wanted leave the table: k_reclaim runs alone on the main stream — the front stream is idle once the last
+// integration has started, and nothing is enqueued on it before the host has seen the main stream drain (front_needs_sync).
 int strict_point(mrh_ctx* c) {
   while (c->npend) {
     const int rc = launch_pending(c, c->npend == 1);
@@ -2147,61 +2214,75 @@ int strict_point(mrh_ctx* c) {
   return MRH_OK;
 }
 
-int ensure_pipe_buffers(mrh_ctx* c, const size_t npix) {
-  if (!c->stream_front) {
-    const size_t cap = c->num_blocks;
-    // (a high-priority front stream, a ring of eight and integrations deferred by two calls were measured: no difference)
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_front, hipStreamNonBlocking));
-    // (hipEventDisableSystemFence on these events — they order two streams of one device — was measured in round 5: no difference)
-    for (hipEvent_t& e : c->ev_front) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->ring_vis[0] = c->tab.compact; c->ring_bbox[0] = c->fast.bbox; c->ring_cfree[0] = c->d_cfree; c->ring_zmin[0] = c->d_zmin;
-    for (int i = 1; i < kPipeRing; i++) {
-      HIP_TRY(c, hipMalloc((void**) &c->ring_vis[i], cap * sizeof(int4)));
-      HIP_TRY(c, hipMalloc((void**) &c->ring_bbox[i], cap * sizeof(int4)));
-      HIP_TRY(c, hipMalloc((void**) &c->ring_cfree[i], cap * sizeof(int4)));
-      HIP_TRY(c, hipMalloc((void**) &c->ring_zmin[i], cap * sizeof(float)));
-    }
-    HIP_TRY(c, hipMalloc((void**) &c->fast.zlist, cap * sizeof(int4)));
-    HIP_TRY(c, hipMalloc((void**) &c->want_ring, (size_t) kPipeRing * c->slots * sizeof(u32)));
-    HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), c->stream));  // stamps start at 1
-    if (!c->h_levels) HIP_TRY(c, hipHostMalloc((void**) &c->h_levels, 4 * sizeof(int), hipHostMallocDefault));
-    c->h_levels[0] = (int) c->num_blocks - 1; c->h_levels[1] = 0; c->h_levels[2] = -1;
-    c->tab.h_levels = c->h_levels;
-    c->front_needs_sync = true;  // the memset above
+// the pipelining state (mrh_ctx::pipe)
+int ensure_pipe_state(mrh_ctx* c) {
+  if (c->stream_front) return MRH_OK;
+  const size_t cap = c->num_blocks;
+  // (a high-priority front stream, a ring of eight and integrations deferred by two calls were measured: no difference)
+  HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_front, hipStreamNonBlocking));
+  // (hipEventDisableSystemFence on these events — they order two streams of one device — was measured in round 5: no difference)
+  for (hipEvent_t& e : c->ev_front) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (int i = 1; i < kPipeRing; i++) {
+    HIP_TRY(c, hipMalloc((void**) &c->ring_vis[i], cap * sizeof(int4)));
+    HIP_TRY(c, hipMalloc((void**) &c->ring_bbox[i], cap * sizeof(int4)));
+    HIP_TRY(c, hipMalloc((void**) &c->ring_cfree[i], cap * sizeof(int4)));
+    HIP_TRY(c, hipMalloc((void**) &c->ring_zmin[i], cap * sizeof(float)));
   }
-  if (c->pipe_npix < npix) {
-    {
-      const int rc = strict_point(c);  // the pending integration reads the buffers that are about to go
-      if (rc) return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream_front));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint2*& d : c->pipe_dcx) { if (d) HIP_TRY(c, hipFree(d)); d = nullptr; }
-    c->pipe_npix = 0;
-    for (uint2*& d : c->pipe_dcx) HIP_TRY(c, hipMalloc((void**) &d, npix * sizeof(uint2)));
-    c->pipe_npix = npix;
-  }
+  HIP_TRY(c, hipMalloc((void**) &c->fast.zlist, cap * sizeof(int4)));
+  HIP_TRY(c, hipMalloc((void**) &c->want_ring, (size_t) kPipeRing * c->slots * sizeof(u32)));
+  HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), c->stream));  // stamps start at 1
+  if (!c->h_levels) HIP_TRY(c, hipHostMalloc((void**) &c->h_levels, 4 * sizeof(int), hipHostMallocDefault));
+  c->h_levels[0] = (int) c->num_blocks - 1; c->h_levels[1] = 0; c->h_levels[2] = -1;
+  c->tab.h_levels = c->h_levels;
+  c->front_needs_sync = true;  // the memset above
   return MRH_OK;
 }
 
-// One single-resolution pinhole frame of a pipelining context.
+// Fast::dcx of the two-launch frames, grow-only: one image per ring slot with the pipelining state, slot 0's alone without it
+int ensure_frame_dcx(mrh_ctx* c, const size_t npix) {
+  if (c->pipe_npix >= npix) return MRH_OK;
+  {
+    const int rc = strict_point(c);  // the pending integrations read the buffers that are about to go
+    if (rc) return rc;
+  }
+  if (c->stream_front) HIP_TRY(c, hipStreamSynchronize(c->stream_front));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (uint2*& d : c->pipe_dcx) { if (d) HIP_TRY(c, hipFree(d)); d = nullptr; }
+  c->pipe_npix = 0;
+  const int n = c->stream_front ? kPipeRing : 1;
+  for (int i = 0; i < n; i++) HIP_TRY(c, hipMalloc((void**) &c->pipe_dcx[i], npix * sizeof(uint2)));
+  c->pipe_npix = npix;
+  return MRH_OK;
+}
+
+// room in the pool, as the last integration launch reported it (a few frames old: the margins are generous).  Pipelining state only.
+bool pool_roomy(const mrh_ctx* c) {
+  const int64_t free_known = (int64_t) ((volatile int*) c->h_levels)[0] + 1, zombies_known = ((volatile int*) c->h_levels)[1];
+  return free_known >= (int64_t) (c->num_blocks / 4) && zombies_known <= (int64_t) (c->num_blocks / 8);
+}
+
+// One frame of a single-resolution map (pinhole or spherical camera):
 //   pipelined: front stream: k_front<LAZY> (+ event) | main stream: wait for that event, k_back<LZ = 2>.  The front stream never
 //              waits for the main one, so this frame's front half runs next to the integration of the frame(s) before it;
 //              the host only holds back when it is kPipeRing - 1 frames ahead of the integration that has started.
 //   serial:    [k_reclaim] -> k_front -> k_back (-> the starve passes), all on the main stream, no zombies anywhere.
-// A serial frame comes after anything else touched the map, every `pipe_period` frames (the reclaim bounds the zombies), on
-// starve frames, and while the pool is short of room: zombies hold their pool slots until the reclaim, so a pool that is
-// nearly full is fused serially — the reference's accounting, exactly.
-int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) {
+// A serial frame comes with MRH_PIPE=0, after anything else touched the map, every `pipe_period` frames (the reclaim bounds the
+// zombies), on starve frames that cannot stay in the pipeline, and while the pool is short of room: zombies hold their pool slots
+// until the reclaim, so a pool that is nearly full is fused serially — the reference's accounting, exactly.
+int integrate_single_res_frame(mrh_ctx* c, const int max_num_frames, const bool starve_now) {
   int rc = MRH_OK;
   hipStream_t s = c->stream;
   const Cam& k = c->cam;
   const Map& m = c->map;
   const Tab& t = c->tab;
   const size_t npix = (size_t) k.rows * k.cols;
-  rc = ensure_pipe_buffers(c, npix);
+  if (c->pipe) {
+    rc = ensure_pipe_state(c);
+    if (rc) return rc;
+  }
+  rc = ensure_frame_dcx(c, npix);
   if (rc) return rc;
-  if (c->fast_summaries_stale) {  // a general frame (spherical camera) ran since: rebuild the GC summaries once
+  if (c->fast_summaries_stale) {  // a LiDAR scan (general kernels) ran since: rebuild the GC summaries once
     rc = strict_point(c);
     if (rc) return rc;
     k_summarize_all<<<2048, 256, 0, s>>>(t, c->fast);
@@ -2210,9 +2291,6 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
   }
   const int tiles_x = (k.cols + kRayTile - 1) / kRayTile, tiles_y = (k.rows + kRayTile - 1) / kRayTile;
   const int n_tiles = tiles_x * tiles_y;
-  // room in the pool, as the last integration launch reported it (a few frames old: the margins are generous)
-  const int64_t free_known = (int64_t) ((volatile int*) c->h_levels)[0] + 1, zombies_known = ((volatile int*) c->h_levels)[1];
-  const bool roomy = free_known >= (int64_t) (c->num_blocks / 4) && zombies_known <= (int64_t) (c->num_blocks / 8);
   // a caller that synchronises (or asks for statistics, a mesh, ...) after EVERY frame gains nothing from the pipeline and would pay
   // for its flush each time: three frames in a row that found the pipeline flushed switch to serial frames, the first frame that
   // follows another frame directly switches back
@@ -2225,9 +2303,9 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
   const bool resident_inputs = c->up_depth.cur < 0 && c->up_rgb.cur < 0;
   // a starve frame stays a frame of the pipeline when its starve step can take the fused launches (round 6; before: every starve
   // frame flushed the pipeline, ran serially and left a host synchronisation in front of the next pipelined frame)
-  const bool starve_in_pipe = starve_now && starve_fused_ok(c) && !getenv("MRH_STARVE_SERIAL");
-  const bool lazy = c->pipe && (!starve_now || starve_in_pipe) && roomy && c->lazy_run < c->pipe_period && c->sync_streak < 3 && (resident_inputs || c->pipe_uploads) &&
-                    !getenv("MRH_PIPE_SERIAL");
+  const bool starve_in_pipe = starve_now && starve_fused_ok(c) && !c->starve_serial;
+  const bool lazy = c->pipe && (!starve_now || starve_in_pipe) && pool_roomy(c) && c->lazy_run < c->pipe_period && c->sync_streak < 3 &&
+                    (resident_inputs || c->pipe_uploads);
   if (!lazy) {
     rc = strict_point(c);
     if (rc) return rc;
@@ -2241,16 +2319,15 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
   c->frame_parity = set;
   c->fast_frames++;
   c->fast.dcx = c->pipe_dcx[ring];
-  c->fast.want = c->want_ring + (size_t) ring * c->slots;
+  c->fast.want = c->want_ring + (size_t) ring * c->slots;  // (no want stamps without the pipelining state: nullptr)
   const Fast f = c->fast;
   const u32 stamp = (u32) ((c->frames + 1) & 0x3FFFFFFFu);
   const float gc_thr = m.trunc + m.trunc_scale * k.max_depth;  // getTruncation(camera.maxDepth(), ...), vds.cu:1720
   const bool safe_div = m.half_vs_two_steps || m.wsum_two_steps;  // the short divisions failed their check at mrh_create
-  const int gc_on = max_num_frames > 0 ? 1 : 0;
   const bool sph = c->spherical;
+  // GC runs inside k_back unless this is a starve frame (the starve step changes weights after the integrate pass)
   c->frame_gc_inline = max_num_frames > 0 && !starve_now;
   const Lists L = ring_lists(c, ring);
-  const size_t lds = (size_t) 4 * kTileMaxPx * sizeof(uint2);
   EvPair ev = {nullptr, nullptr}, evf = {nullptr, nullptr};
   if (c->profile) {
     rc = take_event_pair(c, evf);
@@ -2258,6 +2335,7 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
     rc = take_event_pair(c, ev);
     if (rc) return rc;
   }
+  const FrontArgs front = {k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, set, max_num_frames > 0 ? 1 : 0, gc_thr, 0, 0, nullptr};
   if (lazy) {
     if (c->front_needs_sync) {  // the main stream erased keys / pushed the free list (reclaim, a serial frame, any other entry
       HIP_TRY(c, hipStreamSynchronize(s));  // point) after the front stream last looked: the front half must see all of it
@@ -2279,20 +2357,8 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
     }
     c->dbg_lazy_frames++;
     const auto t_api = std::chrono::steady_clock::now();
-    hipStream_t a = c->stream_front;
-#define MRH_KF(PROF, LAZY, SPH, STREAM)                                                                                                                \
-  do {                                                                                                                                                \
-    if (PROF) hipExtLaunchKernelGGL((k_front<PROF, false, LAZY, SPH>), dim3(n_tiles + c->sweep_wgs), dim3(256), 0, STREAM, evf.a, evf.b, 0u, k, m, t, f, L, c->d_depth, c->d_rgb, \
-                                    tiles_x, n_tiles, stamp, set, gc_on, gc_thr, 0, 0, (const int*) nullptr);                                          \
-    else k_front<PROF, false, LAZY, SPH><<<n_tiles + c->sweep_wgs, 256, 0, STREAM>>>(k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, set, gc_on, gc_thr, 0, 0, nullptr); \
-  } while (0)
-#define MRH_KF2(LAZY, STREAM)                                                                                                                         \
-  do {                                                                                                                                                \
-    if (c->profile && sph) MRH_KF(true, LAZY, true, STREAM); else if (c->profile) MRH_KF(true, LAZY, false, STREAM);                                   \
-    else if (sph) MRH_KF(false, LAZY, true, STREAM); else MRH_KF(false, LAZY, false, STREAM);                                                          \
-  } while (0)
-    MRH_KF2(true, a);
-    HIP_TRY(c, hipEventRecord(c->ev_front[ring], a));
+    launch_front(false, true, sph, n_tiles + c->sweep_wgs, c->stream_front, c->profile ? &evf : nullptr, front);
+    HIP_TRY(c, hipEventRecord(c->ev_front[ring], c->stream_front));
     if (c->profile) c->ev_pending_front.push_back(evf);
     // the integration of the PREVIOUS pipelined frame goes out now (its front half ran a frame ago: usually no wait), this
     // frame's is left for the next call
@@ -2319,27 +2385,13 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
   }
   // ---- serial frame, all on the main stream (strict_point above has flushed and reclaimed)
   c->last_frame_lazy = false;
-  MRH_KF2(false, s);
-#undef MRH_KF2
-#undef MRH_KF
+  launch_front(false, false, sph, n_tiles + c->sweep_wgs, s, c->profile ? &evf : nullptr, front);
   if (c->profile) {
     c->ev_pending_front.push_back(evf);
     k_count_updates<<<c->fused_grid, 256, 0, s>>>(k, m, t, f, c->d_cnt_partials, CTR_SET0 + 4 * set, L.vis, L.cfree, stamp, 0);
   }
-#define MRH_KB(FREE, PROF, SAFE, SPH)                                                                                                                 \
-  do {                                                                                                                                                \
-    if (c->profile) hipExtLaunchKernelGGL((k_back<FREE, PROF, false, SAFE, 0, SPH>), dim3(c->fused_grid), dim3(256), (uint32_t) lds, s, ev.a, ev.b, 0u, k, m, t, f, L, \
-                                          set, zero_set, gc_thr, (const float*) nullptr, (const uint8_t*) nullptr, (u32*) nullptr, stamp, seq);        \
-    else k_back<FREE, PROF, false, SAFE, 0, SPH><<<c->fused_grid, 256, lds, s>>>(k, m, t, f, L, set, zero_set, gc_thr, nullptr, nullptr, nullptr, stamp, seq); \
-  } while (0)
-#define MRH_KB3(FREE, PROF, SAFE) do { if (sph) MRH_KB(FREE, PROF, SAFE, true); else MRH_KB(FREE, PROF, SAFE, false); } while (0)
-#define MRH_KB2(FREE, PROF) do { if (safe_div) MRH_KB3(FREE, PROF, true); else MRH_KB3(FREE, PROF, false); } while (0)
-  if (c->frame_gc_inline && c->profile) MRH_KB2(true, true);
-  else if (c->frame_gc_inline) MRH_KB2(true, false);
-  else MRH_KB2(false, false);
-#undef MRH_KB2
-#undef MRH_KB3
-#undef MRH_KB
+  launch_back(c->frame_gc_inline, false, safe_div, 0, sph, c->fused_grid, s, c->profile ? &ev : nullptr,
+              {k, m, t, f, L, set, zero_set, gc_thr, nullptr, nullptr, nullptr, stamp, seq});
   c->front_needs_sync = true;  // direct frees on the main stream
   if (c->profile) c->ev_pending.push_back(ev);
   if (starve_now && starve_fused_ok(c)) {
@@ -2348,6 +2400,98 @@ int integrate_lazy(mrh_ctx* c, const int max_num_frames, const bool starve_now) 
     c->frames++;  // frame_tail's bookkeeping: the summaries and the garbage collection ran inside the tail launch
     return MRH_OK;
   }
+  return starve_and_tail(c, max_num_frames);
+}
+
+// One fused frame of a multi-resolution map, on the main stream: k_front<MULTI> (with the coarse-list refill, vds.cu:885-891),
+// k_back<MULTI> (GC inline, the re-integration of what checkVarSDF reallocated), k_mr_tail.
+int integrate_fused_mr_frame(mrh_ctx* c, const int max_num_frames) {
+  hipStream_t s = c->stream;
+  const Cam& k = c->cam;
+  const Map& m = c->map;
+  const Tab& t = c->tab;
+  int rc = ensure_frame_dcx(c, (size_t) k.rows * k.cols);
+  if (rc) return rc;
+  c->fast.dcx = c->pipe_dcx[0];
+  const Fast& f = c->fast;
+  const int parity = (int) (c->fast_frames % kListSets), zero_set = (parity + kListSets - 1) % kListSets;  // the frame's list-counter set, and the one to clear
+  c->frame_parity = parity;
+  c->fast_frames++;
+  const u32 stamp = (u32) ((c->frames + 1) & 0x3FFFFFFFu);
+  const float gc_thr = m.trunc + m.trunc_scale * k.max_depth;  // getTruncation(camera.maxDepth(), ...), vds.cu:1720
+  const Lists L = ring_lists(c, 0);
+  const bool safe_div = m.half_vs_two_steps || m.wsum_two_steps;  // the short divisions failed their check at mrh_create
+  const int tiles_x = (k.cols + kRayTile - 1) / kRayTile, tiles_y = (k.rows + kRayTile - 1) / kRayTile;
+  const int n_tiles = tiles_x * tiles_y;
+  if (!c->mr_summaries_valid) {
+    k_summarize_all<<<2048, 256, 0, s>>>(t, f);
+    c->mr_summaries_valid = true;
+  }
+  c->frame_gc_inline = true;
+  // the coarse-list refill rides in k_front; its test was taken by the previous frame's k_mr_tail unless something else touched
+  // the coarse list since (general frames, import, stream-out, reset)
+  if (!c->refill_flag_valid) k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
+  const int n_refill = (c->low_blocks_to_allocate + 255) / 256;
+  launch_front(true, false, false, n_tiles + c->sweep_wgs_mr + n_refill, s, nullptr,
+               {k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, parity, 1, gc_thr, n_refill, c->low_blocks_to_allocate, c->d_flag});
+  launch_back(true, true, safe_div, 0, false, c->fused_grid, s, nullptr,
+              {k, m, t, f, L, parity, zero_set, gc_thr, c->d_depth, c->d_rgb, (u32*) c->d_reint, 0u, 0});
+  k_mr_tail<<<1, 256, 0, s>>>(t, (const u32*) c->d_reint, c->low_blocks_to_allocate, c->d_flag);
+  rc = starve_and_tail(c, max_num_frames);
+  c->refill_flag_valid = rc == MRH_OK;
+  return rc;
+}
+
+// One frame of a multi-resolution map through the general kernels (mrh_kernels.h), on the main stream.
+int integrate_general_frame(mrh_ctx* c, const int max_num_frames) {
+  hipStream_t s = c->stream;
+  const Cam& k = c->cam;
+  const Map& m = c->map;
+  const Tab& t = c->tab;
+  // vds.cu:885-891 (coarse free-list refill), decided on the device
+  k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
+  k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
+  // the image every kernel below reads as "depth": the raw image (pinhole: cloud z == depth, cleaned on the fly) or, for
+  // the spherical model, getDepth(cloud) computed once per frame
+  const float* depth_img = c->d_depth;
+  if (c->spherical) {
+    const size_t npix = (size_t) k.rows * k.cols;
+    if (c->cloud_n < npix) {
+      HIP_TRY(c, hipStreamSynchronize(s));
+      if (c->d_cloud) HIP_TRY(c, hipFree(c->d_cloud));
+      c->d_cloud = nullptr;
+      HIP_TRY(c, hipMalloc((void**) &c->d_cloud, npix * sizeof(float)));
+      c->cloud_n = npix;
+    }
+    k_cloud_depth<<<(int) ((npix + 255) / 256), 256, 0, s>>>(k, c->d_depth, c->d_cloud);
+    depth_img = c->d_cloud;
+  }
+  const dim3 tiles((k.cols + kTile - 1) / kTile, (k.rows + kTile - 1) / kTile);
+  if (c->profile) k_alloc<true><<<tiles, dim3(kTile, kTile), 0, s>>>(k, m, t, depth_img);
+  else k_alloc<false><<<tiles, dim3(kTile, kTile), 0, s>>>(k, m, t, depth_img);
+  k_compact<<<512, 256, 0, s>>>(k, m, t, 1);
+
+  if (c->profile) {
+    EvPair ev;
+    const int rc = take_event_pair(c, ev);
+    if (rc) return rc;
+    HIP_TRY(c, hipEventRecord(ev.a, s));
+    k_integrate<true><<<c->integrate_grid, 512, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_upd_partials);
+    HIP_TRY(c, hipEventRecord(ev.b, s));
+    c->ev_pending.push_back(ev);
+  } else {
+    k_integrate<false><<<c->integrate_grid, 512, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_upd_partials);
+  }
+
+  if (c->frames > 0) {
+    // checkVarSDF -> reallocBlocks -> flatAndReduceHashTable(camera) -> reintegrateDepthMap
+    HIP_TRY(c, hipMemsetAsync(&t.ctr[CTR_NREALLOC], 0, 2 * sizeof(int), s));  // NREALLOC, NREINT
+    k_check_var<<<2048, 64, 0, s>>>(m, t, c->d_realloc);
+    k_realloc<<<64, 256, 0, s>>>(t, c->d_realloc, c->d_reint);
+    k_compact<<<512, 256, 0, s>>>(k, m, t, 1);
+    k_reintegrate<<<1024, 64, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_reint);
+  }
+
   return starve_and_tail(c, max_num_frames);
 }
 
@@ -2405,7 +2549,6 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
   const int max_num_frames = n_frames_invalidate < 0 ? c->p.n_frames_invalidate_voxels : n_frames_invalidate;
   hipStream_t s = c->stream;
   const Tab& t = c->tab;
-  const Map& m = c->map;
   // the table upkeep rebuilds from the descriptors: the zombies of the pipelined frames leave first
   if (c->zombies_possible && c->census_period >= 0 && (c->table_dirty || c->frames_since_census >= (uint64_t) c->census_period)) {
     rc = strict_point(c);
@@ -2423,13 +2566,12 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
   const bool starve_now = max_num_frames > 0 && c->frames > 0 && c->frames % (uint64_t) max_num_frames == 0;
   c->frame_fused_mr = t.multi_res && c->mr_fused && !c->profile && max_num_frames > 0 && !starve_now && !c->mr_next_general &&
                       c->frames >= 2 && !c->spherical;
-  c->frame_general = t.multi_res && !c->frame_fused_mr;  // (round 4: single-resolution maps take the two launches under the spherical model, too)
+  c->frame_general = t.multi_res && !c->frame_fused_mr;  // (a frame of a single-resolution map always takes the two launches)
   if (t.multi_res && !c->frame_fused_mr) {
     c->mr_summaries_valid = false;
     c->mr_next_general = starve_now || c->frames == 0;
     c->refill_flag_valid = false;
   }
-  const bool pipe_frame = (c->pipe || c->spherical) && !c->frame_general && !t.multi_res;  // integrate_lazy also carries the spherical model's serial frames
   if (max_num_frames > 0 && starve_fused_ok(c) && c->zfused_n < (size_t) k.rows * k.cols) {
     // the z-buffers of the starve frames, both pairs empty, while the context is still allocating (not inside its first starve frame)
     const size_t npix = (size_t) k.rows * k.cols;
@@ -2442,162 +2584,11 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
     c->zfused_clean[0] = c->zfused_clean[1] = true;
     c->zfused_clean_npix = npix;
   }
-  if (!pipe_frame) {  // a frame of another kind follows pipelined ones
-    rc = strict_point(c);
-    if (rc) return rc;
-  }
-  if (pipe_frame) return integrate_lazy(c, max_num_frames, starve_now);
+  // the frame's kind: the two launches of a single-resolution map (pipelined or serial), a fused or a general multi-resolution frame
+  if (!t.multi_res) return integrate_single_res_frame(c, max_num_frames, starve_now);
   rc = send_uploads(c, s);  // the frame's kernels read the images on the main stream
   if (rc) return rc;
-  if (!c->frame_general) {
-    // ---- fast path: alloc + sweep -> fused integrate / summary / GC (mrh_fast2.h)
-    if (!t.multi_res && c->fast_summaries_stale) {  // a general frame (spherical camera) ran since: rebuild the GC summaries once
-      k_summarize_all<<<2048, 256, 0, s>>>(t, c->fast);
-      c->fast_summaries_stale = false;
-    }
-    const size_t npix = (size_t) k.rows * k.cols;
-    const int tiles_x = (k.cols + kRayTile - 1) / kRayTile, tiles_y = (k.rows + kRayTile - 1) / kRayTile;
-    if (c->fast_npix < npix) {
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (c->dcx_buf) HIP_TRY(c, hipFree(c->dcx_buf));
-      c->dcx_buf = nullptr;
-      HIP_TRY(c, hipMalloc((void**) &c->dcx_buf, npix * sizeof(uint2)));
-      c->fast_npix = npix;
-    }
-    c->fast.dcx = c->dcx_buf;
-    const Fast& f = c->fast;
-    const int parity = (int) (c->fast_frames % kListSets), zero_set = (parity + kListSets - 1) % kListSets;  // the frame's list-counter set, and the one to clear
-    c->frame_parity = parity;
-    c->fast_frames++;
-    const u32 stamp = (u32) ((c->frames + 1) & 0x3FFFFFFFu);
-    const float gc_thr = m.trunc + m.trunc_scale * k.max_depth;  // getTruncation(camera.maxDepth(), ...), vds.cu:1720
-    const Lists L = {t.compact, c->fast.bbox, c->d_cfree, c->d_zmin, (u32) c->num_blocks};
-    const bool safe_div = m.half_vs_two_steps || m.wsum_two_steps;  // the short divisions failed their check at mrh_create
-    const int n_tiles = tiles_x * tiles_y;
-    const size_t lds = (size_t) 4 * kTileMaxPx * sizeof(uint2);
-    if (c->frame_fused_mr) {
-      if (!c->mr_summaries_valid) {
-        k_summarize_all<<<2048, 256, 0, s>>>(t, f);
-        c->mr_summaries_valid = true;
-      }
-      c->frame_gc_inline = true;
-      // the coarse-list refill (vds.cu:885-891) rides in k_front; its test was taken by the previous frame's k_mr_tail
-      // unless something else touched the coarse list since (general frames, import, stream-out, reset)
-      if (!c->refill_flag_valid) k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-      const int n_refill = (c->low_blocks_to_allocate + 255) / 256;
-      k_front<false, true><<<n_tiles + c->sweep_wgs_mr + n_refill, 256, 0, s>>>(k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, parity, 1, gc_thr,
-                                                                                   n_refill, c->low_blocks_to_allocate, c->d_flag);
-      if (safe_div) k_back<true, false, true, true><<<c->fused_grid, 256, lds, s>>>(k, m, t, f, L, parity, zero_set, gc_thr, c->d_depth, c->d_rgb, (u32*) c->d_reint, 0u, 0);
-      else k_back<true, false, true, false><<<c->fused_grid, 256, lds, s>>>(k, m, t, f, L, parity, zero_set, gc_thr, c->d_depth, c->d_rgb, (u32*) c->d_reint, 0u, 0);
-      k_mr_tail<<<1, 256, 0, s>>>(t, (const u32*) c->d_reint, c->low_blocks_to_allocate, c->d_flag);
-      rc = starve_and_tail(c, max_num_frames);
-      c->refill_flag_valid = rc == MRH_OK;
-      return rc;
-    }
-    // GC runs inside k_back unless this is a starve frame (the starve step changes weights after the integrate pass)
-    c->frame_gc_inline = max_num_frames > 0 && !starve_now;
-    auto take_events = [&](EvPair& e) -> int {
-      if (!c->ev_pool.empty()) { e = c->ev_pool.back(); c->ev_pool.pop_back(); return MRH_OK; }
-      if (c->ev_pending.size() >= 4096) {
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const int r = drain_events(c);
-        if (r) return r;
-        e = c->ev_pool.back(); c->ev_pool.pop_back();
-        return MRH_OK;
-      }
-      HIP_TRY(c, hipEventCreate(&e.a)); HIP_TRY(c, hipEventCreate(&e.b));
-      return MRH_OK;
-    };
-    if (c->profile) {  // event pair attached to the launch, as for k_back below
-      EvPair evf;
-      rc = take_events(evf);
-      if (rc) return rc;
-      hipExtLaunchKernelGGL((k_front<true, false>), dim3(n_tiles + c->sweep_wgs), dim3(256), 0, s, evf.a, evf.b, 0u, k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, parity,
-                            max_num_frames > 0 ? 1 : 0, gc_thr, 0, 0, (const int*) nullptr);
-      c->ev_pending_front.push_back(evf);
-    }
-    else k_front<false, false><<<n_tiles + c->sweep_wgs, 256, 0, s>>>(k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, parity, max_num_frames > 0 ? 1 : 0, gc_thr, 0, 0, nullptr);
-    EvPair ev;
-    if (c->profile) {
-      k_count_updates<<<c->fused_grid, 256, 0, s>>>(k, m, t, f, c->d_cnt_partials, CTR_SET0 + 4 * parity, L.vis, L.cfree, 0u, 0);
-      rc = take_events(ev);
-      if (rc) return rc;
-    }
-    // Profile mode: the event pair is attached to the launch itself (hipExtLaunchKernelGGL), so it holds the kernel's own
-    // begin / end timestamps — the duration rocprofv3 reports — instead of a hipEventRecord bracket, which adds the
-    // dispatch latency of a dependent launch (~3.5 us here) to every sample.
-#define MRH_K_BACK_V(FREE, PROF, SAFE)                                                                                                   \
-  do {                                                                                                                                   \
-    if (c->profile) hipExtLaunchKernelGGL((k_back<FREE, PROF, false, SAFE>), dim3(c->fused_grid), dim3(256), (uint32_t) lds, s, ev.a, ev.b, 0u, k, m, t, f, L,   \
-                                          parity, zero_set, gc_thr, (const float*) nullptr, (const uint8_t*) nullptr, (u32*) nullptr, 0u, 0);  \
-    else k_back<FREE, PROF, false, SAFE><<<c->fused_grid, 256, lds, s>>>(k, m, t, f, L, parity, zero_set, gc_thr, nullptr, nullptr, nullptr, 0u, 0); \
-  } while (0)
-#define MRH_K_BACK(FREE, PROF) do { if (safe_div) MRH_K_BACK_V(FREE, PROF, true); else MRH_K_BACK_V(FREE, PROF, false); } while (0)
-    if (c->frame_gc_inline && c->profile) MRH_K_BACK(true, true);
-    else if (c->frame_gc_inline) MRH_K_BACK(true, false);
-    else MRH_K_BACK(false, false);
-#undef MRH_K_BACK
-#undef MRH_K_BACK_V
-    if (c->profile) c->ev_pending.push_back(ev);
-    if (starve_now && starve_fused_ok(c)) {
-      rc = launch_starve_fused(c, k, f, L, parity, gc_thr, stamp, 0);
-      if (rc) return rc;
-      c->frames++;
-      return MRH_OK;
-    }
-    return starve_and_tail(c, max_num_frames);
-  }
-
-  if (t.multi_res) {
-    // vds.cu:885-891 (coarse free-list refill), decided on the device
-    k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-    k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-  }
-  // the image every kernel below reads as "depth": the raw image (pinhole: cloud z == depth, cleaned on the fly) or, for
-  // the spherical model, getDepth(cloud) computed once per frame
-  const float* depth_img = c->d_depth;
-  if (c->spherical) {
-    const size_t npix = (size_t) k.rows * k.cols;
-    if (c->cloud_n < npix) {
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (c->d_cloud) HIP_TRY(c, hipFree(c->d_cloud));
-      c->d_cloud = nullptr;
-      HIP_TRY(c, hipMalloc((void**) &c->d_cloud, npix * sizeof(float)));
-      c->cloud_n = npix;
-    }
-    k_cloud_depth<<<(int) ((npix + 255) / 256), 256, 0, s>>>(k, c->d_depth, c->d_cloud);
-    depth_img = c->d_cloud;
-  }
-  const dim3 tiles((k.cols + kTile - 1) / kTile, (k.rows + kTile - 1) / kTile);
-  if (c->profile) k_alloc<true><<<tiles, dim3(kTile, kTile), 0, s>>>(k, m, t, depth_img);
-  else k_alloc<false><<<tiles, dim3(kTile, kTile), 0, s>>>(k, m, t, depth_img);
-  k_compact<<<512, 256, 0, s>>>(k, m, t, 1);
-
-  if (c->profile) {
-    EvPair ev;
-    if (!c->ev_pool.empty()) { ev = c->ev_pool.back(); c->ev_pool.pop_back(); }
-    else {
-      if (c->ev_pending.size() >= 4096) { HIP_TRY(c, hipStreamSynchronize(s)); rc = drain_events(c); if (rc) return rc; ev = c->ev_pool.back(); c->ev_pool.pop_back(); }
-      else { HIP_TRY(c, hipEventCreate(&ev.a)); HIP_TRY(c, hipEventCreate(&ev.b)); }
-    }
-    HIP_TRY(c, hipEventRecord(ev.a, s));
-    k_integrate<true><<<c->integrate_grid, 512, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_upd_partials);
-    HIP_TRY(c, hipEventRecord(ev.b, s));
-    c->ev_pending.push_back(ev);
-  } else {
-    k_integrate<false><<<c->integrate_grid, 512, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_upd_partials);
-  }
-
-  if (t.multi_res && c->frames > 0) {
-    // checkVarSDF -> reallocBlocks -> flatAndReduceHashTable(camera) -> reintegrateDepthMap
-    HIP_TRY(c, hipMemsetAsync(&t.ctr[CTR_NREALLOC], 0, 2 * sizeof(int), s));  // NREALLOC, NREINT
-    k_check_var<<<2048, 64, 0, s>>>(m, t, c->d_realloc);
-    k_realloc<<<64, 256, 0, s>>>(t, c->d_realloc, c->d_reint);
-    k_compact<<<512, 256, 0, s>>>(k, m, t, 1);
-    k_reintegrate<<<1024, 64, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_reint);
-  }
-
-  return starve_and_tail(c, max_num_frames);
+  return c->frame_fused_mr ? integrate_fused_mr_frame(c, max_num_frames) : integrate_general_frame(c, max_num_frames);
 }
 
 }  // extern "C"
