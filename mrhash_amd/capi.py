@@ -129,6 +129,15 @@ COMM_SYMBOLS = (
 COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
 
+# every symbol include/mrhash_raycast.h declares (the HIP library only: the oracle does not render)
+RAYCAST_SYMBOLS = ("mrh_raycast mrh_raycast_device").split()
+RAYCAST_NORMALS, RAYCAST_COLORS = 1, 2
+
+
+class MrhRaycastParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float), ("outputs", C.c_uint32)]
+
 
 class MrhCommStatus(C.Structure):
     _fields_ = [("rccl_ranks", C.c_int), ("rccl_rank", C.c_int), ("rccl_device", C.c_int), ("rccl_version", C.c_int), ("async_error", C.c_int),
@@ -222,6 +231,11 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         for name in COMM_SYMBOLS:
             if name != "mrh_comm_last_error":
                 getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_raycast"):  # include/mrhash_raycast.h
+        lib.mrh_raycast.argtypes = [C.c_void_p, P(MrhRaycastParams), P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
+        lib.mrh_raycast_device.argtypes = [C.c_void_p, P(MrhRaycastParams), P(C.c_float), P(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in RAYCAST_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
     return lib
 
 
@@ -657,6 +671,42 @@ class Engine:
         n = C.c_uint64()
         self._check(self.lib.mrh_selftest_division(self._ctx, samples, seed, C.byref(n)))
         return int(n.value)
+
+    # -- rendering (include/mrhash_raycast.h) ------------------------------------------------------
+    @staticmethod
+    def _raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, normals, colors):
+        p = MrhRaycastParams(fx, fy, cx, cy, int(rows), int(cols), min_depth, max_depth, step,
+                             (RAYCAST_NORMALS if normals else 0) | (RAYCAST_COLORS if colors else 0))
+        R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        return p, R, t
+
+    def raycast(self, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, normals=True, colors=True):
+        """Renders the map from the camera-to-world pose (R, t) with a pinhole camera (mrh_raycast).  Returns
+        numpy copies (depth f32 [rows, cols], normals f32 [rows, cols, 3] or None, rgb u8 [rows, cols, 3] or None); a pixel
+        without a hit is 0 in all three.  step = 0: half the context's truncation."""
+        p, R, t = self._raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, normals, colors)
+        pd, pn, pc = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        F = C.POINTER(C.c_float)
+        self._check(self.lib.mrh_raycast(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), C.byref(pd),
+                                         C.byref(pn) if normals else None, C.byref(pc) if colors else None))
+        n = int(rows) * int(cols)
+
+        def arr(ptr, count, dt, shape):
+            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).reshape(shape).copy()
+
+        depth = arr(pd, n, np.float32, (rows, cols))
+        nrm = arr(pn, 3 * n, np.float32, (rows, cols, 3)) if normals else None
+        rgb = arr(pc, 3 * n, np.uint8, (rows, cols, 3)) if colors else None
+        return depth, nrm, rgb
+
+    def raycast_device(self, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, d_depth=0, d_normals=0, d_rgb=0):
+        """mrh_raycast_device: enqueues the render into caller device buffers (integer pointers, e.g. hipmem.DeviceBuffer.ptr;
+        0 = skip that image).  Ordered on the context's stream; finished by sync() or any blocking call."""
+        p, R, t = self._raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, bool(d_normals), bool(d_rgb))
+        F = C.POINTER(C.c_float)
+        self._check(self.lib.mrh_raycast_device(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), d_depth or None,
+                                                d_normals or None, d_rgb or None))
 
     def get_voxel(self, vx: int, vy: int, vz: int):
         out = np.zeros(1, dtype=VOXEL_DTYPE)

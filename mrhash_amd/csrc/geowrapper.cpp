@@ -114,22 +114,29 @@ void GeoWrapper::mergeSubmaps() {
   tile_sharded_ = true;
 }
 
-void GeoWrapper::setCurrPose(const std::array<float, 3>& t, const std::array<float, 4>& q) {
-  // Eigen::Quaternionf(qw,qx,qy,qz).toRotationMatrix() (Eigen 3.4.0 Quaternion.h), float arithmetic, no normalisation
+namespace {
+// Eigen::Quaternionf(qw,qx,qy,qz).toRotationMatrix() (Eigen 3.4.0 Quaternion.h), float arithmetic, no normalisation
+std::array<float, 16> pose_from(const std::array<float, 3>& t, const std::array<float, 4>& q) {
   const float x = q[0], y = q[1], z = q[2], w = q[3];
   const float tx = 2.f * x, ty = 2.f * y, tz = 2.f * z;
   const float twx = tx * w, twy = ty * w, twz = tz * w;
   const float txx = tx * x, txy = ty * x, txz = tz * x;
   const float tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  pose_ = {1.f - (tyy + tzz), txy - twz, txz + twy, t[0],
-           txy + twz, 1.f - (txx + tzz), tyz - twx, t[1],
-           txz - twy, tyz + twx, 1.f - (txx + tyy), t[2],
-           0.f, 0.f, 0.f, 1.f};
+  return {1.f - (tyy + tzz), txy - twz, txz + twy, t[0],
+          txy + twz, 1.f - (txx + tzz), tyz - twx, t[1],
+          txz - twy, tyz + twx, 1.f - (txx + tyy), t[2],
+          0.f, 0.f, 0.f, 1.f};
 }
+}  // namespace
+
+void GeoWrapper::setCurrPose(const std::array<float, 3>& t, const std::array<float, 4>& q) { pose_ = pose_from(t, q); }
 
 void GeoWrapper::setCamera(float fx, float fy, float cx, float cy, int rows, int cols, float min_depth, float max_depth, int camera_model) {
   check(mrh_set_camera(ctx_, fx, fy, cx, cy, rows, cols, min_depth, max_depth, camera_model), "setCamera");
   max_depth_ = max_depth;
+  has_camera_ = true;
+  camera_model_ = camera_model; camera_rows_ = rows; camera_cols_ = cols;
+  camera_fx_ = fx; camera_fy_ = fy; camera_cx_ = cx; camera_cy_ = cy; camera_min_depth_ = min_depth;
   // Streaming radius.  The reference uses max_depth itself (geowrapper.cpp:138), which is the z-range of a pinhole frame,
   // not its reach: a voxel at z = max_depth in an image corner is farther from the camera centre than that, so blocks
   // still inside the frustum can be paged out and then re-created empty.  Here the radius is the true reach of a frame:
@@ -508,6 +515,34 @@ void GeoWrapper::streamAllOut() {
   // then walks the grid chunk by chunk.  With 288 GB of HBM the whole map is extracted in one pass instead
   // (extractMesh brings back whatever the streamer paged out), so this only drains the stream.
   check(mrh_sync(ctx_), "streamAllOut");
+}
+
+GeoWrapper::RaycastImages GeoWrapper::raycast() { return raycastPose(pose_); }
+
+GeoWrapper::RaycastImages GeoWrapper::raycast(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastPose(pose_from(t, q)); }
+
+GeoWrapper::RaycastImages GeoWrapper::raycastPose(const std::array<float, 16>& pose) {
+  if (!has_camera_) throw std::runtime_error("GeoWrapper::raycast | setCamera has not been called");
+  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::raycast | pinhole cameras only (the camera is spherical)");
+  mrh_raycast_params p;
+  std::memset(&p, 0, sizeof p);
+  p.fx = camera_fx_; p.fy = camera_fy_; p.cx = camera_cx_; p.cy = camera_cy_;
+  p.rows = camera_rows_; p.cols = camera_cols_;
+  p.min_depth = camera_min_depth_; p.max_depth = max_depth_;
+  p.step = 0.f;  // half the truncation
+  p.outputs = MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS;
+  const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
+  const float t[3] = {pose[3], pose[7], pose[11]};
+  const float *depth = nullptr, *normals = nullptr;
+  const uint8_t* rgb = nullptr;
+  check(mrh_raycast(ctx_, &p, R, t, &depth, &normals, &rgb), "raycast");
+  RaycastImages out;
+  out.rows = p.rows; out.cols = p.cols;
+  const size_t n = (size_t) p.rows * (size_t) p.cols;
+  out.depth.assign(depth, depth + n);
+  out.normals.assign(normals, normals + 3 * n);
+  out.colors.assign(rgb, rgb + 3 * n);
+  return out;
 }
 
 void GeoWrapper::clearBuffers() {

@@ -12,6 +12,7 @@
 
 #include "mrhash_hip.h"
 #include "mrhash_comm.h"
+#include "mrhash_raycast.h"
 
 namespace pygeowrapper {
 
@@ -89,6 +90,19 @@ public:
   void GSFinalOpt();
   const std::vector<mrh_splat_seed>& splatSeeds() const { return seeds_; }  // accumulated over compute() calls
 
+  // ---- rendering (include/mrhash_raycast.h; no reference counterpart): the map seen by the camera of the last setCamera
+  // (intrinsics, rows, cols, min and max depth), from the current pose (getCurrPose) or from (t, q) converted as setCurrPose
+  // does.  depth [rows * cols] (camera z, metres), normals [rows * cols * 3] (world frame), colors [rows * cols * 3], row-major;
+  // a pixel without a hit is 0 in all three.  A spherical camera throws std::runtime_error.  Blocks paged out to the host
+  // grid (stream(), streamAllOut()) are not on the device and are not rendered.
+  struct RaycastImages {
+    int rows = 0, cols = 0;
+    std::vector<float> depth, normals;
+    std::vector<uint8_t> colors;
+  };
+  RaycastImages raycast();
+  RaycastImages raycast(const std::array<float, 3>& t, const std::array<float, 4>& q);
+
   // ---- multi-GPU (include/mrhash_comm.h; no reference counterpart): one GeoWrapper per process / GPU.
   // commUniqueId() on one rank, the 128 bytes handed to the others by the launcher, then commInit on every rank.
   //   tile_sharded = true : the result-identical mode — every rank is given every frame, compute() fuses the tiles this rank
@@ -125,6 +139,10 @@ private:
   bool sync_compute_ = false;      // MRH_SYNC_COMPUTE=1: compute() blocks and reports its own frame's flags (the reference's contract)
   uint32_t flags_announced_ = 0, last_compute_flags_ = 0;
   float max_depth_ = 0.f;
+  RaycastImages raycastPose(const std::array<float, 16>& pose);
+  bool has_camera_ = false;  // the camera of the last setCamera, for raycast()
+  int camera_model_ = MRH_CAMERA_PINHOLE, camera_rows_ = 0, camera_cols_ = 0;
+  float camera_fx_ = 0.f, camera_fy_ = 0.f, camera_cx_ = 0.f, camera_cy_ = 0.f, camera_min_depth_ = 0.f;
   float reach_ = 0.f;  // farthest distance from the camera centre at which a frame can touch a block (set by setCamera)
 
   int hash_num_buckets_ = 0, num_sdf_blocks_ = 0, hash_bucket_size_ = 10;

@@ -32,8 +32,10 @@
 
 #include "../../include/mrhash_hip.h"
 #include "../../include/mrhash_comm.h"
+#include "../../include/mrhash_raycast.h"
 #include "mrh_kernels.h"
 #include "mrh_mc.h"
+#include "mrh_raycast.h"
 #include "mrh_fast.h"
 #include "mrh_pipe.h"
 #include "mrh_fast2.h"
@@ -416,6 +418,10 @@ struct mrh_ctx {
   hipEvent_t comm_ev[5] = {};
   mrh_comm_phases comm_phases = {};
   std::vector<EvPair> comm_ev_pool, comm_ev_pending;
+  // raycasting (mrh_raycast.h): the images of mrh_raycast, grow-only — device [depth f32 | normals 3 x f32 | rgb 3 x u8] per
+  // pixel and the pinned host copy the caller reads
+  char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
+  char* h_ray = nullptr; size_t h_ray_cap = 0;
   std::string err;
 };
 
@@ -497,6 +503,8 @@ void free_all(mrh_ctx* c) {
   for (auto& e : c->comm_ev_pool) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
   for (auto& e : c->comm_ev_pending) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
   F(c->d_qt_sums); F(c->d_qt_flags); F(c->d_qt_unc); F(c->d_qt_marks); F(c->d_qt_pos); F(c->d_qt_parked); F(c->d_qt_leaves); F(c->d_qt_misc);
+  F(c->d_ray);
+  if (c->h_ray) (void) hipHostFree(c->h_ray);
   if (c->h_qt_seeds) (void) hipHostFree(c->h_qt_seeds);
   if (c->h_qt_out) (void) hipHostFree(c->h_qt_out);
   for (int i = 0; i < c->npend; i++) if (c->pendq[i].profile) c->ev_pool.push_back(c->pendq[i].ev);
@@ -4014,6 +4022,110 @@ int mrh_selftest_division(mrh_ctx* c, uint64_t samples, uint64_t seed, uint64_t*
   HIP_TRY(c, hipMemcpyAsync(&h, d, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *out_mismatches = h;
+  return MRH_OK;
+}
+
+}  // extern "C"
+
+// ---- raycasting (include/mrhash_raycast.h, mrh_raycast.h) ------------------------------------------------------------------
+extern "C++" {
+namespace {
+float ray_z_host(const float min_depth, const float step, const uint32_t k) { return min_depth + (float) k * step; }  // = ray_z
+
+// the arguments both entry points share, checked before the map is touched; fills the kernel's camera
+int raycast_args(mrh_ctx* c, const char* who, const mrh_raycast_params* p, const float* R, const float* t, RayCam* rc) {
+  if (!p || !R || !t) return fail(c, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (c->pending) return fail(c, MRH_ERR_STATE, "%s: an exchange is pending (call mrh_integrate_resume)", who);
+  if (c->map.shard_count > 1) return fail(c, MRH_ERR_UNSUPPORTED, "%s: sharded maps are not rendered (shard_count %d)", who, c->map.shard_count);
+  if (p->rows < 1 || p->rows > MRH_RAYCAST_MAX_SIDE || p->cols < 1 || p->cols > MRH_RAYCAST_MAX_SIDE)
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: image of %d x %d pixels (1 .. %d per side)", who, p->rows, p->cols, MRH_RAYCAST_MAX_SIDE);
+  if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || p->fx == 0.f || p->fy == 0.f || !std::isfinite(p->cx) || !std::isfinite(p->cy))
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: bad intrinsics", who);
+  if (!(p->min_depth > 0.f) || !(p->max_depth > p->min_depth) || !std::isfinite(p->max_depth))
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: need 0 < min_depth < max_depth (got %g, %g)", who, (double) p->min_depth, (double) p->max_depth);
+  if (p->outputs & ~(MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS)) return fail(c, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  const float step = p->step == 0.f ? 0.5f * c->p.sdf_truncation : p->step;
+  if (!(step > 0.f) || !std::isfinite(step)) return fail(c, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(R[i])) return fail(c, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t[i])) return fail(c, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  // samples z_k <= max_depth: z_k is monotone in k (two monotone roundings), so the count is found by bisection on k
+  if (ray_z_host(p->min_depth, step, MRH_RAYCAST_MAX_SAMPLES) <= p->max_depth)
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: more than 2^20 samples per ray (min_depth %g, max_depth %g, step %g)", who, (double) p->min_depth,
+                (double) p->max_depth, (double) step);
+  uint32_t lo = 0, hi = MRH_RAYCAST_MAX_SAMPLES;  // z(lo) <= max_depth < z(hi)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (ray_z_host(p->min_depth, step, mid) <= p->max_depth) lo = mid;
+    else hi = mid;
+  }
+  rc->ifx = 1.0f / p->fx;
+  rc->ify = 1.0f / p->fy;
+  rc->cx = p->cx; rc->cy = p->cy;
+  rc->rows = p->rows; rc->cols = p->cols;
+  rc->min_depth = p->min_depth; rc->max_depth = p->max_depth; rc->step = step;
+  rc->n_samples = hi;
+  for (int i = 0; i < 9; i++) rc->R[i] = R[i];
+  for (int i = 0; i < 3; i++) rc->t[i] = t[i];
+  return MRH_OK;
+}
+
+void launch_raycast(mrh_ctx* c, const RayCam& rc, float* depth, float* normals, uint8_t* rgb) {
+  const dim3 grid((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
+  k_raycast<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, depth, normals, rgb);
+}
+}  // namespace
+}  // extern "C++"
+
+extern "C" {
+
+int mrh_raycast(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], const float** out_depth,
+                const float** out_normals, const uint8_t** out_rgb) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  RayCam rc;
+  int rc_ = raycast_args(c, "mrh_raycast", p, R_row_major, t, &rc);
+  if (rc_) return rc_;
+  rc_ = ensure_ready(c, "mrh_raycast");
+  if (rc_) return rc_;
+  const size_t npix = (size_t) rc.rows * (size_t) rc.cols;
+  const size_t bytes = npix * (sizeof(float) * 4 + 3);
+  if (npix > c->ray_cap) {  // the previous raycast has finished (it blocked): nothing reads the old buffers
+    if (c->d_ray) { (void) hipFree(c->d_ray); c->d_ray = nullptr; c->ray_cap = 0; }
+    HIP_TRY(c, hipMalloc((void**) &c->d_ray, bytes));
+    c->ray_cap = npix;
+  }
+  if (npix > c->h_ray_cap) {
+    if (c->h_ray) { (void) hipHostFree(c->h_ray); c->h_ray = nullptr; c->h_ray_cap = 0; }
+    HIP_TRY(c, hipHostMalloc((void**) &c->h_ray, bytes, hipHostMallocDefault));
+    c->h_ray_cap = npix;
+  }
+  const bool want_n = out_normals && (p->outputs & MRH_RAYCAST_NORMALS), want_c = out_rgb && (p->outputs & MRH_RAYCAST_COLORS);
+  float* d_depth = (float*) c->d_ray;
+  float* d_normals = (float*) (c->d_ray + npix * sizeof(float));
+  uint8_t* d_rgb = (uint8_t*) (c->d_ray + npix * sizeof(float) * 4);
+  launch_raycast(c, rc, out_depth ? d_depth : nullptr, want_n ? d_normals : nullptr, want_c ? d_rgb : nullptr);
+  HIP_TRY(c, hipGetLastError());
+  if (out_depth) HIP_TRY(c, hipMemcpyAsync(c->h_ray, d_depth, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (want_n) HIP_TRY(c, hipMemcpyAsync(c->h_ray + npix * sizeof(float), d_normals, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (want_c) HIP_TRY(c, hipMemcpyAsync(c->h_ray + npix * sizeof(float) * 4, d_rgb, npix * 3, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (out_depth) *out_depth = (const float*) c->h_ray;
+  if (out_normals) *out_normals = want_n ? (const float*) (c->h_ray + npix * sizeof(float)) : nullptr;
+  if (out_rgb) *out_rgb = want_c ? (const uint8_t*) (c->h_ray + npix * sizeof(float) * 4) : nullptr;
+  return MRH_OK;
+}
+
+int mrh_raycast_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_depth, float* d_normals,
+                       uint8_t* d_rgb) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  RayCam rc;
+  int rc_ = raycast_args(c, "mrh_raycast_device", p, R_row_major, t, &rc);
+  if (rc_) return rc_;
+  rc_ = ensure_ready(c, "mrh_raycast_device");
+  if (rc_) return rc_;
+  launch_raycast(c, rc, d_depth, (p->outputs & MRH_RAYCAST_NORMALS) ? d_normals : nullptr, (p->outputs & MRH_RAYCAST_COLORS) ? d_rgb : nullptr);
+  HIP_TRY(c, hipGetLastError());
   return MRH_OK;
 }
 

@@ -4,6 +4,7 @@
 // this image; pybind11 returns numpy arrays where the reference returns Eigen matrices.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
+#include <optional>
 #include <vector>
 #include <pybind11/stl.h>
 
@@ -151,6 +152,27 @@ PYBIND11_MODULE(pygeowrapper, m) {
       }
       return py::make_tuple(to_array<float>(xyz, 3), to_array<float>(scale, 1), to_array<uint8_t>(rgb, 3));
     })
+    // not part of the reference binding: renders the map with the camera of the last setCamera from the current pose, or from
+    // (t, q) = (<tx,ty,tz>, <qx,qy,qz,qw>); returns (depth [H, W] f32, normals [H, W, 3] f32 world frame, colors [H, W, 3] u8)
+    .def("raycast", [](GeoWrapper& g, std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                       std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> q) {
+      if (t.has_value() != q.has_value()) throw std::runtime_error("GeoWrapper::raycast|give both t and q, or neither");
+      GeoWrapper::RaycastImages im;
+      if (t) {
+        if (t->size() != 3 || q->size() != 4) throw std::runtime_error("GeoWrapper::raycast|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+        im = g.raycast({t->data()[0], t->data()[1], t->data()[2]}, {q->data()[0], q->data()[1], q->data()[2], q->data()[3]});
+      } else {
+        im = g.raycast();
+      }
+      const size_t H = (size_t) im.rows, W = (size_t) im.cols;
+      py::array_t<float> depth({H, W});
+      py::array_t<float> normals({H, W, (size_t) 3});
+      py::array_t<uint8_t> colors({H, W, (size_t) 3});
+      std::memcpy(depth.mutable_data(), im.depth.data(), im.depth.size() * sizeof(float));
+      std::memcpy(normals.mutable_data(), im.normals.data(), im.normals.size() * sizeof(float));
+      std::memcpy(colors.mutable_data(), im.colors.data(), im.colors.size());
+      return py::make_tuple(depth, normals, colors);
+    }, py::arg("t") = py::none(), py::arg("q") = py::none())
     .def("clearBuffers", &GeoWrapper::clearBuffers)
     .def("serializeData", &GeoWrapper::serializeData, py::arg("filename_hash") = "./data/hash_points.ply",
          py::arg("filename_voxel") = "./data/voxel_points.ply")
