@@ -649,87 +649,29 @@ int ensure_ready(mrh_ctx* c, const char* who) {
   return strict_point(c);
 }
 
+// The scalars an extraction reads back land in one pinned block, h_mc (a copy into a stack variable is staged by the runtime):
+// k_mc_scan_total's {triangle total, corner-record demand | bit 63: a block found no room}, the post-process's {vertices, faces},
+// each copied as a pair, and compact_all's block count (an int).
+enum HMcSlot { HMC_TRIANGLES = 0, HMC_RECORDS = 1, HMC_VERTICES = 2, HMC_FACES = 3, HMC_COMPACT = 4, HMC_SLOTS = 8 };
+int ensure_h_mc(mrh_ctx* c) {
+  if (c->h_mc) return MRH_OK;
+  HIP_TRY(c, hipHostMalloc((void**) &c->h_mc, HMC_SLOTS * sizeof(u64), hipHostMallocDefault));
+  memset(c->h_mc, 0, HMC_SLOTS * sizeof(u64));
+  return MRH_OK;
+}
+
 // compacts every live block (no frustum filter) and returns the count; blocking
 int compact_all(mrh_ctx* c, int* out_n) {
   hipStream_t s = c->stream;
   HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_COMPACT], 0, sizeof(int), s));
   k_compact<<<512, 256, 0, s>>>(c->cam, c->map, c->tab, 0);
-  if (!c->h_mc) {  // pinned: a copy into a stack variable is staged by the runtime
-    HIP_TRY(c, hipHostMalloc((void**) &c->h_mc, 8 * sizeof(u64), hipHostMallocDefault));
-    memset(c->h_mc, 0, 8 * sizeof(u64));
-  }
-  HIP_TRY(c, hipMemcpyAsync(c->h_mc + 4, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToHost, s));
+  const int rc = ensure_h_mc(c);
+  if (rc) return rc;
+  HIP_TRY(c, hipMemcpyAsync(c->h_mc + HMC_COMPACT, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
   HIP_TRY(c, hipGetLastError());
-  *out_n = *(const int*) (c->h_mc + 4);
+  *out_n = *(const int*) (c->h_mc + HMC_COMPACT);
   return MRH_OK;
-}
-
-struct KeyHash3 {
-  size_t operator()(const std::array<uint64_t, 3>& k) const {
-    uint64_t h = k[0] * 0x9E3779B97F4A7C15ull;
-    h ^= (k[1] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2));
-    h ^= (k[2] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2));
-    return (size_t) h;
-  }
-};
-struct FaceHash {
-  size_t operator()(const std::array<int32_t, 3>& f) const {
-    uint64_t h = (uint64_t) (uint32_t) f[0] * 0x9E3779B97F4A7C15ull;
-    h ^= ((uint64_t) (uint32_t) f[1] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2));
-    h ^= ((uint64_t) (uint32_t) f[2] + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2));
-    return (size_t) h;
-  }
-};
-
-// MeshExtractor::processTriangles for a single extraction (mesh_extractor.cpp:9-76):
-// soup -> vertex merge (exact bit pattern, or floor(v/eps) cells; first occurrence keeps index and colour)
-// -> drop degenerate faces -> drop repeated faces keeping the first.
-void widen_quiesce();
-void process_triangles(mrh_ctx* c) {
-  const size_t nt = c->tris.size();
-  widen_quiesce();  // a helper of the last extraction's widening may still be writing the arrays that are about to be replaced
-  c->V.clear(); c->C.clear(); c->F.clear();
-  if (nt == 0) return;
-  std::vector<double> V, C;
-  std::vector<int32_t> F;
-  const double eps = (double) c->p.vertices_merging_threshold;
-  const double inv_eps = eps != 0.0 ? 1.0 / eps : 0.0;
-  std::unordered_map<std::array<uint64_t, 3>, int32_t, KeyHash3> vmap;
-  vmap.reserve(nt * 3);
-  std::vector<int32_t> faces(nt * 3);
-  for (size_t i = 0; i < nt; i++)
-    for (int k = 0; k < 3; k++) {
-      const mrh_vertex& v = c->tris[i].v[k];
-      const double p[3] = {(double) v.p[0], (double) v.p[1], (double) v.p[2]};
-      std::array<uint64_t, 3> key;
-      for (int a = 0; a < 3; a++) {
-        if (eps == 0.0) memcpy(&key[a], &p[a], 8);
-        else key[a] = (uint64_t) (uint32_t) (int32_t) std::floor(p[a] * inv_eps);
-      }
-      const bool has_nan = p[0] != p[0] || p[1] != p[1] || p[2] != p[2];  // never equal to anything (Vector3dEqual)
-      auto it = has_nan ? vmap.end() : vmap.find(key);
-      int32_t idx;
-      if (it != vmap.end()) idx = it->second;
-      else {
-        idx = (int32_t) (V.size() / 3);
-        if (!has_nan) vmap.emplace(key, idx);
-        V.insert(V.end(), {p[0], p[1], p[2]});
-        C.insert(C.end(), {(double) v.c[0], (double) v.c[1], (double) v.c[2]});
-      }
-      faces[i * 3 + k] = idx;
-    }
-  std::unordered_map<std::array<int32_t, 3>, char, FaceHash> seen;
-  seen.reserve(nt);
-  for (size_t i = 0; i < nt; i++) {
-    const std::array<int32_t, 3> f = {faces[i * 3], faces[i * 3 + 1], faces[i * 3 + 2]};
-    if (f[0] == f[1] || f[0] == f[2] || f[1] == f[2]) continue;
-    if (!seen.emplace(f, 1).second) continue;
-    F.insert(F.end(), {f[0], f[1], f[2]});
-  }
-  c->V.assign(V.data(), V.data() + V.size());
-  c->C.assign(C.data(), C.data() + C.size());
-  c->F.assign(F.data(), F.data() + F.size());
 }
 
 // grow-only scratch `slot` of at least `bytes` (contents undefined); the previous buffer is released only after the stream drained
@@ -747,353 +689,18 @@ int arena_get(mrh_ctx* c, const int slot, const size_t bytes, void** out) {
   return MRH_OK;
 }
 
-// Results leave the device through a copy KERNEL writing pinned host memory, not through hipMemcpyAsync: the runtime's choice
-// of SDMA engine for a stream is not stable within a process — the second context of a process (and every later one) moved its
-// V / C / F at 22 GB/s instead of 54 (tools/dbg_extract2.py: 30 MB in 1.24 vs 0.56 ms; tools/micro/d2h_streams.hip and
-// d2h_second_alloc.hip rule out the host buffer and the stream order in isolation) while 16-byte stores of a kernel reach 53-54 GB/s
-// every time.  It also lets the copy read its sizes on the device: no host round trip between the post-process and the copy.
-//   part p copies ceil(min(count[p], cap[p]) * unit[p] / 16) 16-byte words (both sides are padded to a multiple of 16 bytes)
-struct CopyOut {
-  const uint4* src[3];
-  uint4* dst[3];
-  const u64* count[3];  // device: elements of part p (nullptr: use fixed[p])
-  u64 fixed[3], cap[3];
-  u32 unit[3];          // bytes per element
-};
-__global__ __launch_bounds__(256) void k_copy_out(const CopyOut a) {
-#pragma unroll 1
-  for (int p = 0; p < 3; p++) {
-    if (!a.dst[p]) continue;
-    u64 n = a.count[p] ? *a.count[p] : a.fixed[p];
-    if (n > a.cap[p]) n = a.cap[p];
-    const size_t n16 = (size_t) ((n * a.unit[p] + 15) / 16);
-    for (size_t i = (size_t) blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t) gridDim.x * 256) a.dst[p][i] = a.src[p][i];
-  }
-}
-// V / C / F of an extraction are 48 B per vertex + 12 B per face as the reference hands them out (Eigen::MatrixXd / MatrixXi,
-// geowrapper.h:91-93) — 30 MB at the driver's workload, 0.56 ms of a 1.3 ms extraction at the link's 54 GB/s.  The vertex
-// arithmetic is fp32 (mesh_extractor.cu:6-36), so the doubles carry no more than the floats they are widened from: V and C cross the
-// link as fp32 (24 B per vertex) into pinned staging, in 64 KiB chunks that each raise a flag word when they have landed, and
-// host threads widen chunk after chunk into the caller-visible double arrays while the following chunks and the faces are still
-// on the link (widen_from_staging below; (double) (float) is exact, the arrays are the same bytes as before).  F goes straight
-// to its final buffer.  Few workgroups, each walking its chunks in order: the link is the bottleneck, and chunks must COMPLETE in
-// order for the host to overlap, not all at the end.
-constexpr u32 kStageChunk = 64u << 10;            // bytes
-constexpr u32 kStageWords = kStageChunk / 16;     // uint4 per chunk
-constexpr u32 kStageHdrWords = 16;                // u32 words of stage_ctl before the first flag
-struct StageOut {
-  const uint4* src[3];   // device: V32, C32, F
-  uint4* dst[3];         // pinned: V32 staging, C32 staging, F
-  const u64* totals;     // device: [0] vertices, [1] faces
-  u64 cap_v, cap_f;      // elements the destinations hold
-  u64* hdr;              // pinned: [0] vertices, [1] faces, [2] epoch (written last)
-  u32* flags;            // pinned: chunk c of V32 -> flags[c], of C32 -> flags[flag_stride + c]
-  u32 flag_stride;
-  u32 epoch;
-  // workgroups copy_wgs .. gridDim.x - 1 do not copy: they refill the post-process's index tables with "empty" for the next
-  // extraction (the link keeps the copying workgroups busy for 0.35 ms; the fills used to cost 2 x 9 us up front)
-  u32 copy_wgs;
-  u32* clear;
-  size_t clear_words;
-};
-__global__ __launch_bounds__(256) void k_stage_out(const StageOut a) {
-  if (blockIdx.x >= a.copy_wgs) {
-    const size_t n4 = a.clear_words / 4, stride = (size_t) (gridDim.x - a.copy_wgs) * 256;
-    uint4* c4 = (uint4*) a.clear;
-    const uint4 ff = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    for (size_t i = (size_t) (blockIdx.x - a.copy_wgs) * 256 + threadIdx.x; i < n4; i += stride) c4[i] = ff;
-    if (blockIdx.x == a.copy_wgs && threadIdx.x < (a.clear_words & 3)) a.clear[n4 * 4 + threadIdx.x] = 0xFFFFFFFFu;
-    return;
-  }
-  const u64 nv = a.totals[0], nf = a.totals[1];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    a.hdr[0] = nv; a.hdr[1] = nf;
-    __hip_atomic_store(&a.hdr[2], (u64) a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  if (nv > a.cap_v || nf > a.cap_f) return;  // uniform: the host grows the buffers and launches again
-  const size_t w16[3] = {(size_t) ((nv * 12 + 15) / 16), (size_t) ((nv * 12 + 15) / 16), (size_t) ((nf * 12 + 15) / 16)};
-  const u32 nch[3] = {(u32) ((w16[0] + kStageWords - 1) / kStageWords), (u32) ((w16[1] + kStageWords - 1) / kStageWords),
-                      (u32) ((w16[2] + kStageWords - 1) / kStageWords)};
-  const u32 total = nch[0] + nch[1] + nch[2];
-  for (u32 ch = blockIdx.x; ch < total; ch += a.copy_wgs) {  // uniform per workgroup
-    const int p = ch < nch[0] ? 0 : (ch < nch[0] + nch[1] ? 1 : 2);
-    const u32 lc = ch - (p > 0 ? nch[0] : 0u) - (p > 1 ? nch[1] : 0u);
-    const size_t lo = (size_t) lc * kStageWords, hi = lo + kStageWords < w16[p] ? lo + kStageWords : w16[p];
-    const uint4* __restrict__ src = a.src[p];
-    uint4* __restrict__ dst = a.dst[p];
-    uint4 r[kStageWords / 256];
-#pragma unroll
-    for (u32 k = 0; k < kStageWords / 256; k++) {
-      const size_t i = lo + k * 256 + threadIdx.x;
-      if (i < hi) r[k] = src[i];
-    }
-#pragma unroll
-    for (u32 k = 0; k < kStageWords / 256; k++) {
-      const size_t i = lo + k * 256 + threadIdx.x;
-      if (i < hi) dst[i] = r[k];
-    }
-    if (p < 2) {
-      // (the fence is needed — plain stores to the pinned buffer sit in the XCD's L2: with "stores acknowledged, then the flag" alone
-      // tools/stress_extract.py read a torn mesh within 50 extractions — and it is not what the kernel waits for: write-through stores
-      // (sc0 sc1) + acknowledgement + flag, no fence, gave the same 0.83-0.87 ms per extraction; profiles/r06/ab_stage_out_fences.txt)
-      __threadfence_system();
-      __syncthreads();
-      if (threadIdx.x == 0) __hip_atomic_store(&a.flags[(p ? a.flag_stride : 0u) + lc], a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
-}
-// host side of the above (defined with the copy pool further down): widens nfloat floats of each of the two staging parts into
-// dst[0] / dst[1], chunk by chunk as flags[part][chunk] reaches `epoch` (flags == nullptr: everything has landed already).
-// `drained(arg)` tells whether the stream has run dry (then a missing flag means a failed launch).  Returns false if it gave up.
-bool widen_from_staging(double* const dst[2], const float* const src[2], const volatile u32* const flags[2], u32 epoch, size_t nfloat,
-                        bool (*drained)(void*), void* arg);
-void widen_prewake();
-void widen_quiesce();
-uint64_t widen_redone();
-
-// MeshExtractor::processTriangles on the device (mrh_mesh.h): fills V / C / F from a triangle soup in device memory.
-// MRH_MESH_HOST=1 keeps the host restatement above (same arrays; tests compare the two).
-int process_triangles_device(mrh_ctx* c, const mrh_triangle* d_tris, const size_t nt) {
-  // a helper that lost its core during the last extraction's widening may still be reading the staging this one is about to
-  // rewrite, or writing the arrays it may regrow (CopyPool: the call no longer waits for its helpers)
-  widen_quiesce();
-  c->V.clear(); c->C.clear(); c->F.clear();
-  if (nt == 0) return MRH_OK;
-  if (nt * 3 >= (1ull << 30)) return fail(c, MRH_ERR_CAPACITY, "mesh post-process: %zu triangles exceed the 2^30 soup vertices one index table holds", nt);
-  hipStream_t s = c->stream;
-  const u32 n = (u32) (nt * 3), ntr = (u32) nt;
-  const double eps = (double) c->p.vertices_merging_threshold;
-  const double inv_eps = eps != 0.0 ? 1.0 / eps : 0.0;
-  const u32 cap = (u32) next_pow2((uint64_t) n * 2);  // load factor <= 1/2
-  const u32 fcap = (u32) next_pow2((uint64_t) ntr * 2);
-  MeshScratch m;
-  m.bytes = (size_t) n * 4 * 5 + ((size_t) cap + fcap) * 4 + 32 * 256;
-  {
-    const int arc = arena_get(c, 1, m.bytes, &m.base);
-    if (arc) return arc;
-  }
-  // The two index tables come first, so that they lie where the last extraction's lay: that extraction's read-back kernel left
-  // them empty again (k_stage_out's extra workgroups clear them while the link is busy), and the two fills — 24 MB at the
-  // driver's workload, ahead of the vertex and of the face kernels — are only needed when the scratch moved or grew.
-  u32* table = m.take<u32>(cap);
-  u32* ftable = m.take<u32>(fcap);
-  const size_t clear_words = (size_t) ((ftable + fcap) - (u32*) m.base);
-  const bool tables_clean = !c->f64_link && c->mesh_clean_base == m.base && c->mesh_clean_words >= clear_words && !getenv("MRH_MESH_FILL");
-  c->mesh_clean_words = 0;  // dirty from here on, until a clear is enqueued
-  const u32 vtiles = (n + kMeshTile - 1) / kMeshTile, ftiles = (ntr + 255) / 256;
-  u32* rep = m.take<u32>(n);   u32* vloc = m.take<u32>(n);   u32* corner = m.take<u32>(n);
-  u32* floc = m.take<u32>(n);  // faces (nt <= n)
-  u32* tcount = m.take<u32>(vtiles);  u32* toff = m.take<u32>(vtiles);  // first occurrences per vertex tile, and their scan
-  u32* fcount = m.take<u32>(ftiles);  u32* foff = m.take<u32>(ftiles);  // kept faces per face tile
-  u64* d_totals = m.take<u64>(2);
-  const u32 gv = (n + 255) / 256, gf = (ntr + 255) / 256;
-  const float* soup = (const float*) d_tris;
-  int rc = MRH_OK;
-  void *dV = nullptr, *dC = nullptr;  // doubles with f64_link, floats otherwise
-  int* dF = nullptr;
-  if (!c->h_mc) {
-    HIP_TRY(c, hipHostMalloc((void**) &c->h_mc, 8 * sizeof(u64), hipHostMallocDefault));
-    memset(c->h_mc, 0, 8 * sizeof(u64));
-  }
-  const bool f64 = c->f64_link;
-  if (!f64) widen_prewake();  // the helper threads are awake and spinning by the time the first chunk lands
-#define MESH_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { rc = fail(c, MRH_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); goto done; } } while (0)
-  {
-    // V, C (at most n vertices each) and the faces (at most nt) share slot 2, sized by those bounds: nothing of the
-    // post-process waits for a count from the device
-    {
-      void* vcf = nullptr;
-      const size_t vbytes = ((size_t) n * 3 * (f64 ? sizeof(double) : sizeof(float)) + 16 + 255) & ~(size_t) 255;  // + 16: the copy kernels read whole 16-byte words
-      rc = arena_get(c, 2, 2 * vbytes + (size_t) ntr * 3 * sizeof(int) + 16, &vcf);
-      if (rc) goto done;
-      dV = vcf;
-      dC = (char*) vcf + vbytes;
-      dF = (int*) ((char*) vcf + 2 * vbytes);
-    }
-    // ---- vertices
-    if (!tables_clean) MESH_TRY(hipMemsetAsync(m.base, 0xFF, clear_words * 4, s));
-    k_mesh_vertex_insert<<<(n + kMeshTile - 1) / kMeshTile, kMeshTile, 0, s>>>(soup, n, eps, inv_eps, table, cap - 1, rep);
-    k_mesh_vertex_rep<<<vtiles, kMeshTile, 0, s>>>(soup, n, eps, inv_eps, table, cap - 1, rep, vloc, tcount);
-    k_tile_scan<<<1, 1024, 0, s>>>(tcount, vtiles, toff, d_totals);
-    if (f64) k_mesh_emit_vertices<double><<<gv, 256, 0, s>>>(soup, rep, vloc, toff, n, (double*) dV, (double*) dC, corner);
-    else k_mesh_emit_vertices<float><<<gv, 256, 0, s>>>(soup, rep, vloc, toff, n, (float*) dV, (float*) dC, corner);
-    // ---- faces
-    k_mesh_face_insert<<<gf, 256, 0, s>>>(corner, ntr, ftable, fcap - 1);
-    k_mesh_face_keep<<<gf, 256, 0, s>>>(corner, ntr, ftable, fcap - 1, floc, fcount);
-    k_tile_scan<<<1, 1024, 0, s>>>(fcount, ftiles, foff, d_totals + 1);
-    k_mesh_emit_faces<<<gf, 256, 0, s>>>(corner, floc, foff, ntr, dF);
-    const bool dbg = getenv("MRH_DEBUG") != nullptr;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = now();
-    // (Tried in round 4: V and C on a second stream as soon as the vertices are final, next to the face kernels.  The copy kernel and
-    // k_mesh_face_insert do not share the memory system gracefully — the insert's atomics ran 37 -> 240-450 us whether the copy had
-    // 1 024 or 128 workgroups — and the extraction took as long as before.)
-    if (f64) {
-      // ---- the round-3 way out: doubles over the link.  V, C, F go out behind the post-process without the host in between
-      // (k_copy_out reads the two totals on the device), into the buffers of the previous extraction; if they turn out too small
-      // (or not pinned) they grow and the copy runs again.
-      const bool pinned = c->V.dev && c->C.dev && c->F.dev && !getenv("MRH_D2H_MEMCPY");  // MRH_D2H_MEMCPY=1: hipMemcpyAsync instead (A/B)
-      auto copy_out = [&](const bool by_kernel, const size_t nv_known, const size_t nf_known) {
-        if (by_kernel) {
-          CopyOut a;
-          a.src[0] = (const uint4*) dV; a.dst[0] = (uint4*) c->V.dev; a.count[0] = d_totals; a.cap[0] = c->V.cap / 3; a.unit[0] = 24;
-          a.src[1] = (const uint4*) dC; a.dst[1] = (uint4*) c->C.dev; a.count[1] = d_totals; a.cap[1] = c->C.cap / 3; a.unit[1] = 24;
-          a.src[2] = (const uint4*) dF; a.dst[2] = (uint4*) c->F.dev; a.count[2] = d_totals + 1; a.cap[2] = c->F.cap / 3; a.unit[2] = 12;
-          a.fixed[0] = a.fixed[1] = a.fixed[2] = 0;
-          k_copy_out<<<1024, 256, 0, s>>>(a);
-          return hipGetLastError();
-        }
-        hipError_t e = hipMemcpyAsync(c->V.data(), dV, nv_known * 3 * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->C.data(), dC, nv_known * 3 * sizeof(double), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && nf_known) e = hipMemcpyAsync(c->F.data(), dF, nf_known * 3 * sizeof(int), hipMemcpyDeviceToHost, s);
-        return e;
-      };
-      const size_t cap_v = std::min(c->V.cap, c->C.cap) / 3, cap_f = c->F.cap / 3;
-      const bool speculative = pinned && cap_v > 0 && c->V.data() && c->C.data() && c->F.data();
-      if (speculative) MESH_TRY(copy_out(true, 0, 0));
-      MESH_TRY(hipMemcpyAsync(c->h_mc + 2, d_totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, s));
-      MESH_TRY(hipStreamSynchronize(s));
-      const double t1 = now();
-      const size_t nv = (size_t) c->h_mc[2], nf = (size_t) c->h_mc[3];
-      const bool fits = speculative && nv <= cap_v && nf <= cap_f;
-      c->V.resize_discard(nv * 3); c->C.resize_discard(nv * 3); c->F.resize_discard(std::max<size_t>(nf, 1) * 3);
-      c->F.n = nf * 3;
-      if (!fits) {
-        MESH_TRY(copy_out(c->V.dev && c->C.dev && c->F.dev && !getenv("MRH_D2H_MEMCPY"), nv, nf));
-        MESH_TRY(hipStreamSynchronize(s));
-      }
-      MESH_TRY(hipGetLastError());
-      if (dbg) fprintf(stderr, "[mrhash_hip] mesh post-process: %u soup vertices -> %zu vertices, %zu faces | kernels%s %.2f ms, second copy (buffers grown) %.2f (%.1f MB)\n",
-                       n, nv, nf, speculative ? " + copy to the host" : "", t1 - t0, now() - t1, (nv * 48 + nf * 12) / 1e6);
-    } else {
-      // ---- fp32 over the link, widened by the host as the chunks land (k_stage_out).  Speculative like the above: into the
-      // staging of the previous extraction, and again if that turns out too small.
-      struct Drain { hipStream_t s; };
-      Drain drain{s};
-      auto drained = [](void* a) { return hipStreamQuery(((Drain*) a)->s) != hipErrorNotReady; };
-      auto stage_ready = [&] { return c->V32.dev && c->C32.dev && c->F.dev && c->stage_ctl.dev; };
-      bool clear_pending = true;  // the first launch of this extraction also clears the index tables
-      auto launch = [&](u32& epoch_out) {
-        StageOut a;
-        a.src[0] = (const uint4*) dV; a.src[1] = (const uint4*) dC; a.src[2] = (const uint4*) dF;
-        a.dst[0] = (uint4*) c->V32.dev; a.dst[1] = (uint4*) c->C32.dev; a.dst[2] = (uint4*) c->F.dev;
-        a.totals = d_totals;
-        a.cap_v = std::min(c->V32.cap, c->C32.cap) / 3; a.cap_f = c->F.cap / 3;
-        // one flag per chunk the staging can hold
-        const u32 max_chunks = (u32) ((a.cap_v * 12 + 15) / 16 / kStageWords + 1);
-        const size_t room = (c->stage_ctl.cap - kStageHdrWords) / 2;
-        if (max_chunks > room) a.cap_v = (u64) (room > 1 ? (room - 1) : 0) * kStageChunk / 12;
-        a.hdr = (u64*) c->stage_ctl.dev;
-        a.flags = c->stage_ctl.dev + kStageHdrWords;
-        a.flag_stride = (u32) room;
-        if (++c->stage_epoch == 0) c->stage_epoch = 1;
-        a.epoch = epoch_out = c->stage_epoch;
-        static const int grid = getenv("MRH_STAGE_WGS") ? std::max(1, atoi(getenv("MRH_STAGE_WGS"))) : 64;
-        a.copy_wgs = (u32) grid;
-        a.clear = (u32*) m.base;
-        a.clear_words = clear_pending ? clear_words : 0;
-        k_stage_out<<<grid + (clear_pending ? 256 : 0), 256, 0, s>>>(a);
-        if (clear_pending) { c->mesh_clean_base = m.base; c->mesh_clean_words = clear_words; }
-        clear_pending = false;
-        return a;
-      };
-      // waits for the header of launch `epoch`; false: the stream ran dry without it (a failed launch)
-      auto wait_hdr = [&](const u32 epoch) {
-        const volatile u64* hdr = (const volatile u64*) c->stage_ctl.data();
-        for (u32 spins = 1;; spins++) {
-          if (hdr[2] == (u64) epoch) break;
-          MRH_CPU_RELAX();
-          if ((spins & 1023u) == 0 && drained(&drain)) {  // dry: the header is there, or about to be — or the launch failed
-            const auto t = std::chrono::steady_clock::now();
-            while (hdr[2] != (u64) epoch && std::chrono::steady_clock::now() - t < std::chrono::milliseconds(200)) MRH_CPU_RELAX();
-            if (hdr[2] == (u64) epoch) break;
-            return false;
-          }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return true;
-      };
-      auto widen = [&](const u32 epoch, const size_t nv, const bool flagged) {
-        double* const dst[2] = {c->V.data(), c->C.data()};
-        const float* const src[2] = {c->V32.data(), c->C32.data()};
-        const volatile u32* f0 = (const volatile u32*) c->stage_ctl.data() + kStageHdrWords;
-        const volatile u32* const flags[2] = {flagged ? f0 : nullptr, flagged ? f0 + (c->stage_ctl.cap - kStageHdrWords) / 2 : nullptr};
-        return widen_from_staging(dst, src, flags, epoch, nv * 3, drained, &drain);
-      };
-      bool done_ok = false;
-      size_t nv = 0, nf = 0;
-      double t1 = t0;
-      if (stage_ready() && std::min(c->V32.cap, c->C32.cap) >= 3 && c->F.cap >= 3) {
-        u32 epoch = 0;
-        const StageOut a = launch(epoch);
-        MESH_TRY(hipGetLastError());
-        MESH_TRY(hipMemcpyAsync(c->h_mc + 2, d_totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, s));
-        if (!wait_hdr(epoch)) { MESH_TRY(hipStreamSynchronize(s)); MESH_TRY(hipGetLastError()); rc = fail(c, MRH_ERR_DEVICE, "mesh read-back: the staging kernel did not report"); goto done; }
-        const volatile u64* hdr = (const volatile u64*) c->stage_ctl.data();
-        nv = (size_t) hdr[0]; nf = (size_t) hdr[1];
-        if (nv <= a.cap_v && nf <= a.cap_f) {
-          c->V.resize_discard(nv * 3); c->C.resize_discard(nv * 3);
-          c->F.n = nf * 3;
-          const bool ok = widen(epoch, nv, true);
-          MESH_TRY(hipStreamSynchronize(s));  // the faces, and the end of the launch
-          MESH_TRY(hipGetLastError());
-          if (!ok) { rc = fail(c, MRH_ERR_DEVICE, "mesh read-back: a staged chunk never arrived"); goto done; }
-          done_ok = true;
-        } else {
-          MESH_TRY(hipStreamSynchronize(s));
-        }
-        t1 = now();
-      } else {
-        MESH_TRY(hipMemcpyAsync(c->h_mc + 2, d_totals, 2 * sizeof(u64), hipMemcpyDeviceToHost, s));
-        MESH_TRY(hipStreamSynchronize(s));
-        nv = (size_t) c->h_mc[2]; nf = (size_t) c->h_mc[3];
-        t1 = now();
-      }
-      if (!done_ok) {  // first extraction, or the mesh outgrew the buffers: size them and go again
-        c->V32.resize_discard(nv * 3 + 4); c->C32.resize_discard(nv * 3 + 4);
-        c->F.resize_discard(std::max<size_t>(nf, 1) * 3 + 4);
-        c->F.n = nf * 3;
-        c->stage_ctl.resize_discard(kStageHdrWords + 2 * ((std::min(c->V32.cap, c->C32.cap) * 4 + kStageChunk - 1) / kStageChunk + 2));
-        c->V.resize_discard(nv * 3); c->C.resize_discard(nv * 3);
-        if (stage_ready()) {
-          u32 epoch = 0;
-          const StageOut a = launch(epoch);
-          MESH_TRY(hipGetLastError());
-          bool ok = wait_hdr(epoch) && nv <= a.cap_v && nf <= a.cap_f;
-          if (ok) ok = widen(epoch, nv, true);
-          MESH_TRY(hipStreamSynchronize(s));
-          MESH_TRY(hipGetLastError());
-          if (!ok) { rc = fail(c, MRH_ERR_DEVICE, "mesh read-back: the staged copy did not complete"); goto done; }
-        } else {  // registration refused: plain copies, then the widening
-          MESH_TRY(hipMemcpyAsync(c->V32.data(), dV, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-          MESH_TRY(hipMemcpyAsync(c->C32.data(), dC, nv * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-          if (nf) MESH_TRY(hipMemcpyAsync(c->F.data(), dF, nf * 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-          MESH_TRY(hipStreamSynchronize(s));
-          (void) widen(0, nv, false);
-        }
-      }
-      MESH_TRY(hipGetLastError());
-      if (dbg) fprintf(stderr, "[mrhash_hip] mesh post-process: %u soup vertices -> %zu vertices, %zu faces | kernels + fp32 staging + widening %.2f ms, second pass (buffers grown) %.2f (%.1f MB over the link)\n",
-                       n, nv, nf, t1 - t0, now() - t1, (nv * 24 + nf * 12) / 1e6);
-    }
-  }
-done:
-#undef MESH_TRY
-  return rc;
-}
-
-
-
-// the soup buffer: grow-only, owned by the context, valid until the next extraction
-int ensure_soup(mrh_ctx* c, size_t n) {
-  if (n > c->soup_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_soup) HIP_TRY(c, hipFree(c->d_soup));
-    c->d_soup = nullptr; c->soup_cap = 0;
-    const size_t cap = n + n / 8;
-    HIP_TRY(c, hipMalloc((void**) &c->d_soup, cap * sizeof(mrh_triangle) + 16));  // + 16: k_copy_out reads whole 16-byte words
-    c->soup_cap = cap;
-  }
+// Arena `slot` handed out by `lay(MeshScratch&)`, the one list of the buffers that live in it: `lay` runs once on no memory to
+// learn the size the arena needs and again on the real base, so the size asked for and the pointers handed out cannot disagree.
+template <typename Layout>
+int arena_layout(mrh_ctx* c, const int slot, MeshScratch* m, Layout&& lay) {
+  MeshScratch dry;
+  lay(dry);
+  m->bytes = dry.used;
+  const int rc = arena_get(c, slot, m->bytes, &m->base);
+  if (rc) return rc;
+  m->used = 0;
+  lay(*m);
+  if (m->used > m->bytes) return fail(c, MRH_ERR_STATE, "scratch arena %d: the layout took %zu of %zu bytes", slot, m->used, m->bytes);
   return MRH_OK;
 }
 
@@ -1230,6 +837,8 @@ int starve_and_tail(mrh_ctx* c, int max_num_frames) {
 }
 
 }  // namespace
+
+#include "mrh_extract.h"
 
 extern "C" {
 
@@ -2538,9 +2147,7 @@ static void prewarm_maybe(mrh_ctx* c) {
   if (nv < 65536) return;  // a mesh this small costs its first extraction next to nothing
   try {
     const size_t nf = (size_t) (nv + nv / 4);  // faces: a little above the vertices (closed surfaces: twice; what is seen of a room: ~1.1 x)
-    c->V32.resize_discard((size_t) nv * 3 + 4); c->C32.resize_discard((size_t) nv * 3 + 4);
-    c->F.resize_discard(nf * 3 + 4);
-    c->stage_ctl.resize_discard(kStageHdrWords + 2 * ((std::min(c->V32.cap, c->C32.cap) * 4 + kStageChunk - 1) / kStageChunk + 2));
+    size_mesh_staging(c, (size_t) nv, nf);
     if (c->stage_ctl.data()) memset(c->stage_ctl.data(), 0, c->stage_ctl.cap * sizeof(u32));  // no epoch, no flag of an earlier life
     c->V.reserve_unpinned((size_t) nv * 3); c->C.reserve_unpinned((size_t) nv * 3);  // never pinned: mapped and faulted in
     c->V32.clear(); c->C32.clear(); c->F.clear(); c->V.clear(); c->C.clear();  // capacity, not content: the getters still answer "no mesh"
@@ -2722,18 +2329,10 @@ int lidar_sort(mrh_ctx* c, K* k0, K* k1, float* v0, float* v1, const size_t n, c
     HIP_TRY(c, hipMalloc(&c->d_sort_tmp, (size_t) total * sizeof(u32) * 2 + 1024));
     c->sort_tmp_bytes = (size_t) total * sizeof(u32) * 2 + 1024;
   }
-  u32* hist = (u32*) c->d_sort_tmp + 256;  // [0, 256): the digit totals
-  K* ks[2] = {k0, k1};
-  float* vs[2] = {v0, v1};
-  int src = 0;
-  for (int shift = 0; shift < end_bit; shift += 8) {
-    k_sort_hist<K><<<ntiles, kSortThreads, 0, s>>>(ks[src], (u32) n, shift, hist, ntiles);
-    k_sort_scan<<<256, 256, 0, s>>>(hist, ntiles, (u32*) c->d_sort_tmp);
-    k_sort_scatter<K><<<ntiles, kSortThreads, 0, s>>>(ks[src], vs[src], ks[src ^ 1], vs[src ^ 1], (u32) n, shift, hist, ntiles, (const u32*) c->d_sort_tmp);
-    src ^= 1;
-  }
+  K* const ks[2] = {k0, k1};
+  float* const vs[2] = {v0, v1};
+  *out_buf = radix_sort_pairs<K, float>(s, ks, vs, nullptr, n, end_bit, (u32*) c->d_sort_tmp, (u32*) c->d_sort_tmp + 256);  // [0, 256): the digit totals
   HIP_TRY(c, hipGetLastError());
-  *out_buf = src;
   return MRH_OK;
 }
 }  // namespace
@@ -3262,284 +2861,6 @@ int mrh_get_stats(mrh_ctx* c, mrh_stats* out) {
   return MRH_OK;
 }
 
-int mrh_extract_triangles(mrh_ctx* c, const mrh_triangle** out_tris, uint64_t* out_n) {
-  int rc = ensure_ready(c, "mrh_extract_triangles");
-  if (rc) return rc;
-  if (!out_n) return MRH_ERR_INVALID_ARG;
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_extract_triangles: an exchange is pending (call mrh_integrate_resume)");
-  // out_tris == NULL: the caller only wants the mesh (mrh_extract_mesh) — the soup stays on the device.  The host
-  // restatement of the post-process (MRH_MESH_HOST=1) reads the host copy, so it keeps it.
-  const bool want_soup = out_tris != nullptr || c->mesh_on_host;
-  uint64_t n_tris = 0;
-  hipStream_t s = c->stream;
-  const bool dbg = getenv("MRH_DEBUG") != nullptr;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t0 = now(), t1 = t0, t2 = t0, t3 = t0, t4 = t0, t5 = t0;
-  int n = 0;
-  rc = compact_all(c, &n);  // the one scalar the host needs up front: it sizes the sort and the launches
-  if (rc) return rc;
-  c->n_extractions++;  // from here on the caller may hold pointers into the result buffers: the prewarm leaves them alone
-  c->tris.clear();
-  c->tri_blocks.clear();
-  c->tri_counts.clear();
-  c->tri_dev_n = 0;
-  c->last_triangles = 0;
-  c->soup_n = 0;
-  bool processed = false;
-  if (n > 0) {
-    // Everything between the block count and the triangle total stays on the device: canonical order by a radix sort of the
-    // packed keys (key order == (x, y, z) order), the 27-block neighbourhoods resolved by one thread per (block, neighbour),
-    // per-block triangle counts -> exclusive scan (k_mc_scan_total) -> exact offsets, the emit pass launched right behind it.  The
-    // sorted list and the counts are read back only if somebody asks (mrh_get_triangle_blocks).
-    u64 *k_in, *k_out, *d_offsets, *d_total;
-    int4* sorted;
-    u32 *d_counts, *d_nb, *d_rec_base, *d_rec_n, *d_rec_ctr, *d_partial;
-    uint8_t* d_per_voxel;  // triangles per voxel from the count pass: k_mc<emit> (the fallback of the record pass) skips the empty ones
-    void* tmp;
-    int4* sorted2 = nullptr;
-    const bool no_rank_sort = getenv("MRH_MC_RADIX_SORT") != nullptr;  // MRH_MC_RADIX_SORT=1: the radix sort of mrh_sort.h for every list (A/B, tests)
-    const bool radix = n > kRankSortMax || no_rank_sort;
-    const u32 sort_tiles = (u32) ((n + kSortTile - 1) / kSortTile);
-    const size_t tmp_bytes = radix ? ((size_t) 256 * sort_tiles + 256) * sizeof(u32) : 0;  // digit totals + the tile histogram of a pass
-    {
-      MeshScratch a;
-      const size_t rank_words = !radix ? (size_t) n * (size_t) ((n + kRankSlice - 1) / kRankSlice) : 1;  // k_block_rank: one row of partial ranks per slice
-      a.bytes = (size_t) n * (8 * 3 + 16 + 4 + 4 * kMcNbStride + 512 + 8) + rank_words * 4 + tmp_bytes + (radix ? (size_t) n * sizeof(int4) + 256 : 0) + 32 * 256;
-      rc = arena_get(c, 0, a.bytes, &a.base);
-      if (rc) return rc;
-      k_in = a.take<u64>((size_t) n); k_out = a.take<u64>((size_t) n); d_offsets = a.take<u64>((size_t) n);
-      sorted = a.take<int4>((size_t) n); d_counts = a.take<u32>((size_t) n); d_nb = a.take<u32>((size_t) n * kMcNbStride);
-      d_per_voxel = a.take<uint8_t>((size_t) n * 512); d_total = a.take<u64>(2);
-      d_rec_base = a.take<u32>((size_t) n); d_rec_n = a.take<u32>((size_t) n); d_rec_ctr = a.take<u32>(2);
-      d_partial = a.take<u32>(rank_words);
-      tmp = a.take<char>(tmp_bytes ? tmp_bytes : 1);
-      if (radix) sorted2 = a.take<int4>((size_t) n);
-    }
-    if (!c->h_mc) {
-      HIP_TRY(c, hipHostMalloc((void**) &c->h_mc, 8 * sizeof(u64), hipHostMallocDefault));
-      memset(c->h_mc, 0, 8 * sizeof(u64));
-    }
-    if (!radix) {  // canonical order by counting (mrh_mc.h: k_block_rank)
-      const int slices = (n + kRankSlice - 1) / kRankSlice;
-      k_list_keys<<<(n + 255) / 256, 256, 0, s>>>(c->tab.compact, n, k_in);
-      k_block_rank<<<dim3((n + 255) / 256, slices), 256, 0, s>>>(k_in, n, d_partial);
-      k_block_scatter<<<(n + 255) / 256, 256, 0, s>>>(c->tab.compact, n, d_partial, slices, sorted);
-    } else {
-      // lists beyond the counting rank: the stable byte-wise radix sort of mrh_sort.h over the 64-bit position keys, the list
-      // entries riding along (eight passes of histogram / scan / scatter; the first reads the list itself, the last lands in `sorted`)
-      k_list_keys<<<(n + 255) / 256, 256, 0, s>>>(c->tab.compact, n, k_in);
-      u32* totals = (u32*) tmp;
-      u32* hist = totals + 256;
-      u64* ks[2] = {k_in, k_out};
-      int4* vs[2] = {sorted, sorted2};
-      int src = 0;
-      for (int shift = 0; shift < 64; shift += 8) {
-        k_sort_hist<u64><<<sort_tiles, kSortThreads, 0, s>>>(ks[src], (u32) n, shift, hist, sort_tiles);
-        k_sort_scan<<<256, 256, 0, s>>>(hist, sort_tiles, totals);
-        k_sort_scatter<u64, int4><<<sort_tiles, kSortThreads, 0, s>>>(ks[src], shift == 0 ? (const int4*) c->tab.compact : (const int4*) vs[src], ks[src ^ 1], vs[src ^ 1], (u32) n, shift,
-                                                                      hist, sort_tiles, totals);
-        src ^= 1;
-      }
-      static_assert((64 / 8) % 2 == 0, "an even number of passes ends in the first buffer pair");
-    }
-    k_mc_neighbors<<<(int) (((size_t) n * 32 + 255) / 256), 256, 0, s>>>(c->tab, sorted, n, d_nb);
-    if (dbg) { HIP_TRY(c, hipStreamSynchronize(s)); t1 = now(); }
-    // One workgroup per block, block e = workgroup id: the eight XCDs walk the position-sorted list side by side, so a block's
-    // neighbours are staged by other XCDs at about the same time and their rows come out of the memory-side Infinity Cache
-    // (rocprofv3 counts 3.3 x the algorithmic bytes on the L2 -> fabric side).  Round 5 measured the alternative — runs of 2^k
-    // blocks dealt to the XCDs in turn, so that neighbours share an L2 (mc_first_block; MRH_MC_SLAB_LOG2=k switches it on): the
-    // fabric traffic falls to 261 / 253 / 217 / 172 / 160 MB for k = 3 / 5 / 7 / 9 / one run per XCD, and the count pass gets
-    // SLOWER with every step, 0.246 -> 0.258 / 0.263 / 0.284 / 0.350 / 0.347 ms (profiles/r05/README.md): the re-reads are
-    // Infinity Cache hits, not HBM traffic, and they are not what the kernel waits for.  Off by default.
-    int slab_log2 = getenv("MRH_MC_SLAB_LOG2") ? std::min(20, std::max(0, atoi(getenv("MRH_MC_SLAB_LOG2")))) : -1;
-    while (slab_log2 > 0 && ((size_t) 8 << slab_log2) > (size_t) n + 8) slab_log2--;  // never more than one run per XCD
-    const int grid = slab_log2 < 0 ? n : (int) ((((size_t) n + ((size_t) 8 << slab_log2) - 1) >> (slab_log2 + 3)) << (slab_log2 + 3));
-    // largest truncation a stored sample can carry (integration clamps to trunc + scale * depth, depth <= the integration distance)
-    const float sdf_bound = c->has_camera && !getenv("MRH_MC_NO_PRESCREEN") ? c->map.trunc + c->map.trunc_scale * c->cam.max_int_dist : 0.f;
-    c->last_mc_count_ms = c->last_mc_emit_ms = 0.f;
-    c->last_mc_blocks = (uint64_t) n;
-    // kernel times for mrh_stats only in profile mode: launches that carry events switch the queue to its profiling mode,
-    // which slows every later dispatch of the process
-    const bool timed = c->profile != 0;
-    if (timed)
-      for (hipEvent_t& ev : c->mc_ev)
-        if (!ev) HIP_TRY(c, hipEventCreate(&ev));
-    // Corner records (mrh_mc.h McRecords): the count pass parks the corner values of every voxel that produces triangles, the
-    // emit pass interpolates them.  The buffer is sized from the last extraction's demand (first time: 128 records a block);
-    // if a block finds no room the whole extraction is emitted by k_mc<emit> and the buffer grows for the next one.
-    // MRH_MC_NO_RECORDS=1 keeps the two-pass evaluation (tests compare the two).
-    bool use_records = getenv("MRH_MC_NO_RECORDS") == nullptr;
-    if (use_records && c->mc_rec_cap == 0) {
-      const char* per_block = getenv("MRH_MC_RECORDS_PER_BLOCK");  // tests: a first buffer too small for the map
-      const size_t cap = std::max<size_t>((size_t) n * (size_t) (per_block ? std::max(1, atoi(per_block)) : 128), 16);
-      if (hipMalloc((void**) &c->d_mc_recs, cap * kMcRecWords * sizeof(u32)) == hipSuccess) c->mc_rec_cap = cap;
-      else { (void) hipGetLastError(); c->d_mc_recs = nullptr; use_records = false; }  // no room for the records: the two-pass emit needs none
-    }
-    McRecords R;
-    R.ctr = d_rec_ctr; R.recs = use_records ? c->d_mc_recs : nullptr; R.base = d_rec_base; R.count = d_rec_n;
-    R.cap = (u32) std::min<size_t>(c->mc_rec_cap, 0xFFFFFFF0u);
-    McRecords none;
-    none.ctr = nullptr; none.recs = nullptr; none.base = nullptr; none.count = nullptr; none.cap = 0;
-    if (use_records) HIP_TRY(c, hipMemsetAsync(d_rec_ctr, 0, 2 * sizeof(u32), s));
-    const int mc_flags = (getenv("MRH_MC_NO_COARSE_KNOWN") ? 2 : 0)   // bit 1: coarse voxels on the literal evaluation only (A/B, tests)
-                         | (slab_log2 < 0 ? 4 : (slab_log2 << 4));    // bit 2: block e = workgroup id; else bits 4..8: log2 of an XCD's run of blocks
-    if (timed) hipExtLaunchKernelGGL((k_mc<false>), dim3(grid), dim3(kMcThreads), 0, s, c->mc_ev[0], c->mc_ev[1], 0u, c->map, c->tab, (const int4*) sorted, n, (const u32*) d_nb,
-                                     (u32*) d_counts, (const u64*) nullptr, (mrh_triangle*) nullptr, (u64) 0, (uint8_t*) d_per_voxel, sdf_bound, mc_flags, R);
-    else k_mc<false><<<grid, kMcThreads, 0, s>>>(c->map, c->tab, sorted, n, d_nb, d_counts, nullptr, nullptr, (u64) 0, d_per_voxel, sdf_bound, mc_flags, R);
-    // exact offsets + the total: one workgroup chains tiles of 8 192 counts through a carry (10^6 blocks: 122 tiles, ~0.2 ms
-    // next to the ~20 ms of their count pass)
-    k_mc_scan_total<<<1, 1024, 0, s>>>(d_counts, n, d_offsets, use_records ? d_rec_ctr : nullptr, d_total);
-    HIP_TRY(c, hipMemcpyAsync(c->h_mc, d_total, 2 * sizeof(u64), hipMemcpyDeviceToHost, s));
-    auto emit = [&](const u64 cap, const int flag_overflow, const bool from_records) {
-      if (from_records) {
-        if (timed) hipExtLaunchKernelGGL(k_mc_emit_records, dim3(grid), dim3(kMcThreads), 0, s, c->mc_ev[2], c->mc_ev[3], 0u, c->map, c->tab, (const int4*) sorted, n, R,
-                                         (const u64*) d_offsets, (mrh_triangle*) c->d_soup, cap, flag_overflow | mc_flags);
-        else k_mc_emit_records<<<grid, kMcThreads, 0, s>>>(c->map, c->tab, sorted, n, R, d_offsets, c->d_soup, cap, flag_overflow | mc_flags);
-      } else {
-        if (timed) hipExtLaunchKernelGGL((k_mc<true>), dim3(grid), dim3(kMcThreads), 0, s, c->mc_ev[2], c->mc_ev[3], 0u, c->map, c->tab, (const int4*) sorted, n, (const u32*) d_nb,
-                                         (u32*) d_counts, (const u64*) d_offsets, (mrh_triangle*) c->d_soup, cap, (uint8_t*) d_per_voxel, 0.f, flag_overflow | mc_flags, none);
-        else k_mc<true><<<grid, kMcThreads, 0, s>>>(c->map, c->tab, sorted, n, d_nb, d_counts, d_offsets, c->d_soup, cap, d_per_voxel, 0.f, flag_overflow | mc_flags, none);
-      }
-    };
-    // The emit pass goes out BEFORE the host knows the total, into the soup buffer of the previous extraction (grow-only, 12 %
-    // head room): a map that is extracted again — the usual case — needs no round trip between the two passes.  Writes beyond
-    // the capacity are suppressed by the kernel; if the total turns out larger, the buffer grows and the pass runs again.
-    const u64 spec_cap = std::min<u64>(c->soup_cap, c->max_triangles);
-    // the host waits for the TOTAL, not for the emit pass behind it: it sizes and enqueues the post-process while the emit pass
-    // runs (a stream synchronisation here left the GPU idle for the ~20 us of the host's round trip and first launch)
-    if (!c->ev_mc_total) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mc_total, hipEventDisableTiming));
-    HIP_TRY(c, hipEventRecord(c->ev_mc_total, s));
-    if (spec_cap > 0) emit(spec_cap, 0, use_records);
-    HIP_TRY(c, hipEventSynchronize(c->ev_mc_total));
-    const u64 total = c->h_mc[0];
-    const u64 rec_demand = c->h_mc[1] & ~(1ull << 63);
-    const bool records_ok = use_records && (c->h_mc[1] >> 63) == 0;
-    const bool emitted = spec_cap > 0 && total <= spec_cap && (records_ok || !use_records);
-    struct GrowRecords {  // on every way out: room for this map's demand (+ 25 %) at the next extraction
-      mrh_ctx* c; u64 demand;
-      ~GrowRecords() {
-        if (demand <= c->mc_rec_cap) return;
-        (void) hipStreamSynchronize(c->stream);
-        if (c->d_mc_recs) (void) hipFree(c->d_mc_recs);
-        c->d_mc_recs = nullptr; c->mc_rec_cap = 0;
-        const size_t cap = (size_t) (demand + demand / 4);
-        if (hipMalloc((void**) &c->d_mc_recs, cap * kMcRecWords * sizeof(u32)) == hipSuccess) c->mc_rec_cap = cap;
-        else (void) hipGetLastError();  // no room: the next extraction starts from the default again
-      }
-    } grow_records{c, use_records ? rec_demand : 0};
-    if (dbg) t2 = now();
-    c->tri_dev_n = n;
-    c->d_tri_sorted = sorted;
-    c->d_tri_counts = d_counts;
-    if (total > c->max_triangles) {
-      return fail(c, MRH_ERR_CAPACITY, "triangle buffer full: %llu triangles > max_triangles %llu", (unsigned long long) total, (unsigned long long) c->max_triangles);
-    }
-    if (total > 0) {
-      if (!emitted) {
-        rc = ensure_soup(c, (size_t) total);
-        if (rc) return rc;
-        emit(total, 1, records_ok);
-        if (use_records && !records_ok) c->mc_rec_fallbacks++;
-      }
-      mrh_triangle* d_tris = c->d_soup;
-      c->soup_n = (size_t) total;
-      if (timed) {
-        HIP_TRY(c, hipEventSynchronize(c->mc_ev[3]));
-        HIP_TRY(c, hipEventElapsedTime(&c->last_mc_count_ms, c->mc_ev[0], c->mc_ev[1]));
-        HIP_TRY(c, hipEventElapsedTime(&c->last_mc_emit_ms, c->mc_ev[2], c->mc_ev[3]));
-      }
-      if (dbg) { HIP_TRY(c, hipStreamSynchronize(s)); t3 = now(); }
-      if (want_soup) {
-        c->tris.resize_discard(total);
-        if (c->tris.dev) {  // pinned: out through the copy kernel (see k_copy_out)
-          CopyOut a;
-          for (int p = 0; p < 3; p++) { a.src[p] = nullptr; a.dst[p] = nullptr; a.count[p] = nullptr; a.fixed[p] = 0; a.cap[p] = 0; a.unit[p] = 0; }
-          a.src[0] = (const uint4*) d_tris; a.dst[0] = (uint4*) c->tris.dev; a.fixed[0] = total; a.cap[0] = total; a.unit[0] = (u32) sizeof(mrh_triangle);
-          k_copy_out<<<1024, 256, 0, s>>>(a);
-        } else {
-          HIP_TRY(c, hipMemcpyAsync(c->tris.data(), d_tris, total * sizeof(mrh_triangle), hipMemcpyDeviceToHost, s));
-        }
-      }
-      if (dbg) { HIP_TRY(c, hipStreamSynchronize(s)); t4 = now(); }
-      int prc = MRH_OK;
-      if (c->merge_on) {  // the running mesh takes this soup; the post-process runs once, over everything, in mrh_mesh_merge_end
-        if (c->acc_n + total > c->acc_cap) {
-          const size_t cap = (c->acc_n + total) + (c->acc_n + total) / 2;
-          mrh_triangle* grown = nullptr;
-          HIP_TRY(c, hipMalloc((void**) &grown, cap * sizeof(mrh_triangle)));
-          if (c->acc_n) HIP_TRY(c, hipMemcpyAsync(grown, c->d_acc, c->acc_n * sizeof(mrh_triangle), hipMemcpyDeviceToDevice, s));
-          HIP_TRY(c, hipStreamSynchronize(s));
-          if (c->d_acc) HIP_TRY(c, hipFree(c->d_acc));
-          c->d_acc = grown; c->acc_cap = cap;
-        }
-        HIP_TRY(c, hipMemcpyAsync(c->d_acc + c->acc_n, d_tris, total * sizeof(mrh_triangle), hipMemcpyDeviceToDevice, s));
-        c->acc_n += total;
-        processed = true;
-      } else if (!c->mesh_on_host) { prc = process_triangles_device(c, d_tris, total); processed = true; }
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (prc) return prc;
-      n_tris = total;
-    } else if (timed) {
-      HIP_TRY(c, hipEventElapsedTime(&c->last_mc_count_ms, c->mc_ev[0], c->mc_ev[1]));
-    }
-    HIP_TRY(c, hipGetLastError());
-  }
-  c->last_triangles = n_tris;
-  if (!processed && !c->merge_on) process_triangles(c);
-  t5 = now();
-  if (dbg) fprintf(stderr, "[mrhash_hip] extract: %d blocks, %llu triangles | list+sort+neighbours %.2f ms, count+scan(+speculative emit) %.2f, emit %.2f, soup D2H %.2f, post-process + V/F/C D2H %.2f, total %.2f\n",
-                   n, (unsigned long long) n_tris, t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t5 - t0);
-  if (out_tris) *out_tris = c->tris.empty() ? nullptr : c->tris.data();
-  *out_n = n_tris;
-  return MRH_OK;
-}
-
-// MeshExtractor::merge_mesh_ = true (geowrapper.cpp:161) ... the chunk loop ... the final mesh.  The reference runs
-// processTriangles after every extraction, on (running mesh + new soup).  That equals ONE processTriangles over the soups back
-// to back: the vertex merge keeps first occurrences with their indices and colours, and "drop degenerate faces" / "drop
-// repeated faces keeping the first" are order-preserving filters, so applying them to a prefix first changes nothing
-// (tests/test_geowrapper_gpu.py compares with the oracle, which restates the incremental form literally).
-int mrh_mesh_merge_begin(mrh_ctx* c) {
-  if (!c) return MRH_ERR_INVALID_ARG;
-  c->n_extractions++;
-  c->merge_on = true;
-  c->acc_n = 0;
-  c->V.clear(); c->C.clear(); c->F.clear();
-  return MRH_OK;
-}
-
-int mrh_mesh_merge_end(mrh_ctx* c, uint64_t* out_total_triangles) {
-  int rc = ensure_ready(c, "mrh_mesh_merge_end");
-  if (rc) return rc;
-  if (!c->merge_on) return fail(c, MRH_ERR_STATE, "mrh_mesh_merge_end: no merge in progress (mrh_mesh_merge_begin)");
-  c->merge_on = false;
-  if (out_total_triangles) *out_total_triangles = c->acc_n;
-  c->last_triangles = c->acc_n;
-  c->tris.clear();
-  if (c->acc_n == 0) { c->V.clear(); c->C.clear(); c->F.clear(); return MRH_OK; }
-  if (c->mesh_on_host) {  // MRH_MESH_HOST=1: the host restatement of the post-process
-    c->tris.resize_discard(c->acc_n);
-    HIP_TRY(c, hipMemcpyAsync(c->tris.data(), c->d_acc, c->acc_n * sizeof(mrh_triangle), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    process_triangles(c);
-    return MRH_OK;
-  }
-  rc = process_triangles_device(c, c->d_acc, c->acc_n);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return rc;
-}
-
-int mrh_extract_mesh(mrh_ctx* c, const double** v, uint64_t* nv, const int32_t** f, uint64_t* nf, const double** col) {
-  if (!c || !v || !nv || !f || !nf || !col) return MRH_ERR_INVALID_ARG;
-  c->n_extractions++;  // the caller holds these pointers until the next extraction
-  *v = c->V.empty() ? nullptr : c->V.data();
-  *nv = c->V.size() / 3;
-  *f = c->F.empty() ? nullptr : c->F.data();
-  *nf = c->F.size() / 3;
-  *col = c->C.empty() ? nullptr : c->C.data();
-  return MRH_OK;
-}
-
 // Streamer, device half (streamer.cu:11-160): select by distance from the camera, copy out, free.
 int mrh_stream_out(mrh_ctx* c, const float center[3], float radius, mrh_block_desc* descs, mrh_voxel* voxels, uint64_t capacity,
                    uint64_t* out_n) {
@@ -3902,110 +3223,6 @@ int mrh_drop_blocks(mrh_ctx* c, int mode, uint64_t* out_dropped) {
   if (rc) return rc;
   if (out_dropped) *out_dropped = (uint64_t) n;
   return MRH_OK;
-}
-
-int mrh_get_triangle_blocks(mrh_ctx* c, const mrh_block_desc** out_descs, const uint32_t** out_counts, uint64_t* out_n) {
-  if (!c || !out_descs || !out_counts || !out_n) return MRH_ERR_INVALID_ARG;
-  if (c->tri_dev_n > 0) {  // the list and the counts of the last extraction are still where the kernels left them
-    const size_t n = (size_t) c->tri_dev_n;
-    std::vector<int4> list(n);
-    c->tri_counts.resize(n);
-    HIP_TRY(c, hipMemcpyAsync(list.data(), c->d_tri_sorted, n * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->tri_counts.data(), c->d_tri_counts, n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->tri_blocks.resize(n);
-    for (size_t i = 0; i < n; i++) c->tri_blocks[i] = {list[i].x, list[i].y, list[i].z, (list[i].w & (int) kValCoarseBit) ? 1 : 0};
-    c->tri_dev_n = 0;
-  }
-  *out_descs = c->tri_blocks.empty() ? nullptr : c->tri_blocks.data();
-  *out_counts = c->tri_counts.empty() ? nullptr : c->tri_counts.data();
-  *out_n = c->tri_blocks.size();
-  return MRH_OK;
-}
-
-int mrh_process_triangles(mrh_ctx* c, const mrh_triangle* triangles, uint64_t n) {
-  if (!c || (n && !triangles)) return MRH_ERR_INVALID_ARG;
-  c->tris.assign(triangles, triangles + n);
-  c->last_triangles = n;
-  if (c->mesh_on_host || n == 0) { process_triangles(c); return MRH_OK; }
-  int rc = ensure_ready(c, "mrh_process_triangles");
-  if (rc) return rc;
-  DevBuf<mrh_triangle> d_tris;
-  HIP_TRY(c, d_tris.alloc(n));
-  HIP_TRY(c, hipMemcpyAsync(d_tris, triangles, n * sizeof(mrh_triangle), hipMemcpyHostToDevice, c->stream));
-  return process_triangles_device(c, d_tris, n);
-}
-
-int mrh_get_triangles_device(mrh_ctx* c, const mrh_triangle** out, uint64_t* out_n, int* out_is_device_memory) {
-  if (!c || !out || !out_n) return MRH_ERR_INVALID_ARG;
-  *out = c->soup_n ? c->d_soup : nullptr;
-  *out_n = c->soup_n;
-  if (out_is_device_memory) *out_is_device_memory = 1;
-  return MRH_OK;
-}
-
-int mrh_process_triangle_runs(mrh_ctx* c, const mrh_block_desc* descs, const uint32_t* counts, uint64_t n_blocks, const mrh_triangle* triangles,
-                              uint64_t n_triangles, int is_device_memory) {
-  int rc = ensure_ready(c, "mrh_process_triangle_runs");
-  if (rc) return rc;
-  if ((n_blocks && (!descs || !counts)) || (n_triangles && !triangles)) return fail(c, MRH_ERR_INVALID_ARG, "mrh_process_triangle_runs: null argument");
-  hipStream_t s = c->stream;
-  // runs in input order -> canonical order (block position): a host sort of the few-byte descriptors, a device permutation
-  // of the 72-byte triangles
-  std::vector<uint64_t> src_off(n_blocks);
-  uint64_t total = 0;
-  for (uint64_t i = 0; i < n_blocks; i++) { src_off[i] = total; total += counts[i]; }
-  if (total != n_triangles) return fail(c, MRH_ERR_INVALID_ARG, "mrh_process_triangle_runs: the counts add up to %llu triangles, %llu given", (unsigned long long) total, (unsigned long long) n_triangles);
-  std::vector<uint32_t> order(n_blocks);
-  for (uint64_t i = 0; i < n_blocks; i++) order[i] = (uint32_t) i;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    if (descs[a].x != descs[b].x) return descs[a].x < descs[b].x;
-    if (descs[a].y != descs[b].y) return descs[a].y < descs[b].y;
-    return descs[a].z < descs[b].z;
-  });
-  c->tri_dev_n = 0;
-  c->tri_blocks.resize(n_blocks);
-  c->tri_counts.resize(n_blocks);
-  std::vector<ulonglong2> runs;  // {source offset, destination offset | count << 40}
-  runs.reserve(n_blocks);
-  uint64_t dst = 0;
-  for (uint64_t k = 0; k < n_blocks; k++) {
-    const uint32_t i = order[k];
-    c->tri_blocks[k] = descs[i];
-    c->tri_counts[k] = counts[i];
-    if (counts[i]) runs.push_back(make_ulonglong2(src_off[i], dst | ((uint64_t) counts[i] << 40)));
-    dst += counts[i];
-  }
-  c->tris.clear();
-  c->last_triangles = n_triangles;
-  c->soup_n = 0;
-  if (n_triangles == 0) { c->V.clear(); c->C.clear(); c->F.clear(); return MRH_OK; }
-  if (n_triangles >= (1ull << 40)) return fail(c, MRH_ERR_CAPACITY, "mrh_process_triangle_runs: too many triangles");
-  rc = ensure_soup(c, (size_t) n_triangles);
-  if (rc) return rc;
-  DevBuf<mrh_triangle> staged;
-  const mrh_triangle* d_in = triangles;
-  if (!is_device_memory) {
-    HIP_TRY(c, staged.alloc(n_triangles));
-    HIP_TRY(c, hipMemcpyAsync(staged, triangles, n_triangles * sizeof(mrh_triangle), hipMemcpyHostToDevice, s));
-    d_in = staged;
-  }
-  DevBuf<ulonglong2> d_runs;
-  HIP_TRY(c, d_runs.alloc(runs.size()));
-  HIP_TRY(c, hipMemcpyAsync(d_runs, runs.data(), runs.size() * sizeof(ulonglong2), hipMemcpyHostToDevice, s));
-  k_permute_runs<<<(int) std::min<size_t>(runs.size(), 8192), 256, 0, s>>>((const ulonglong2*) d_runs, (int) runs.size(), (const uint4*) d_in, (uint4*) c->d_soup);
-  c->soup_n = (size_t) n_triangles;
-  if (c->mesh_on_host) {
-    c->tris.resize_discard(n_triangles);
-    HIP_TRY(c, hipMemcpyAsync(c->tris.data(), c->d_soup, n_triangles * sizeof(mrh_triangle), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    process_triangles(c);
-    return MRH_OK;
-  }
-  rc = process_triangles_device(c, c->d_soup, n_triangles);
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipGetLastError());
-  return rc;
 }
 
 int mrh_selftest_division(mrh_ctx* c, uint64_t samples, uint64_t seed, uint64_t* out_mismatches) {

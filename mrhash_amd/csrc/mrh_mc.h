@@ -755,7 +755,7 @@ struct McRecords {
 };
 constexpr int kMcThreads = 256;
 // Which block a workgroup takes: its own id (flags bit 2, the default), or — MRH_MC_SLAB_LOG2=k, an experiment kept for the record
-// (mrh_capi.hip: mrh_extract_triangles has the numbers) — the list cut into runs of 2^k blocks dealt to the eight XCDs in turn
+// (mrh_extract.h: mc_pass_shape has the numbers) — the list cut into runs of 2^k blocks dealt to the eight XCDs in turn
 // (workgroups go to the XCDs round-robin by id), the j-th workgroup of an XCD taking the j-th block of that XCD's runs, so that a
 // block's neighbours are staged through the same L2.  The grid is then a multiple of 8 * 2^k: a permutation of the ids.
 // flags: bit 2 = block e = workgroup id; bits 4..8 = k.

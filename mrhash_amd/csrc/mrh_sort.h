@@ -151,6 +151,24 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_scatter(const K* __restri
   }
 }
 
+// Host side: the passes over key bits [0, end_bit), eight bits each, ping-pong between the two (keys, vals) buffer pairs; the
+// first pass reads pair 0's keys and, if `first_vals` is given, those values instead of vals[0] (the extraction sorts the block
+// list where it lies).  `totals` holds 256 words, `hist` 256 per tile of kSortTile records.  Returns the pair that holds the
+// sorted records (an even number of passes: 0).  Nothing is checked here: the caller sizes the buffers and reads the launch errors.
+template <typename K, typename V>
+int radix_sort_pairs(hipStream_t s, K* const keys[2], V* const vals[2], const V* first_vals, const size_t n, const int end_bit, u32* totals, u32* hist) {
+  const u32 ntiles = (u32) ((n + kSortTile - 1) / kSortTile);
+  int src = 0;
+  for (int shift = 0; shift < end_bit; shift += 8) {
+    k_sort_hist<K><<<ntiles, kSortThreads, 0, s>>>(keys[src], (u32) n, shift, hist, ntiles);
+    k_sort_scan<<<256, 256, 0, s>>>(hist, ntiles, totals);
+    k_sort_scatter<K, V><<<ntiles, kSortThreads, 0, s>>>(keys[src], shift == 0 && first_vals ? first_vals : (const V*) vals[src], keys[src ^ 1], vals[src ^ 1], (u32) n, shift,
+                                                          hist, ntiles, totals);
+    src ^= 1;
+  }
+  return src;
+}
+
 // Exclusive scan of n 64-bit words (the marks of a quad-tree, mrh_splat.h: two 32-bit counters in one word) in two launches of one
 // workgroup per tile of 4 096 words: the tiles' sums, then every tile adds up the sums in front of it (a few dozen words) and scans
 // itself through LDS (four neighbours a thread, loads and stores coalesced).  (A first version chained the tiles through one
