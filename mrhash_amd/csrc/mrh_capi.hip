@@ -286,28 +286,37 @@ struct mrh_ctx {
   uint64_t dbg_waits = 0;
   double dbg_spin_us = 0, dbg_api_us = 0; uint64_t dbg_lazy_frames = 0;  // MRH_DEBUG: where the host's time in a pipelined frame goes
   int4* d_cfree = nullptr;
-  // LiDAR scan of the current frame (mrh_lidar.h)
   float* d_cloud = nullptr; size_t cloud_n = 0;  // spherical camera: getDepth(cloud) image of the current frame (k_cloud_depth)
-  float* d_normals = nullptr; uint64_t normals_cap = 0, num_normals = 0;  // one normal per point (mrh_upload_normals)
   bool frame_general = false;       // this frame ran through the general kernels (mrh_kernels.h): GC by k_gc_identify / k_gc_free
   bool fast_summaries_stale = false;  // single-resolution map: a general frame left Fast::summary behind
-  float* d_points = nullptr;        // owned copy (mrh_upload_points) ...
-  const float* d_points_cur = nullptr;  // ... or the caller's device pointer (mrh_set_points_device)
-  uint64_t points_cap = 0, num_points = 0;
-  u32* d_pt_counts = nullptr; u32* d_pt_offsets = nullptr; uint64_t pt_cap = 0;
-  u32* h_scan = nullptr;               // pinned {hwm, last offset, last count, sequence}: the one report of a scan
-  u32 scan_seq = 0;
-  void* d_rec_keys[2] = {nullptr, nullptr}; float* d_rec_vals[2] = {nullptr, nullptr}; uint64_t rec_cap = 0; size_t rec_key_bytes = 0;
-  void* d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
-  // voxel-bucket scans (mrh_scan.h): per-voxel counters + block stamps (allocated with the first scan), stash, placed records, chunks
-  Scan scan = {};
-  int lidar_buckets = 1;         // MRH_LIDAR_BUCKETS=0: scans through the sorted records of mrh_lidar.h (cross-check)
-  int scan_state = 0;            // 0: scratch not tried yet, 1: allocated, -1: does not fit / not applicable (sorted path)
-  bool scan_dirty = false;       // a scan failed half way: the counters are cleared before the next one
-  uint64_t scan_rec_cap = 0, scan_wg_cap = 0;
-  u32* d_scan_ctr = nullptr;
-  u32 scan2_seq = 0;
-  size_t scan_lds_set = 0;
+  // LiDAR scans (mrh_points.h).  Nothing here is touched by mrh_reset: the counters are zero between scans, buckets_dirty covers a failed one
+  struct Lidar {
+    // ---- the cloud of the next scan
+    float* d_points = nullptr;        // owned copy (mrh_upload_points) ...
+    const float* d_points_cur = nullptr;  // ... or the caller's device pointer (mrh_set_points_device)
+    size_t points_cap = 0, num_points = 0;
+    float* d_normals = nullptr; size_t normals_cap = 0, num_normals = 0;  // one normal per point (mrh_upload_normals)
+    int layout_hint = 0;    // mrh_set_scan_layout / MRH_SCAN_ROW_LEN: > 0 points per row of the caller's organised scans, 0 find out (host clouds), < 0 none
+    int row_len = 0;        // ... of the CURRENT cloud (0: not organised, or not known)
+    uint64_t detect_n = 0;  // the look at a host cloud is repeated when the cloud's size changes and every 64th upload (a sensor keeps its layout;
+    int detect_len = 0, detect_age = 0;  // the look itself costs the calling thread ~20 us of cache misses, more than the order wins per scan)
+    int patch_log2 = 4;     // MRH_SCAN_PATCH_LOG2: columns (log2) of the beam patch a walk workgroup takes from an organised scan; 8 = 256 consecutive points
+    // ---- the sorted path (mrh_lidar.h): per-point counts, two (key, sdf) record buffers, the sort's scratch
+    u32* d_pt_counts = nullptr; u32* d_pt_offsets = nullptr; size_t pt_cap = 0;
+    u32* h_sorted_report = nullptr;   // pinned {hwm, last offset, last count, sequence}: the one report of a sorted scan
+    u32 sorted_seq = 0;
+    void* d_rec_keys[2] = {nullptr, nullptr}; float* d_rec_vals[2] = {nullptr, nullptr}; size_t rec_cap = 0, rec_key_bytes = 0;
+    void* d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
+    // ---- the voxel buckets (mrh_scan.h): per-voxel counters + block stamps (allocated with the first scan), stash, placed records, chunks
+    Scan buckets = {};
+    int use_buckets = 1;           // MRH_LIDAR_BUCKETS=0: scans through the sorted records of mrh_lidar.h (cross-check)
+    int buckets_scratch = 0;       // the counters and stamps — 0: not tried yet, 1: allocated, -1: do not fit / not applicable (sorted path)
+    bool buckets_dirty = false;    // a scan failed half way: the counters are cleared before the next one
+    size_t buckets_rec_cap = 0, buckets_wg_cap = 0;
+    u32* d_buckets_ctr = nullptr;  // two sets of SC_N counters: a scan zeroes the next one's
+    u32 buckets_seq = 0;
+    size_t buckets_lds_set = 0;
+  } lidar;
   // 3DGS splat seeds (mrh_splat.h): sized for one (image shape, min pixel size)
   QTree qt = {0, 0, 0, 0, 0};
   QSum* d_qt_sums = nullptr; u32* d_qt_flags = nullptr; u32* d_qt_unc = nullptr; u64* d_qt_marks = nullptr; u64* d_qt_pos = nullptr;
@@ -323,11 +332,6 @@ struct mrh_ctx {
   std::vector<mrh_qtree_leaf> qt_leaves;
   uint64_t qt_n_leaves = 0;            // leaves of the last mrh_splat_seeds, still on the device (d_qt_leaves) until someone asks
   bool qt_leaves_on_host = true;
-  int scan_layout_hint = 0;    // mrh_set_scan_layout / MRH_SCAN_ROW_LEN: > 0 points per row of the caller's organised scans, 0 find out (host clouds), < 0 none
-  int scan_row_len = 0;        // ... of the CURRENT cloud (0: not organised, or not known)
-  uint64_t scan_detect_n = 0;  // the look at a host cloud is repeated when the cloud's size changes and every 64th upload (a sensor keeps its layout;
-  int scan_detect_len = 0, scan_detect_age = 0;  // the look itself costs the calling thread ~20 us of cache misses, more than the order wins per scan)
-  int scan_patch_log2 = 4;     // MRH_SCAN_PATCH_LOG2: columns (log2) of the beam patch a walk workgroup takes from an organised scan; 8 = 256 consecutive points
   int mr_fused = 1;          // MRH_MR_FUSED=0: multi-resolution maps always through the general kernels (mrh_kernels.h)
   bool mr_next_general = true;    // the next multi-resolution frame must take the general path (frame 0 / after a starve frame / after an import)
   bool mr_summaries_valid = false;  // fast.summary / summary_c describe every live block (the general kernels do not maintain them)
@@ -460,6 +464,37 @@ struct DevBuf {
   operator T*() const { return p; }
 };
 
+// Grow-only device buffers of the context whose contents are NOT kept.  The old buffers are released before the new ones are
+// allocated (the peak is one buffer, not two), behind a drained stream unless the caller knows that nothing reads them
+// (sync = false), and `cap` is zero for as long as a pointer is null: an allocation that fails leaves "no buffer, capacity 0",
+// never a recorded capacity over a null pointer.  `members` grow together under the one capacity: all of them, or none.
+// Sizing — what is compared, head room, what else a grow resets — is the call site's.
+struct GrowMember {
+  void** p; size_t bytes;
+  template <typename T> GrowMember(T*& q, size_t b) : p((void**) &q), bytes(b) {}
+};
+int regrow_all(mrh_ctx* c, size_t& cap, const size_t cap_new, std::initializer_list<GrowMember> members, const bool sync = true) {
+  cap = 0;
+  if (sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (const GrowMember& m : members) {
+    if (*m.p) HIP_TRY(c, hipFree(*m.p));
+    *m.p = nullptr;
+  }
+  for (const GrowMember& m : members) {
+    const hipError_t e = hipMalloc(m.p, m.bytes);
+    if (e == hipSuccess) continue;
+    for (const GrowMember& f : members) { if (*f.p) (void) hipFree(*f.p); *f.p = nullptr; }
+    return fail(c, MRH_ERR_DEVICE, "hipMalloc of %zu bytes failed: %s", m.bytes, hipGetErrorString(e));
+  }
+  cap = cap_new;
+  return MRH_OK;
+}
+// one buffer of `bytes` bytes recorded as `cap_new`, if `cap_new` does not fit in `cap`
+template <typename T>
+int regrow(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes, const bool sync = true) {
+  return cap_new <= cap ? MRH_OK : regrow_all(c, cap, cap_new, {{p, bytes}}, sync);
+}
+
 uint64_t next_pow2(uint64_t v) {
   uint64_t r = 1;
   while (r < v) r <<= 1;
@@ -490,11 +525,11 @@ void free_all(mrh_ctx* c) {
   for (hipEvent_t e : c->peek_done) if (e) (void) hipEventDestroy(e);
   if (c->h_peek) (void) hipHostFree(c->h_peek);
   if (c->h_mc) (void) hipHostFree(c->h_mc);
-  if (c->h_scan) (void) hipHostFree(c->h_scan);
+  if (c->lidar.h_sorted_report) (void) hipHostFree(c->lidar.h_sorted_report);
   for (void* a : c->arena) if (a) (void) hipFree(a);
   F(c->d_decision); F(c->d_zbuf); F(c->d_zfused); F(c->d_realloc); F(c->d_reint); F(c->d_flag);
-  F(c->d_upd_partials); F(c->d_misc); F(c->d_rcp_w); F(c->d_cfree); F(c->d_zmin); F(c->d_points); F(c->d_pt_counts); F(c->d_pt_offsets); F(c->d_rec_keys[0]); F(c->d_rec_keys[1]); F(c->d_rec_vals[0]); F(c->d_rec_vals[1]); F(c->d_sort_tmp); F(c->scan.vcnt); F(c->scan.bstamp); F(c->scan.st_meta); F(c->scan.st_sdf); F(c->scan.st_grp); F(c->scan.wgdesc); F(c->scan.rec); F(c->scan.chunks); F(c->d_scan_ctr); F(c->fast.summary); F(c->fast.summary_c); F(c->fast.bbox); F(c->d_cnt_partials);
-  F(c->d_pack); F(c->d_halo); F(c->d_taken); F(c->d_cloud); F(c->d_normals); F(c->d_soup); F(c->d_mc_recs);
+  F(c->d_upd_partials); F(c->d_misc); F(c->d_rcp_w); F(c->d_cfree); F(c->d_zmin); F(c->lidar.d_points); F(c->lidar.d_pt_counts); F(c->lidar.d_pt_offsets); F(c->lidar.d_rec_keys[0]); F(c->lidar.d_rec_keys[1]); F(c->lidar.d_rec_vals[0]); F(c->lidar.d_rec_vals[1]); F(c->lidar.d_sort_tmp); F(c->lidar.buckets.vcnt); F(c->lidar.buckets.bstamp); F(c->lidar.buckets.st_meta); F(c->lidar.buckets.st_sdf); F(c->lidar.buckets.st_grp); F(c->lidar.buckets.wgdesc); F(c->lidar.buckets.rec); F(c->lidar.buckets.chunks); F(c->lidar.d_buckets_ctr); F(c->fast.summary); F(c->fast.summary_c); F(c->fast.bbox); F(c->d_cnt_partials);
+  F(c->d_pack); F(c->d_halo); F(c->d_taken); F(c->d_cloud); F(c->lidar.d_normals); F(c->d_soup); F(c->d_mc_recs);
   for (hipEvent_t e : c->mc_ev) if (e) (void) hipEventDestroy(e);
   if (c->ev_mc_total) (void) hipEventDestroy(c->ev_mc_total);
   comm_release(c);
@@ -587,7 +622,7 @@ int drain_events(mrh_ctx* c) {
 int check_device_flags(mrh_ctx* c, u32 flags) {
   // the flags are already cleared on the device (take_device_flags): whatever else is reported first, a scan that left its
   // bounds has left counters behind, and the next scan must start from zero
-  if (flags & ERR_SCAN) c->scan_dirty = true;
+  if (flags & ERR_SCAN) c->lidar.buckets_dirty = true;
   if (flags & ERR_RANGE) return fail(c, MRH_ERR_OUT_OF_RANGE, "a block coordinate left the packed-key range of +-2^20 blocks");
   if (flags & ERR_POOL) return fail(c, MRH_ERR_CAPACITY, "SDF block pool exhausted (num_sdf_blocks = %llu)", (unsigned long long) c->num_blocks);
   if (flags & ERR_TABLE) return fail(c, MRH_ERR_CAPACITY, "hash table probe limit reached (hash_slots = %llu)", (unsigned long long) c->slots);
@@ -660,12 +695,38 @@ int ensure_h_mc(mrh_ctx* c) {
   return MRH_OK;
 }
 
-// compacts every live block (no frustum filter) and returns the count; blocking
+// What every frame — images or a scan — does to the table before its kernels: the upkeep rebuilds from the descriptors, so the
+// zombies of the pipelined frames leave first
+int frame_upkeep(mrh_ctx* c) {
+  if (c->zombies_possible && c->census_period >= 0 && (c->table_dirty || c->frames_since_census >= (uint64_t) c->census_period)) {
+    const int rc = strict_point(c);
+    if (rc) return rc;
+  }
+  const int rc = maintain_table(c, false);
+  if (rc) return rc;
+  c->frames_since_census++;
+  return MRH_OK;
+}
+
+// coarse free-list refill of a multi-resolution map, decided on the device (vds.cu:885-891, :1048-1054)
+void refill_coarse(mrh_ctx* c) {
+  k_refill_decide<<<1, 64, 0, c->stream>>>(c->tab, c->low_blocks_to_allocate, c->d_flag);
+  k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, c->stream>>>(c->tab, c->low_blocks_to_allocate, c->d_flag);
+}
+
+// flatAndReduceHashTable() without a camera: every live block onto the compact list (no frustum filter); enqueue only
+int launch_compact_all(mrh_ctx* c) {
+  HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_COMPACT], 0, sizeof(int), c->stream));
+  k_compact<<<512, 256, 0, c->stream>>>(c->cam, c->map, c->tab, 0);
+  return MRH_OK;
+}
+
+// compacts every live block and returns the count; blocking
 int compact_all(mrh_ctx* c, int* out_n) {
   hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_COMPACT], 0, sizeof(int), s));
-  k_compact<<<512, 256, 0, s>>>(c->cam, c->map, c->tab, 0);
-  const int rc = ensure_h_mc(c);
+  int rc = launch_compact_all(c);
+  if (rc) return rc;
+  rc = ensure_h_mc(c);
   if (rc) return rc;
   HIP_TRY(c, hipMemcpyAsync(c->h_mc + HMC_COMPACT, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipStreamSynchronize(s));
@@ -677,13 +738,9 @@ int compact_all(mrh_ctx* c, int* out_n) {
 // grow-only scratch `slot` of at least `bytes` (contents undefined); the previous buffer is released only after the stream drained
 int arena_get(mrh_ctx* c, const int slot, const size_t bytes, void** out) {
   if (bytes > c->arena_cap[slot]) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->arena[slot]) HIP_TRY(c, hipFree(c->arena[slot]));
-    c->arena[slot] = nullptr; c->arena_cap[slot] = 0;
     if (slot == 1) c->mesh_clean_words = 0;  // new memory: the post-process's tables are not the empty ones it left behind
-    const size_t cap = bytes + bytes / 4;
-    HIP_TRY(c, hipMalloc(&c->arena[slot], cap));
-    c->arena_cap[slot] = cap;
+    const int rc = regrow(c, c->arena[slot], c->arena_cap[slot], bytes + bytes / 4, bytes + bytes / 4);
+    if (rc) return rc;
   }
   *out = c->arena[slot];
   return MRH_OK;
@@ -704,16 +761,7 @@ int arena_layout(mrh_ctx* c, const int slot, MeshScratch* m, Layout&& lay) {
   return MRH_OK;
 }
 
-int ensure_zbuf(mrh_ctx* c, size_t npix) {
-  if (c->zbuf_n < npix) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_zbuf) HIP_TRY(c, hipFree(c->d_zbuf));
-    c->d_zbuf = nullptr;
-    HIP_TRY(c, hipMalloc((void**) &c->d_zbuf, 2 * npix * sizeof(u64)));
-    c->zbuf_n = npix;
-  }
-  return MRH_OK;
-}
+int ensure_zbuf(mrh_ctx* c, size_t npix) { return regrow(c, c->d_zbuf, c->zbuf_n, npix, 2 * npix * sizeof(u64)); }
 
 // A starve frame of a single-resolution, unsharded map on the two-launch path: behind the frame's k_back<FREE = false>, the two
 // min-passes and the tail (pass 2 + summaries + garbage collection + the other z-buffer pair cleared) — three launches on the main
@@ -722,12 +770,9 @@ int launch_starve_fused(mrh_ctx* c, const Cam& k, const Fast& f, const Lists& L,
   const size_t npix = (size_t) k.rows * k.cols;
   hipStream_t s = c->stream;
   if (c->zfused_n < npix) {
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (c->d_zfused) HIP_TRY(c, hipFree(c->d_zfused));
-    c->d_zfused = nullptr; c->zfused_n = 0;
-    HIP_TRY(c, hipMalloc((void**) &c->d_zfused, 4 * npix * sizeof(u64)));
-    c->zfused_n = npix;
     c->zfused_clean[0] = c->zfused_clean[1] = false;
+    const int rc = regrow(c, c->d_zfused, c->zfused_n, npix, 4 * npix * sizeof(u64));
+    if (rc) return rc;
   }
   if (c->zfused_clean_npix != npix) c->zfused_clean[0] = c->zfused_clean[1] = false;  // the camera changed size since the pairs were cleared
   c->zfused_clean_npix = npix;
@@ -1034,10 +1079,10 @@ int mrh_create(const mrh_params* p, mrh_ctx** out) {
   c->V.pin = c->C.pin = c->f64_link;  // fp32 link: the doubles are written by the host only
   if (const char* g = getenv("MRH_QTREE_LITERAL")) c->qt_literal = atoi(g) ? 1 : 0;
   if (const char* g = getenv("MRH_MR_FUSED")) c->mr_fused = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_SCAN_ROW_LEN")) c->scan_layout_hint = atoi(g);
-  if (const char* g = getenv("MRH_SCAN_PATCH_LOG2")) { const int v = atoi(g); if (v >= 0 && v <= 8) c->scan_patch_log2 = v; }
-  if (const char* g = getenv("MRH_LIDAR_BUCKETS")) c->lidar_buckets = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_SCAN_SEQ_START")) c->scan2_seq = (u32) strtoul(g, nullptr, 0);  // tests: scans next to the wrap of the block stamps
+  if (const char* g = getenv("MRH_SCAN_ROW_LEN")) c->lidar.layout_hint = atoi(g);
+  if (const char* g = getenv("MRH_SCAN_PATCH_LOG2")) { const int v = atoi(g); if (v >= 0 && v <= 8) c->lidar.patch_log2 = v; }
+  if (const char* g = getenv("MRH_LIDAR_BUCKETS")) c->lidar.use_buckets = atoi(g) ? 1 : 0;
+  if (const char* g = getenv("MRH_SCAN_SEQ_START")) c->lidar.buckets_seq = (u32) strtoul(g, nullptr, 0);  // tests: scans next to the wrap of the block stamps
   if (const char* g = getenv("MRH_REHASH_PERIOD")) { const int v = atoi(g); if (v > 0) c->census_period = v; }
   if (const char* g = getenv("MRH_REHASH_FORCE")) c->census_force = atoi(g) ? 1 : 0;
   if (const char* g = getenv("MRH_REHASH_OFF")) { if (atoi(g)) c->census_period = -1; }  // no upkeep at all (tests: shows what it prevents)
@@ -1064,11 +1109,11 @@ int mrh_destroy(mrh_ctx* c) {
   if (getenv("MRH_DEBUG") && c->dbg_lazy_frames)
     fprintf(stderr, "[mrhash_hip] pipelined frames %llu: host waited %.1f us per frame for the ring, spent %.1f us per frame in the launch calls, %llu cross-stream waits\n",
             (unsigned long long) c->dbg_lazy_frames, c->dbg_spin_us / c->dbg_lazy_frames, c->dbg_api_us / c->dbg_lazy_frames, (unsigned long long) c->dbg_waits);
-  if (getenv("MRH_DEBUG") && c->d_scan_ctr && c->scan2_seq) {  // the last scan's counters (mrh_scan.h)
+  if (getenv("MRH_DEBUG") && c->lidar.d_buckets_ctr && c->lidar.buckets_seq) {  // the last scan's counters (mrh_scan.h)
     u32 h[2 * SC_N] = {0};
     (void) hipStreamSynchronize(c->stream);
-    (void) hipMemcpy(h, c->d_scan_ctr, sizeof(h), hipMemcpyDeviceToHost);
-    const u32* k = h + (c->scan2_seq & 1u) * SC_N;
+    (void) hipMemcpy(h, c->lidar.d_buckets_ctr, sizeof(h), hipMemcpyDeviceToHost);
+    const u32* k = h + (c->lidar.buckets_seq & 1u) * SC_N;
     fprintf(stderr, "[mrhash_hip] last scan: %u records, %u chunks + %u runs beyond a wave\n", k[SC_PLACED], k[SC_CHUNKS], k[SC_BIG]);
   }
 #ifdef MRH_TRACE
@@ -2065,21 +2110,14 @@ int integrate_general_frame(mrh_ctx* c, const int max_num_frames) {
   const Cam& k = c->cam;
   const Map& m = c->map;
   const Tab& t = c->tab;
-  // vds.cu:885-891 (coarse free-list refill), decided on the device
-  k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-  k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
+  refill_coarse(c);
   // the image every kernel below reads as "depth": the raw image (pinhole: cloud z == depth, cleaned on the fly) or, for
   // the spherical model, getDepth(cloud) computed once per frame
   const float* depth_img = c->d_depth;
   if (c->spherical) {
     const size_t npix = (size_t) k.rows * k.cols;
-    if (c->cloud_n < npix) {
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (c->d_cloud) HIP_TRY(c, hipFree(c->d_cloud));
-      c->d_cloud = nullptr;
-      HIP_TRY(c, hipMalloc((void**) &c->d_cloud, npix * sizeof(float)));
-      c->cloud_n = npix;
-    }
+    const int rc = regrow(c, c->d_cloud, c->cloud_n, npix, npix * sizeof(float));
+    if (rc) return rc;
     k_cloud_depth<<<(int) ((npix + 255) / 256), 256, 0, s>>>(k, c->d_depth, c->d_cloud);
     depth_img = c->d_cloud;
   }
@@ -2164,14 +2202,8 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
   const int max_num_frames = n_frames_invalidate < 0 ? c->p.n_frames_invalidate_voxels : n_frames_invalidate;
   hipStream_t s = c->stream;
   const Tab& t = c->tab;
-  // the table upkeep rebuilds from the descriptors: the zombies of the pipelined frames leave first
-  if (c->zombies_possible && c->census_period >= 0 && (c->table_dirty || c->frames_since_census >= (uint64_t) c->census_period)) {
-    rc = strict_point(c);
-    if (rc) return rc;
-  }
-  rc = maintain_table(c, false);
+  rc = frame_upkeep(c);
   if (rc) return rc;
-  c->frames_since_census++;
 
   // Multi-resolution maps take the same two launches when that is exact: the fused kernel checks the variance of a
   // fine block right after updating it, which covers every block the reference's checkVarSDF can newly decide on —
@@ -2190,11 +2222,9 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
   if (max_num_frames > 0 && starve_fused_ok(c) && c->zfused_n < (size_t) k.rows * k.cols) {
     // the z-buffers of the starve frames, both pairs empty, while the context is still allocating (not inside its first starve frame)
     const size_t npix = (size_t) k.rows * k.cols;
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (c->d_zfused) HIP_TRY(c, hipFree(c->d_zfused));
-    c->d_zfused = nullptr; c->zfused_n = 0;
-    HIP_TRY(c, hipMalloc((void**) &c->d_zfused, 4 * npix * sizeof(u64)));
-    c->zfused_n = npix;
+    c->zfused_clean[0] = c->zfused_clean[1] = false;
+    rc = regrow(c, c->d_zfused, c->zfused_n, npix, 4 * npix * sizeof(u64));
+    if (rc) return rc;
     k_fill_u64<<<512, 256, 0, s>>>(c->d_zfused, 4 * npix, 0x7FFFFFFFFFFFFFFFull);
     c->zfused_clean[0] = c->zfused_clean[1] = true;
     c->zfused_clean_npix = npix;
@@ -2208,393 +2238,9 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
 
 }  // extern "C"
 
-namespace {
-// Is this cloud an organised scan — rows of L points each, row-major, neighbours in the array neighbours in direction both along a
-// row and from one row to the next?  A few dozen point pairs decide: the candidate L (a power of two that leaves a multiple of 16
-// rows) whose points i and i + L lie closest in direction, if that and the step to i + 1 are within a few degrees.  Only a hint
-// for the order in which k_scan_walk takes the beams (mrh_scan.h: Scan::patch_log2): a wrong answer costs time, never a bit.
-int detect_scan_row_len(const float* xyz, const uint64_t n) {
-  if (n < 4096 || n % 256) return 0;
-  auto cos_between = [&](uint64_t a, uint64_t b, double* out) {
-    const float *p = xyz + 3 * a, *q = xyz + 3 * b;
-    const double pp = (double) p[0] * p[0] + (double) p[1] * p[1] + (double) p[2] * p[2], qq = (double) q[0] * q[0] + (double) q[1] * q[1] + (double) q[2] * q[2];
-    if (!(pp > 0.0) || !(qq > 0.0)) return false;  // a missing return
-    *out = ((double) p[0] * q[0] + (double) p[1] * q[1] + (double) p[2] * q[2]) / std::sqrt(pp * qq);
-    return true;
-  };
-  constexpr int kSamples = 96;
-  const double cos_limit = 0.99756;  // 4 degrees (a 16-beam sensor's rows are 2-3 degrees apart)
-  int best = 0;
-  double best_cos = cos_limit;
-  for (uint64_t L = 16; L <= 8192 && L * 16 <= n; L <<= 1) {
-    if (n % L || (n / L) % 16) continue;
-    double sum_row = 0.0, sum_next = 0.0;
-    int ok = 0;
-    for (int k = 0; k < kSamples; k++) {
-      const uint64_t i = (uint64_t) ((double) k * (double) (n - L - 2) / kSamples);
-      double a, b;
-      if ((i % L) + 1 < L && cos_between(i, i + 1, &a) && cos_between(i, i + L, &b)) { sum_next += a; sum_row += b; ok++; }
-    }
-    if (ok < kSamples / 4) continue;
-    if (sum_next / ok > cos_limit && sum_row / ok > best_cos) { best_cos = sum_row / ok; best = (int) L; }
-  }
-  return best;
-}
-}  // namespace
+#include "mrh_points.h"
 
 extern "C" {
-
-int mrh_detect_scan_layout(const float* xyz, uint64_t n) { return xyz ? detect_scan_row_len(xyz, n) : 0; }
-
-int mrh_set_scan_layout(mrh_ctx* c, int row_len) {
-  if (!c) return MRH_ERR_INVALID_ARG;
-  c->scan_layout_hint = row_len;
-  c->scan_row_len = row_len > 0 ? row_len : 0;
-  c->scan_detect_n = 0;
-  return MRH_OK;
-}
-
-int mrh_upload_points(mrh_ctx* c, const float* xyz, uint64_t n) {
-  int rc = ensure_ready(c, "mrh_upload_points");
-  if (rc) return rc;
-  if (n && !xyz) return fail(c, MRH_ERR_INVALID_ARG, "mrh_upload_points: null argument");
-  if (n > c->points_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_points) HIP_TRY(c, hipFree(c->d_points));
-    c->d_points = nullptr;
-    HIP_TRY(c, hipMalloc((void**) &c->d_points, n * 3 * sizeof(float)));
-    c->points_cap = n;
-  }
-  if (n) HIP_TRY(c, hipMemcpyAsync(c->d_points, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's buffer is free on return (GeoWrapper::setPointCloud copies)
-  c->d_points_cur = c->d_points;
-  c->num_points = n;
-  if (c->scan_layout_hint > 0) c->scan_row_len = c->scan_layout_hint;
-  else if (c->scan_layout_hint == 0 && n) {
-    if (n != c->scan_detect_n || ++c->scan_detect_age >= 64) {
-      c->scan_detect_len = detect_scan_row_len(xyz, n);
-      c->scan_detect_n = n;
-      c->scan_detect_age = 0;
-    }
-    c->scan_row_len = c->scan_detect_len;
-  } else c->scan_row_len = 0;
-  return MRH_OK;
-}
-
-int mrh_set_points_device(mrh_ctx* c, const float* d_xyz, uint64_t n) {
-  int rc = ensure_ready(c, "mrh_set_points_device");
-  if (rc) return rc;
-  if (n && !d_xyz) return fail(c, MRH_ERR_INVALID_ARG, "mrh_set_points_device: null argument");
-  c->d_points_cur = d_xyz;
-  c->num_points = n;
-  c->scan_row_len = c->scan_layout_hint > 0 ? c->scan_layout_hint : 0;  // a cloud in device memory is not looked at: mrh_set_scan_layout says how it is laid out
-  return MRH_OK;
-}
-
-int mrh_upload_normals(mrh_ctx* c, const float* nxyz, uint64_t n) {
-  int rc = ensure_ready(c, "mrh_upload_normals");
-  if (rc) return rc;
-  if (n && !nxyz) return fail(c, MRH_ERR_INVALID_ARG, "mrh_upload_normals: null argument");
-  if (n > c->normals_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_normals) HIP_TRY(c, hipFree(c->d_normals));
-    c->d_normals = nullptr;
-    HIP_TRY(c, hipMalloc((void**) &c->d_normals, n * 3 * sizeof(float)));
-    c->normals_cap = n;
-  }
-  if (n) HIP_TRY(c, hipMemcpyAsync(c->d_normals, nxyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the caller's buffer is free on return
-  c->num_normals = n;
-  return MRH_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// stable radix sort of the scan's (voxel id, sdf) records on key bits [0, end_bit): the padding key (all ones) ends up last,
-// equal ids keep their point-major order (mrh_sort.h)
-// *out_buf = which of the two buffer pairs holds the sorted records
-template <typename K>
-int lidar_sort(mrh_ctx* c, K* k0, K* k1, float* v0, float* v1, const size_t n, const int end_bit, int* out_buf) {
-  const u32 ntiles = (u32) ((n + kSortTile - 1) / kSortTile);
-  const u32 total = 256u * ntiles;
-  if (n > 0xFFFFFFFFull - kSortTile || (uint64_t) 256u * ntiles > kSortScanMax)  // records and histogram entries are indexed in 32 bits
-    return fail(c, MRH_ERR_CAPACITY, "mrh_integrate_points: %zu records in one scan through the sorted path (limit 2^32 - %d)", n, kSortTile + 1);
-  // the scan-sized sort of mrh_sort.h: per 8-bit digit a tile histogram, a one-workgroup scan, a stable scatter
-  hipStream_t s = c->stream;
-  if ((size_t) total * sizeof(u32) + 1024 > c->sort_tmp_bytes) {
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (c->d_sort_tmp) HIP_TRY(c, hipFree(c->d_sort_tmp));
-    c->d_sort_tmp = nullptr;
-    HIP_TRY(c, hipMalloc(&c->d_sort_tmp, (size_t) total * sizeof(u32) * 2 + 1024));
-    c->sort_tmp_bytes = (size_t) total * sizeof(u32) * 2 + 1024;
-  }
-  K* const ks[2] = {k0, k1};
-  float* const vs[2] = {v0, v1};
-  *out_buf = radix_sort_pairs<K, float>(s, ks, vs, nullptr, n, end_bit, (u32*) c->d_sort_tmp, (u32*) c->d_sort_tmp + 256);  // [0, 256): the digit totals
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// Scratch and buffers of the voxel-bucket scans (mrh_scan.h).  0: ready, 1: not on this context (the sorted path takes over), < 0: error.
-static int scan_prepare(mrh_ctx* c, const uint64_t n, const uint64_t rec_bound, const size_t walk_lds) {
-  hipStream_t s = c->stream;
-  Scan& sc = c->scan;
-  if (c->scan_state == 0) {
-    const size_t nb = (size_t) c->num_blocks;
-    bool ok = hipMalloc((void**) &sc.vcnt, nb * 512 * sizeof(u32)) == hipSuccess;
-    ok = ok && hipMalloc((void**) &sc.bstamp, nb * sizeof(u32)) == hipSuccess;
-    ok = ok && hipMalloc((void**) &c->d_scan_ctr, 2 * SC_N * sizeof(u32)) == hipSuccess;
-    if (!ok) {  // one counter per voxel slot does not fit next to this map
-      (void) hipGetLastError();
-      auto F = [](void* p) { if (p) (void) hipFree(p); };
-      F(sc.vcnt); F(sc.bstamp); F(c->d_scan_ctr);
-      sc.vcnt = sc.bstamp = c->d_scan_ctr = nullptr;
-      c->scan_state = -1;
-      return 1;
-    }
-    HIP_TRY(c, hipMemsetAsync(sc.vcnt, 0, nb * 512 * sizeof(u32), s));
-    HIP_TRY(c, hipMemsetAsync(sc.bstamp, 0, nb * sizeof(u32), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_scan_ctr, 0, 2 * SC_N * sizeof(u32), s));
-    c->scan_state = 1;
-    c->scan_dirty = false;
-  }
-  if (c->scan_dirty) {  // a scan that failed half way leaves counters behind
-    HIP_TRY(c, hipMemsetAsync(sc.vcnt, 0, (size_t) c->num_blocks * 512 * sizeof(u32), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_scan_ctr, 0, 2 * SC_N * sizeof(u32), s));
-    c->scan_dirty = false;
-  }
-  if (rec_bound > c->scan_rec_cap) {
-    HIP_TRY(c, hipStreamSynchronize(s));
-    for (void* p : {(void*) sc.st_meta, (void*) sc.st_sdf, (void*) sc.st_grp, (void*) sc.rec, (void*) sc.chunks})
-      if (p) HIP_TRY(c, hipFree(p));
-    sc.st_meta = nullptr; sc.st_sdf = nullptr; sc.st_grp = nullptr; sc.rec = nullptr; sc.chunks = nullptr;
-    c->scan_rec_cap = 0;
-    const uint64_t cap = rec_bound;
-    // chunks: one per touched block + one per kScanChunkWeight of weight (a record weighs at least 32: <= records / 256, taken as
-    // records / 128) + two per run beyond kScanLongRun (the run's own chunk and the cut behind it: <= 2 * records / 65)
-    const uint64_t chunk_cap = std::min<uint64_t>(c->num_blocks, cap) + cap / 128 + 2 * cap / (kScanLongRun + 1) + 64;
-    HIP_TRY(c, hipMalloc((void**) &sc.st_meta, cap * sizeof(uint2)));
-    HIP_TRY(c, hipMalloc((void**) &sc.st_sdf, cap * sizeof(float)));
-    HIP_TRY(c, hipMalloc((void**) &sc.st_grp, cap * sizeof(uint2)));
-    HIP_TRY(c, hipMalloc((void**) &sc.rec, cap * sizeof(uint4)));
-    HIP_TRY(c, hipMalloc((void**) &sc.chunks, chunk_cap * sizeof(uint4)));
-    sc.rec_cap = (u32) std::min<uint64_t>(cap, 0xFFFFFFF0ull);
-    sc.chunk_cap = (u32) std::min<uint64_t>(chunk_cap, 0xFFFFFFF0ull);
-    c->scan_rec_cap = cap;
-  }
-  const uint64_t wgs = (n + 255) / 256;
-  if (wgs > c->scan_wg_cap) {
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (sc.wgdesc) HIP_TRY(c, hipFree(sc.wgdesc));
-    sc.wgdesc = nullptr;
-    HIP_TRY(c, hipMalloc((void**) &sc.wgdesc, wgs * sizeof(uint2)));
-    c->scan_wg_cap = wgs;
-  }
-  if (walk_lds > 65536 && walk_lds > c->scan_lds_set) {
-    HIP_TRY(c, hipFuncSetAttribute((const void*) k_scan_walk, hipFuncAttributeMaxDynamicSharedMemorySize, (int) walk_lds));
-    c->scan_lds_set = walk_lds;
-  }
-  return 0;
-}
-
-// VoxelContainer::integrate(point_cloud, ...) voxel_data_structures.cpp:112-135 (mrh_lidar.h)
-int mrh_integrate_points(mrh_ctx* c, int n_frames_invalidate) {
-  int rc = ensure_ready(c, "mrh_integrate_points");
-  if (rc) return rc;
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_integrate_points: an exchange is pending (call mrh_integrate_resume)");
-  if (c->halo_upper) return fail(c, MRH_ERR_STATE, "mrh_integrate_points: halo blocks of other shards are present (call mrh_drop_blocks(MRH_DROP_HALO) after the extraction)");
-  if (!c->has_camera) return fail(c, MRH_ERR_STATE, "mrh_integrate_points: set_camera has not been called");
-  const int max_num_frames = n_frames_invalidate < 0 ? c->p.n_frames_invalidate_voxels : n_frames_invalidate;
-  const uint64_t n = c->num_points;
-  if (!c->p.projective_sdf && c->num_normals != n)
-    return fail(c, MRH_ERR_STATE, "mrh_integrate_points: the normal-direction SDF needs one normal per point (mrh_upload_normals)");
-  if (n >= (1ull << 24)) return fail(c, MRH_ERR_CAPACITY, "mrh_integrate_points: %llu points in one scan (limit 2^24 - 1)", (unsigned long long) n);
-  hipStream_t s = c->stream;
-  const Cam& k = c->cam;
-  const Map& m = c->map;
-  const Tab& t = c->tab;
-  // the table upkeep rebuilds from the descriptors: the zombies of the pipelined frames leave first
-  if (c->zombies_possible && c->census_period >= 0 && (c->table_dirty || c->frames_since_census >= (uint64_t) c->census_period)) {
-    rc = strict_point(c);
-    if (rc) return rc;
-  }
-  rc = maintain_table(c, false);
-  if (rc) return rc;
-  c->frames_since_census++;
-  c->frame_general = true;  // GC (and the starve step) of a scan run through the general kernels on the list of ALL live blocks
-  c->frame_fused_mr = false;
-  if (t.multi_res) { c->mr_summaries_valid = false; c->mr_next_general = true; c->refill_flag_valid = false; }
-  const float* normals = c->p.projective_sdf ? nullptr : c->d_normals;
-  if (n > 0) {
-    const u32 np = (u32) n, grid = (np + 255) / 256;
-    const float* pts = c->d_points_cur;
-    const u32 stamp = (u32) ((c->frames + 1) & 0x3FFFFFFFu);
-    if (t.multi_res) {  // vds.cu:1048-1054: coarse free-list refill, decided on the device
-      k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-      k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-    }
-    // an organised scan is taken in 2-D patches of beams (mrh_lidar.h: BeamOrder); its row length: mrh_set_scan_layout, the look
-    // at a host cloud (mrh_upload_points), or the spherical camera's columns if it has one pixel per point
-    BeamOrder order;
-    order.patch_log2 = 8; order.patches_per_row = 1; order.row_len = 256;
-    {
-      const int want = c->scan_patch_log2;
-      const uint64_t row_len = c->scan_row_len > 0 ? (uint64_t) c->scan_row_len : (c->scan_layout_hint == 0 && (uint64_t) k.rows * (uint64_t) k.cols == n ? (uint64_t) k.cols : 0);
-      if (want < 8 && row_len > 0 && n % row_len == 0 && row_len % (1u << want) == 0 && (n / row_len) % (256u >> want) == 0) {
-        order.patch_log2 = (u32) want; order.patches_per_row = (u32) (row_len >> want); order.row_len = (u32) row_len;
-      }
-    }
-    k_alloc3d<<<grid, 256, 0, s>>>(k, m, t, c->fast, pts, normals, np, stamp, order);
-    // ---- integrate3D (vds.cu:1215-1410): records of every (point, voxel) in point-major order -> stable sort by voxel -> fold.
-    // The record buffers are sized by a bound the host can compute (a beam crosses at most `slots` voxels), so the emit pass
-    // needs nothing from the host and runs WHILE the host picks up the scan's one report (record count, high-water mark: they
-    // size the sort): count -> scan -> report -> emit are enqueued together, the sort and the fold follow the report.
-    // slots: the voxel-level DDA walks from voxel(p_min) to voxel(p_max), |p_max - p_min| <= 2 tr, tr <= trunc + scale *
-    // integration distance: at most sum_axis(|end - start|) + 1 steps <= (2 tr / vs) * sqrt(3) + 3, plus the roundings
-    const double tr_max = (double) m.trunc + (double) m.trunc_scale * (double) k.max_int_dist;
-    const uint64_t slots = std::min<uint64_t>(kMaxDdaIter, (uint64_t) std::floor(2.0 * tr_max / (double) m.vs * 1.7320508) + 10);
-    const uint64_t rec_bound = n * slots;
-    if (rec_bound >= 0xFFFFFFF0ull) return fail(c, MRH_ERR_CAPACITY, "mrh_integrate_points: %llu points x %llu voxels per beam exceed 2^32 records per scan", (unsigned long long) n, (unsigned long long) slots);
-    // key width from the pool capacity: voxel id < cap * 512, one more bit for coarse units
-    auto bits_for = [](uint64_t max_value) { int b = 1; while (b < 63 && (max_value >> b)) b++; return b; };
-    const int coarse_bit = bits_for((uint64_t) c->num_blocks * 512 - 1);
-    const bool wide = coarse_bit + (t.multi_res ? 1 : 0) > 32;
-    const size_t key_bytes = wide ? 8 : 4;
-    // voxel buckets (mrh_scan.h) unless the map's voxel ids, the beam length or the memory say otherwise: then the sorted records below
-    bool buckets = c->lidar_buckets && c->scan_state >= 0 && !wide && (uint64_t) c->num_blocks * 512 < 0x7FFFFE00ull &&
-                   slots <= (uint64_t) kScanMaxSlots;
-    if (buckets) {
-      rc = scan_prepare(c, n, rec_bound, (size_t) (2 * slots * 256 + 2 * kScanSetSize) * sizeof(u32));
-      if (rc < 0) return rc;
-      buckets = rc == 0;
-    }
-    auto integrate_scan_buckets = [&]() -> int {
-      Scan sc = c->scan;
-      sc.seq = ++c->scan2_seq;
-      if (sc.seq >= 0x80000000u) {  // a block's stamp is seq * 2 + coarse in 32 bits: the sequence restarts at 1 with clean stamps
-        HIP_TRY(c, hipMemsetAsync(sc.bstamp, 0, (size_t) c->num_blocks * sizeof(u32), s));
-        // ... and with both counter sets at zero: the restart breaks the alternation that lets a scan zero the next one's set
-        HIP_TRY(c, hipMemsetAsync(c->d_scan_ctr, 0, 2 * SC_N * sizeof(u32), s));
-        sc.seq = c->scan2_seq = 1;
-      }
-      sc.ctr = c->d_scan_ctr + (sc.seq & 1u) * SC_N;
-      sc.ctr_next = c->d_scan_ctr + ((sc.seq + 1u) & 1u) * SC_N;
-      sc.ord_shift = t.multi_res ? 5 : 0;
-      sc.narrow = ((uint64_t) np << sc.ord_shift) <= (1ull << 23) && !getenv("MRH_SCAN_WIDE_RECORDS") ? 1 : 0;  // tag + 9 bits of voxel index in one word (MRH_SCAN_WIDE_RECORDS=1: tests)
-      sc.order = order;
-      const size_t lds = (size_t) (2 * slots * 256 + 2 * kScanSetSize) * sizeof(u32);
-      k_scan_walk<<<grid, 256, lds, s>>>(k, m, t, pts, normals, np, sc, (int) slots);
-      // the touched blocks are found by their stamps inside k_scan_offsets, windows of kScanWindow blocks; 512 workgroups walk the
-      // windows (2 048 of these 1 024-thread workgroups took 9 us to DISPATCH for ~1 us of work each, tools/trace_scan.py)
-      k_scan_offsets<<<std::min<u32>(512u, (u32) ((c->num_blocks + kScanWindow - 1) / kScanWindow)), 1024, 0, s>>>(t, sc, t.multi_res ? (u32) c->num_blocks : 0u);
-      k_scan_place<<<grid, 256, 0, s>>>(sc, (int) slots);
-      k_scan_apply<<<1536, 256, 0, s>>>(m, t, sc, np << sc.ord_shift, c->profile);
-      HIP_TRY(c, hipGetLastError());
-      return MRH_OK;
-    };
-    if (!buckets && (rec_bound > c->rec_cap || key_bytes > c->rec_key_bytes)) {
-      HIP_TRY(c, hipStreamSynchronize(s));
-      for (int b = 0; b < 2; b++) {
-        if (c->d_rec_keys[b]) HIP_TRY(c, hipFree(c->d_rec_keys[b]));
-        if (c->d_rec_vals[b]) HIP_TRY(c, hipFree(c->d_rec_vals[b]));
-        c->d_rec_keys[b] = nullptr; c->d_rec_vals[b] = nullptr;
-      }
-      const uint64_t cap = std::max<uint64_t>(rec_bound, c->rec_cap);
-      for (int b = 0; b < 2; b++) {
-        HIP_TRY(c, hipMalloc((void**) &c->d_rec_keys[b], cap * std::max(key_bytes, c->rec_key_bytes)));
-        HIP_TRY(c, hipMalloc((void**) &c->d_rec_vals[b], cap * sizeof(float)));
-      }
-      c->rec_cap = cap;
-      c->rec_key_bytes = std::max(key_bytes, c->rec_key_bytes);
-    }
-    if (!buckets && n > c->pt_cap) {
-      HIP_TRY(c, hipStreamSynchronize(s));
-      if (c->d_pt_counts) HIP_TRY(c, hipFree(c->d_pt_counts));
-      if (c->d_pt_offsets) HIP_TRY(c, hipFree(c->d_pt_offsets));
-      c->d_pt_counts = c->d_pt_offsets = nullptr;
-      HIP_TRY(c, hipMalloc((void**) &c->d_pt_counts, n * sizeof(u32)));
-      HIP_TRY(c, hipMalloc((void**) &c->d_pt_offsets, (n / 256 + 2) * sizeof(u32)));  // one total per count workgroup
-      c->pt_cap = n;
-    }
-    if (!c->h_scan) {
-      HIP_TRY(c, hipHostMalloc((void**) &c->h_scan, 4 * sizeof(u32), hipHostMallocDefault));
-      memset(c->h_scan, 0, 4 * sizeof(u32));
-    }
-    auto integrate_scan = [&]() -> int {
-      // the one host round trip of a scan: the emit pass derives its offsets from the per-workgroup totals itself, and its LAST
-      // workgroup, which knows the grand total before its walk starts, writes {high-water mark, records} and a sequence mark into
-      // pinned memory: the host reads it and enqueues the sort while the emit pass runs
-      ScanState ss;
-      ss.wg_totals = c->d_pt_offsets; ss.host_rec = c->h_scan; ss.seq = ++c->scan_seq;
-      const u32 seq = ss.seq;
-      k_points_walk<false, u32><<<grid, 256, 0, s>>>(k, m, t, pts, normals, np, c->d_pt_counts, ss, (u32*) nullptr, nullptr, coarse_bit, 0u);
-      if (wide) k_points_walk<true, u64><<<grid, 256, 0, s>>>(k, m, t, pts, normals, np, c->d_pt_counts, ss, (u64*) c->d_rec_keys[0], c->d_rec_vals[0], coarse_bit, (u32) std::min<uint64_t>(c->rec_cap, 0xFFFFFFFFull));
-      else k_points_walk<true, u32><<<grid, 256, 0, s>>>(k, m, t, pts, normals, np, c->d_pt_counts, ss, (u32*) c->d_rec_keys[0], c->d_rec_vals[0], coarse_bit, (u32) std::min<uint64_t>(c->rec_cap, 0xFFFFFFFFull));
-      HIP_TRY(c, hipGetLastError());
-      {
-        volatile u32* mark = c->h_scan + 3;
-        const auto t0 = std::chrono::steady_clock::now();
-        int spins = 0;
-        while (*mark != seq) {
-          MRH_CPU_RELAX();
-          if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;  // long scan or a fault
-        }
-        if (*mark != seq) HIP_TRY(c, hipStreamSynchronize(s));  // reports a device error if that is why the mark never came
-        if (*mark != seq) return fail(c, MRH_ERR_DEVICE, "mrh_integrate_points: the scan report did not arrive");
-        std::atomic_thread_fence(std::memory_order_acquire);
-      }
-      const int hwm = (int) c->h_scan[0];
-      const uint64_t n_rec = (uint64_t) c->h_scan[1];
-      if (n_rec > rec_bound) return fail(c, MRH_ERR_DEVICE, "mrh_integrate_points: %llu records exceed the bound of %llu", (unsigned long long) n_rec, (unsigned long long) rec_bound);
-      if (n_rec == 0) return MRH_OK;
-      // the sort only looks at the bits a voxel id of THIS map can have (the high-water mark of the pool); it is stable, and the
-      // records were emitted in point order: every voxel's run ends up in ascending point index (D6)
-      const int end_bit = t.multi_res ? coarse_bit + 1 : bits_for((uint64_t) (hwm > 0 ? hwm : 1) * 512 - 1);
-      const u32 agrid = (u32) ((n_rec + kApplyChunk - 1) / kApplyChunk);
-      int r, sb = 1;
-      if (wide) {
-        r = lidar_sort(c, (u64*) c->d_rec_keys[0], (u64*) c->d_rec_keys[1], c->d_rec_vals[0], c->d_rec_vals[1], (size_t) n_rec, end_bit, &sb);
-        if (r) return r;
-        k_points_apply<u64><<<agrid, 256, 0, s>>>(m, t, (const u64*) c->d_rec_keys[sb], c->d_rec_vals[sb], (u32) n_rec, coarse_bit, c->profile);
-      } else {
-        r = lidar_sort(c, (u32*) c->d_rec_keys[0], (u32*) c->d_rec_keys[1], c->d_rec_vals[0], c->d_rec_vals[1], (size_t) n_rec, end_bit, &sb);
-        if (r) return r;
-        k_points_apply<u32><<<agrid, 256, 0, s>>>(m, t, (const u32*) c->d_rec_keys[sb], c->d_rec_vals[sb], (u32) n_rec, coarse_bit, c->profile);
-      }
-      HIP_TRY(c, hipGetLastError());
-      return MRH_OK;
-    };
-    rc = buckets ? integrate_scan_buckets() : integrate_scan();
-    if (rc) return rc;
-    if (t.multi_res && c->frames > 0) {
-      // checkVarSDF -> reallocBlocks -> flatAndReduceHashTable() -> reintegrate3D, which launches integrate3DKernel again
-      // (vds.cu:1561-1580): the whole scan a second time, into fine and coarse blocks alike
-      HIP_TRY(c, hipMemsetAsync(&t.ctr[CTR_COMPACT], 0, sizeof(int), s));
-      k_compact<<<512, 256, 0, s>>>(k, m, t, 0);
-      HIP_TRY(c, hipMemsetAsync(&t.ctr[CTR_NREALLOC], 0, 2 * sizeof(int), s));  // NREALLOC, NREINT
-      k_check_var<<<2048, 64, 0, s>>>(m, t, c->d_realloc);
-      k_realloc<<<64, 256, 0, s>>>(t, c->d_realloc, c->d_reint);
-      rc = buckets ? integrate_scan_buckets() : integrate_scan();
-      if (rc) return rc;
-    }
-  }
-  if (max_num_frames > 0) {  // flatAndReduceHashTable() without a camera: every live block (voxel_data_structures.cpp:121, :126)
-    HIP_TRY(c, hipMemsetAsync(&t.ctr[CTR_COMPACT], 0, sizeof(int), s));
-    k_compact<<<512, 256, 0, s>>>(k, m, t, 0);
-  }
-  rc = starve_and_tail(c, max_num_frames);  // garbageCollect(camera, max_num_frames); counts the frame
-  if (rc < 0) return rc;
-  HIP_TRY(c, hipGetLastError());
-  if (c->peek_enabled) {
-    const int mrc = mark_frame(c);  // pool-level report for mrh_peek_free_blocks
-    if (mrc) return mrc;
-  }
-  return rc;
-}
 
 int mrh_integrate_resume(mrh_ctx* c) {
   int rc = ensure_ready(c, "mrh_integrate_resume");
@@ -3118,12 +2764,9 @@ int mrh_pack_blocks(mrh_ctx* c, int mode, int rank_arg, const mrh_block_record**
   *out_records = nullptr;
   if (n == 0) return MRH_OK;
   const size_t bytes = (size_t) n * sizeof(mrh_block_record);
-  if (bytes > c->pack_cap) {
-    if (c->d_pack) HIP_TRY(c, hipFree(c->d_pack));
-    c->d_pack = nullptr; c->pack_cap = 0;
-    const size_t cap = bytes + bytes / 4;
-    HIP_TRY(c, hipMalloc((void**) &c->d_pack, cap));
-    c->pack_cap = cap;
+  if (bytes > c->pack_cap) {  // select_blocks blocked: nothing reads the old buffer
+    rc = regrow(c, c->d_pack, c->pack_cap, bytes + bytes / 4, bytes + bytes / 4, false);
+    if (rc) return rc;
   }
   k_pack_records<<<n < 4096 ? n : 4096, 512, 0, c->stream>>>(c->tab, 0, n, c->d_pack);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3307,11 +2950,8 @@ int mrh_raycast(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major
   if (rc_) return rc_;
   const size_t npix = (size_t) rc.rows * (size_t) rc.cols;
   const size_t bytes = npix * (sizeof(float) * 4 + 3);
-  if (npix > c->ray_cap) {  // the previous raycast has finished (it blocked): nothing reads the old buffers
-    if (c->d_ray) { (void) hipFree(c->d_ray); c->d_ray = nullptr; c->ray_cap = 0; }
-    HIP_TRY(c, hipMalloc((void**) &c->d_ray, bytes));
-    c->ray_cap = npix;
-  }
+  rc_ = regrow(c, c->d_ray, c->ray_cap, npix, bytes, false);  // the previous raycast has finished (it blocked): nothing reads the old buffers
+  if (rc_) return rc_;
   if (npix > c->h_ray_cap) {
     if (c->h_ray) { (void) hipHostFree(c->h_ray); c->h_ray = nullptr; c->h_ray_cap = 0; }
     HIP_TRY(c, hipHostMalloc((void**) &c->h_ray, bytes, hipHostMallocDefault));

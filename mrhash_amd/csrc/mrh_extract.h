@@ -2,7 +2,7 @@
 // (mrh_extract_triangles: kernels in mrh_mc.h, the block sort's in mrh_mc.h / mrh_sort.h), the post-process
 // MeshExtractor::processTriangles on the device (kernels in mrh_mesh.h) or restated on the host, the read-back of V / C / F,
 // the merge mode and the triangle-run calls of the sharded extraction.  Included by mrh_capi.hip, same translation unit: it
-// needs the context's internals (mrh_ctx, HIP_TRY, arena_layout, compact_all, ensure_h_mc, the copy pool's widen_* calls).
+// needs the context's internals (mrh_ctx, HIP_TRY, regrow, arena_layout, compact_all, ensure_h_mc, the copy pool's widen_* calls).
 #pragma once
 
 namespace {
@@ -181,15 +181,8 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 
 // the soup buffer: grow-only, owned by the context, valid until the next extraction
 int ensure_soup(mrh_ctx* c, size_t n) {
-  if (n > c->soup_cap) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->d_soup) HIP_TRY(c, hipFree(c->d_soup));
-    c->d_soup = nullptr; c->soup_cap = 0;
-    const size_t cap = n + n / 8;
-    HIP_TRY(c, hipMalloc((void**) &c->d_soup, cap * sizeof(mrh_triangle) + 16));  // + 16: k_copy_out reads whole 16-byte words
-    c->soup_cap = cap;
-  }
-  return MRH_OK;
+  if (n <= c->soup_cap) return MRH_OK;
+  return regrow(c, c->d_soup, c->soup_cap, n + n / 8, (n + n / 8) * sizeof(mrh_triangle) + 16);  // + 16: k_copy_out reads whole 16-byte words
 }
 
 // ---- the post-process on the device: MeshExtractor::processTriangles (mrh_mesh.h) and the way out of V / C / F ------------------
