@@ -234,7 +234,8 @@ int mrh_upload_points(mrh_ctx* ctx, const float* xyz, uint64_t n);
 /* One normal per point of the current scan (sensor frame, any length: normalised on the device as vds.cu:1236 does), for
  * the normal-direction SDF (projective_sdf = 0, vds.cu:1248-1251, :1322-1326).  Replaces the first eigenvector the
  * reference takes from its MAD-tree (geowrapper.cpp:386-403: three eigenvectors per point, indexed by 3 * point,
- * vds.cu:1229); estimating normals is the caller's business here.  Copied before the call returns. */
+ * vds.cu:1229).  Normals the caller has; mrh_estimate_normals (mrhash_normals.h) fills the same buffer on the device from the
+ * current scan instead.  Copied before the call returns. */
 int mrh_upload_normals(mrh_ctx* ctx, const float* nxyz, uint64_t n);
 int mrh_set_points_device(mrh_ctx* ctx, const float* d_xyz, uint64_t n); /* zero-copy: device pointer, valid until the next integrate returns */
 int mrh_integrate_points(mrh_ctx* ctx, int n_frames_invalidate);

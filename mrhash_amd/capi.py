@@ -139,6 +139,21 @@ class MrhRaycastParams(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float), ("outputs", C.c_uint32)]
 
 
+# every symbol include/mrhash_normals.h declares (the HIP library only: the oracle is given its normals)
+NORMALS_SYMBOLS = ("mrh_estimate_normals_device mrh_estimate_normals mrh_get_normals").split()
+
+
+class MrhNormalsParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("min_points", C.c_uint32), ("min_spread", C.c_float), ("max_flatness", C.c_float)]
+
+
+class MrhNormalsInfo(C.Structure):
+    _fields_ = [("points", C.c_uint64), ("estimated", C.c_uint64), ("fallback", C.c_uint64), ("missing", C.c_uint64), ("cells", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class MrhCommStatus(C.Structure):
     _fields_ = [("rccl_ranks", C.c_int), ("rccl_rank", C.c_int), ("rccl_device", C.c_int), ("rccl_version", C.c_int), ("async_error", C.c_int),
                 ("async_error_string", C.c_char * 64), ("library_path", C.c_char * 256)]
@@ -235,6 +250,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_raycast.argtypes = [C.c_void_p, P(MrhRaycastParams), P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
         lib.mrh_raycast_device.argtypes = [C.c_void_p, P(MrhRaycastParams), P(C.c_float), P(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
         for name in RAYCAST_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_estimate_normals"):  # include/mrhash_normals.h
+        lib.mrh_estimate_normals_device.argtypes = [C.c_void_p, P(MrhNormalsParams), C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.mrh_estimate_normals.argtypes = [C.c_void_p, P(MrhNormalsParams), P(MrhNormalsInfo)]
+        lib.mrh_get_normals.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_uint64), P(MrhNormalsInfo)]
+        for name in NORMALS_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     return lib
 
@@ -707,6 +728,31 @@ class Engine:
         F = C.POINTER(C.c_float)
         self._check(self.lib.mrh_raycast_device(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), d_depth or None,
                                                 d_normals or None, d_rgb or None))
+
+    # -- scan normals (include/mrhash_normals.h) ----------------------------------------------------
+    def estimate_normals(self, radius=0.0, min_points=0, min_spread=0.0, max_flatness=0.0, info=False):
+        """Estimates one normal per point of the current scan (upload_points / set_points_device) on the device, into the
+        context's normal buffer: what upload_normals would otherwise be given (mrh_estimate_normals).  0 = the
+        default of a parameter.  info=True blocks and returns the counts {points, estimated, fallback, missing, cells}."""
+        p = MrhNormalsParams(radius, int(min_points), min_spread, max_flatness)
+        out = MrhNormalsInfo()
+        self._check(self.lib.mrh_estimate_normals(self._ctx, C.byref(p), C.byref(out) if info else None))
+        return out.as_dict() if info else None
+
+    def estimate_normals_device(self, ptr_xyz: int, n: int, ptr_out: int, radius=0.0, min_points=0, min_spread=0.0, max_flatness=0.0):
+        """mrh_estimate_normals_device: normals of the n points at device pointer ptr_xyz into device pointer ptr_out ([n, 3]
+        float32 each).  Ordered on the context's stream; finished by sync() or any blocking call."""
+        p = MrhNormalsParams(radius, int(min_points), min_spread, max_flatness)
+        self._check(self.lib.mrh_estimate_normals_device(self._ctx, C.byref(p), ptr_xyz or None, int(n), ptr_out or None))
+
+    def get_normals(self):
+        """(normals float32 [N, 3] as a numpy copy, counts of the estimate that made them): the context's normal buffer."""
+        ptr, n, info = C.c_void_p(), C.c_uint64(), MrhNormalsInfo()
+        self._check(self.lib.mrh_get_normals(self._ctx, C.byref(ptr), C.byref(n), C.byref(info)))
+        k = int(n.value)
+        if k == 0:
+            return np.zeros((0, 3), np.float32), info.as_dict()
+        return np.frombuffer((C.c_char * (k * 12)).from_address(ptr.value), dtype=np.float32).reshape(k, 3).copy(), info.as_dict()
 
     def get_voxel(self, vx: int, vy: int, vz: int):
         out = np.zeros(1, dtype=VOXEL_DTYPE)

@@ -18,7 +18,7 @@
 
 namespace pygeowrapper {
 
-void GeoWrapper::check(int rc, const char* what) {
+void GeoWrapper::check(int rc, const char* what) const {
   if (rc != MRH_OK) throw std::runtime_error(std::string("GeoWrapper::") + what + " | " + mrh_last_error(ctx_));
 }
 
@@ -164,10 +164,23 @@ void GeoWrapper::setRGBImage(const uint8_t* data, size_t rows, size_t cols) {
   have_rgb_ = true;
 }
 
-void GeoWrapper::setPointCloud(const float* pts, size_t n, const float* normals_or_null) {
+void GeoWrapper::setPointCloud(const float* pts, size_t n, const float* normals_or_null, bool compute_normals) {
   point_cloud_.assign(pts, pts + 3 * n);
   if (normals_or_null) normals_.assign(normals_or_null, normals_or_null + 3 * n);
   else normals_.clear();
+  estimate_normals_ = compute_normals && !normals_or_null;
+  normals_on_device_ = false;
+}
+
+const std::vector<float>& GeoWrapper::normals() const {
+  if (normals_on_device_) {
+    const float* nxyz = nullptr;
+    uint64_t n = 0;
+    check(mrh_get_normals(ctx_, &nxyz, &n, nullptr), "getNormals");
+    normals_.assign(nxyz, nxyz + 3 * n);
+    normals_on_device_ = false;
+  }
+  return normals_;
 }
 
 // ---- streamer, host side: chunk grid (streamer.cuh:251-352, streamer.cpp:214-247, :292-331) ---------------------------
@@ -295,9 +308,14 @@ void GeoWrapper::compute() {
     // Normals passed along with the points (one per point) drive the normal-direction SDF when the wrapper was built with
     // projective_sdf = false (vds.cu:1248-1251, :1322-1326); with the projective SDF (every shipped configuration and
     // runner) the reference only normalises them and never uses them (vds.cu:1236), so they are simply not needed.
-    // Estimating normals (the reference's MAD-tree, geowrapper.cpp:377-403) is the caller's business here.
-    if (!normals_.empty()) check(mrh_upload_normals(ctx_, normals_.data(), normals_.size() / 3), "compute");
+    // setPointCloud(points, compute_normals = true) has them estimated on the device from the uploaded points, one plane per
+    // 0.4 m neighbourhood as the reference's MAD-tree leaves (geowrapper.cpp:377-403); the definition is DESIGN.md D12.
+    if (!normals_.empty() && !estimate_normals_) check(mrh_upload_normals(ctx_, normals_.data(), normals_.size() / 3), "compute");
     check(mrh_upload_points(ctx_, point_cloud_.data(), point_cloud_.size() / 3), "compute");
+    if (estimate_normals_) {
+      check(mrh_estimate_normals(ctx_, nullptr, nullptr), "compute");
+      normals_on_device_ = true;
+    }
     check(mrh_integrate_points(ctx_, n_frames_invalidate_voxels_), "compute");
   }
 }

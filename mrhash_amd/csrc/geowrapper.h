@@ -13,6 +13,7 @@
 #include "mrhash_hip.h"
 #include "mrhash_comm.h"
 #include "mrhash_raycast.h"
+#include "mrhash_normals.h"
 
 namespace pygeowrapper {
 
@@ -62,9 +63,12 @@ public:
   // raw-pointer forms of the numpy setters; shape checks live in the binding (geowrapper.cpp:246-321)
   void setDepthImage(const float* data, size_t rows, size_t cols);
   void setRGBImage(const uint8_t* data, size_t rows, size_t cols);
-  void setPointCloud(const float* pts, size_t n, const float* normals_or_null);
+  // normals_or_null: one per point, or none; compute_normals (without normals): compute() estimates them on the device
+  // (mrh_estimate_normals), as the reference's MAD-tree does on the host (geowrapper.cpp:374-404)
+  void setPointCloud(const float* pts, size_t n, const float* normals_or_null, bool compute_normals = false);
   const std::vector<float>& pointCloud() const { return point_cloud_; }
-  const std::vector<float>& normals() const { return normals_; }
+  // the normals given to setPointCloud, or, after a compute() that estimated them, those: read back on the first call only
+  const std::vector<float>& normals() const;
 
   void compute();                                // geowrapper.cpp:118-148
   void extractMesh(const std::string& filename);  // geowrapper.cpp:150-230
@@ -120,7 +124,7 @@ public:
   mrh_ctx* ctx() { return ctx_; }
 
 private:
-  void check(int rc, const char* what);
+  void check(int rc, const char* what) const;
   // host side of the streamer (streamer.cuh:40-80, :251-352): chunk grid of streamed-out blocks
   struct HostBlock {
     mrh_block_desc desc;
@@ -160,7 +164,10 @@ private:
   bool have_depth_ = false, have_rgb_ = false;  // the images themselves live in the library (pinned staging + device slots)
   std::vector<uint8_t> rgb_;
   size_t depth_rows_ = 0, depth_cols_ = 0, rgb_rows_ = 0, rgb_cols_ = 0;
-  std::vector<float> point_cloud_, normals_;
+  std::vector<float> point_cloud_;
+  mutable std::vector<float> normals_;
+  bool estimate_normals_ = false;           // setPointCloud(..., compute_normals = true): compute() estimates on the device
+  mutable bool normals_on_device_ = false;  // ... and did: normals_ is filled by the first normals() after it
   void cacheMesh() const;
   void writeMesh(const std::string& filename, double t0);
   mutable std::vector<double> V_, C_;

@@ -33,9 +33,11 @@
 #include "../../include/mrhash_hip.h"
 #include "../../include/mrhash_comm.h"
 #include "../../include/mrhash_raycast.h"
+#include "../../include/mrhash_normals.h"
 #include "mrh_kernels.h"
 #include "mrh_mc.h"
 #include "mrh_raycast.h"
+#include "mrh_normals.h"
 #include "mrh_fast.h"
 #include "mrh_pipe.h"
 #include "mrh_fast2.h"
@@ -295,7 +297,8 @@ struct mrh_ctx {
     float* d_points = nullptr;        // owned copy (mrh_upload_points) ...
     const float* d_points_cur = nullptr;  // ... or the caller's device pointer (mrh_set_points_device)
     size_t points_cap = 0, num_points = 0;
-    float* d_normals = nullptr; size_t normals_cap = 0, num_normals = 0;  // one normal per point (mrh_upload_normals)
+    float* d_normals = nullptr; size_t normals_cap = 0, num_normals = 0;  // one normal per point (mrh_upload_normals, mrh_estimate_normals)
+    bool have_cloud = false;          // a scan has been handed over (mrh_upload_points / mrh_set_points_device), n = 0 included
     int layout_hint = 0;    // mrh_set_scan_layout / MRH_SCAN_ROW_LEN: > 0 points per row of the caller's organised scans, 0 find out (host clouds), < 0 none
     int row_len = 0;        // ... of the CURRENT cloud (0: not organised, or not known)
     uint64_t detect_n = 0;  // the look at a host cloud is repeated when the cloud's size changes and every 64th upload (a sensor keeps its layout;
@@ -426,6 +429,20 @@ struct mrh_ctx {
   // pixel and the pinned host copy the caller reads
   char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
   char* h_ray = nullptr; size_t h_ray_cap = 0;
+  // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of
+  // every point, grow-only; two sets of counters, a scan's last launch zeroes the next one's
+  struct Normals {
+    NrmTab tab = {};
+    size_t cap = 0;                // points the scratch holds
+    u64* d_ctr = nullptr;          // [2][NC_N]
+    u32 seq = 0;
+    bool dirty = false;            // a call failed between its first and its last launch: table and counters are cleared first
+    int fold = 1;                  // MRH_NORMALS_FOLD=0: k_normals_accumulate<false> (A/B, tests)
+    u64* h_ctr = nullptr;          // pinned [NC_N]: the counters of the last mrh_estimate_normals, copied behind its kernels
+    mrh_normals_info info = {};    // ... as the caller sees them; `points` = 0 and info_pending = false: none
+    bool info_pending = false;     // h_ctr has not been folded into `info` yet
+    float* h_out = nullptr; size_t h_out_cap = 0;  // pinned: what mrh_get_normals hands out
+  } nrm;
   std::string err;
 };
 
@@ -540,6 +557,9 @@ void free_all(mrh_ctx* c) {
   F(c->d_qt_sums); F(c->d_qt_flags); F(c->d_qt_unc); F(c->d_qt_marks); F(c->d_qt_pos); F(c->d_qt_parked); F(c->d_qt_leaves); F(c->d_qt_misc);
   F(c->d_ray);
   if (c->h_ray) (void) hipHostFree(c->h_ray);
+  F(c->nrm.tab.keys); F(c->nrm.tab.sums); F(c->nrm.tab.cell); F(c->nrm.tab.list); F(c->nrm.tab.pt_slot); F(c->nrm.tab.partial); F(c->nrm.d_ctr);
+  if (c->nrm.h_ctr) (void) hipHostFree(c->nrm.h_ctr);
+  if (c->nrm.h_out) (void) hipHostFree(c->nrm.h_out);
   if (c->h_qt_seeds) (void) hipHostFree(c->h_qt_seeds);
   if (c->h_qt_out) (void) hipHostFree(c->h_qt_out);
   for (int i = 0; i < c->npend; i++) if (c->pendq[i].profile) c->ev_pool.push_back(c->pendq[i].ev);
@@ -1082,6 +1102,7 @@ int mrh_create(const mrh_params* p, mrh_ctx** out) {
   if (const char* g = getenv("MRH_SCAN_ROW_LEN")) c->lidar.layout_hint = atoi(g);
   if (const char* g = getenv("MRH_SCAN_PATCH_LOG2")) { const int v = atoi(g); if (v >= 0 && v <= 8) c->lidar.patch_log2 = v; }
   if (const char* g = getenv("MRH_LIDAR_BUCKETS")) c->lidar.use_buckets = atoi(g) ? 1 : 0;
+  if (const char* g = getenv("MRH_NORMALS_FOLD")) c->nrm.fold = atoi(g) ? 1 : 0;
   if (const char* g = getenv("MRH_SCAN_SEQ_START")) c->lidar.buckets_seq = (u32) strtoul(g, nullptr, 0);  // tests: scans next to the wrap of the block stamps
   if (const char* g = getenv("MRH_REHASH_PERIOD")) { const int v = atoi(g); if (v > 0) c->census_period = v; }
   if (const char* g = getenv("MRH_REHASH_FORCE")) c->census_force = atoi(g) ? 1 : 0;
@@ -2983,6 +3004,161 @@ int mrh_raycast_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_ro
   if (rc_) return rc_;
   launch_raycast(c, rc, d_depth, (p->outputs & MRH_RAYCAST_NORMALS) ? d_normals : nullptr, (p->outputs & MRH_RAYCAST_COLORS) ? d_rgb : nullptr);
   HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+
+}  // extern "C"
+
+// ---- normal estimation (include/mrhash_normals.h, mrh_normals.h) ------------------------------------------------------------
+extern "C++" {
+namespace {
+
+// the parameter block with its defaults filled in, as the kernels take it
+int normals_args(mrh_ctx* c, const char* who, const mrh_normals_params* p, const uint64_t n, NrmPar* out) {
+  mrh_normals_params q = {0.f, 0u, 0.f, 0.f};
+  if (p) q = *p;
+  auto bad = [](float v) { return !(v >= 0.f) || !std::isfinite(v); };
+  if (bad(q.radius) || bad(q.min_spread) || bad(q.max_flatness) || q.max_flatness >= 1.f)
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: bad parameter (radius %g, min_spread %g, max_flatness %g)", who, (double) q.radius, (double) q.min_spread, (double) q.max_flatness);
+  if (n >= (1ull << 24)) return fail(c, MRH_ERR_CAPACITY, "%s: %llu points in one scan (limit 2^24 - 1)", who, (unsigned long long) n);
+  out->rho = q.radius == 0.f ? 2.0f * c->p.virtual_voxel_size : q.radius;
+  if (!(out->rho > 0.f) || !std::isfinite(out->rho)) return fail(c, MRH_ERR_INVALID_ARG, "%s: the cell side must be > 0 (radius %g)", who, (double) out->rho);
+  out->min_points = q.min_points == 0u ? 5u : q.min_points;
+  const double spread = 1024.0 * (q.min_spread == 0.f ? 0.0625 : (double) q.min_spread);
+  out->min_l1 = spread * spread;
+  out->max_flat = q.max_flatness == 0.f ? 0.0625 : (double) q.max_flatness;
+  return MRH_OK;
+}
+
+// scratch for n points: grown to the next power of two, born clean
+int normals_scratch(mrh_ctx* c, const uint64_t n) {
+  auto& N = c->nrm;
+  hipStream_t s = c->stream;
+  if (!N.d_ctr) {
+    HIP_TRY(c, hipMalloc((void**) &N.d_ctr, 2 * NC_N * sizeof(u64)));
+    HIP_TRY(c, hipMemsetAsync(N.d_ctr, 0, 2 * NC_N * sizeof(u64), s));
+  }
+  if (n > N.cap) {
+    const size_t cap = (size_t) next_pow2(std::max<uint64_t>(n, 512)), slots = 2 * cap;
+    NrmTab& t = N.tab;
+    const int rc = regrow_all(c, N.cap, cap, {{t.keys, slots * sizeof(u64)}, {t.sums, slots * kNrmSums * sizeof(u64)}, {t.cell, slots * sizeof(float4)},
+                                              {t.list, cap * sizeof(u32)}, {t.pt_slot, cap * sizeof(u32)}, {t.partial, (cap / 256 + 1) * 3 * sizeof(u32)}});
+    if (rc) return rc;
+    t.mask = (u32) (slots - 1);
+    N.dirty = true;
+  }
+  if (N.dirty) {
+    const size_t slots = (size_t) N.tab.mask + 1;
+    HIP_TRY(c, hipMemsetAsync(N.tab.keys, 0xFF, slots * sizeof(u64), s));
+    HIP_TRY(c, hipMemsetAsync(N.tab.sums, 0, slots * kNrmSums * sizeof(u64), s));
+    HIP_TRY(c, hipMemsetAsync(N.d_ctr, 0, 2 * NC_N * sizeof(u64), s));
+    N.dirty = false;
+  }
+  return MRH_OK;
+}
+
+// The four launches of one scan, n > 0.  *out_ctr: this scan's counters on the device, valid until the scan after the next
+int launch_normals(mrh_ctx* c, const NrmPar& par, const float* d_xyz, const uint64_t n, float* d_nxyz, const u64** out_ctr) {
+  int rc = normals_scratch(c, n);
+  if (rc) return rc;
+  auto& N = c->nrm;
+  hipStream_t s = c->stream;
+  NrmTab t = N.tab;
+  const u32 set = ++N.seq & 1u;
+  t.ctr = N.d_ctr + set * NC_N;
+  t.ctr_next = N.d_ctr + (set ^ 1u) * NC_N;
+  const u32 np = (u32) n, grid = (np + 255u) / 256u;
+  N.dirty = true;
+  if (N.fold) k_normals_accumulate<true><<<grid, 256, 0, s>>>(t, par, d_xyz, np);
+  else k_normals_accumulate<false><<<grid, 256, 0, s>>>(t, par, d_xyz, np);
+  k_normals_solve<<<std::min<u32>(1024u, (np + kNrmSolveCells - 1) / kNrmSolveCells), 1024, 0, s>>>(t, par);
+  k_normals_assign<<<grid, 256, 0, s>>>(t, d_xyz, np, d_nxyz);
+  k_normals_sweep<<<std::min<u32>(1024u, grid), 256, 0, s>>>(t, grid);
+  HIP_TRY(c, hipGetLastError());
+  N.dirty = false;
+  *out_ctr = t.ctr;
+  return MRH_OK;
+}
+
+// the counters of the last mrh_estimate_normals have landed in pinned memory (the caller synchronised): into Normals::info
+void normals_fold_info(mrh_ctx* c) {
+  auto& N = c->nrm;
+  if (!N.info_pending) return;
+  N.info.estimated = N.h_ctr[NC_ESTIMATED]; N.info.fallback = N.h_ctr[NC_FALLBACK];
+  N.info.missing = N.h_ctr[NC_MISSING]; N.info.cells = N.h_ctr[NC_CELLS];
+  N.info_pending = false;
+}
+
+}  // namespace
+}  // extern "C++"
+
+extern "C" {
+
+int mrh_estimate_normals_device(mrh_ctx* c, const mrh_normals_params* p, const float* d_xyz, uint64_t n, float* d_nxyz) {
+  int rc = ensure_device(c, "mrh_estimate_normals_device");
+  if (rc) return rc;
+  if (n && (!d_xyz || !d_nxyz)) return fail(c, MRH_ERR_INVALID_ARG, "mrh_estimate_normals_device: null argument");
+  NrmPar par;
+  rc = normals_args(c, "mrh_estimate_normals_device", p, n, &par);
+  if (rc || n == 0) return rc;
+  const u64* ctr;
+  return launch_normals(c, par, d_xyz, n, d_nxyz, &ctr);
+}
+
+int mrh_estimate_normals(mrh_ctx* c, const mrh_normals_params* p, mrh_normals_info* out_info) {
+  int rc = ensure_device(c, "mrh_estimate_normals");
+  if (rc) return rc;
+  auto& L = c->lidar;
+  auto& N = c->nrm;
+  if (!L.have_cloud) return fail(c, MRH_ERR_STATE, "mrh_estimate_normals: no current scan (mrh_upload_points / mrh_set_points_device)");
+  const uint64_t n = L.num_points;
+  NrmPar par;
+  rc = normals_args(c, "mrh_estimate_normals", p, n, &par);
+  if (rc) return rc;
+  if (!N.h_ctr) {
+    HIP_TRY(c, hipHostMalloc((void**) &N.h_ctr, NC_N * sizeof(u64), hipHostMallocDefault));
+    memset(N.h_ctr, 0, NC_N * sizeof(u64));
+  }
+  L.num_normals = 0;  // none valid from the moment the buffer may change
+  rc = regrow(c, L.d_normals, L.normals_cap, (size_t) n, (size_t) n * 3 * sizeof(float));
+  if (rc) return rc;
+  N.info = {};
+  N.info.points = n;
+  N.info_pending = false;
+  if (n) {
+    const u64* ctr;
+    rc = launch_normals(c, par, L.d_points_cur, n, L.d_normals, &ctr);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(N.h_ctr, ctr, NC_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    N.info_pending = true;
+  }
+  L.num_normals = n;
+  if (out_info) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    normals_fold_info(c);
+    *out_info = N.info;
+  }
+  return MRH_OK;
+}
+
+int mrh_get_normals(mrh_ctx* c, const float** out_nxyz, uint64_t* out_n, mrh_normals_info* out_info) {
+  const int rc = ensure_device(c, "mrh_get_normals");
+  if (rc) return rc;
+  if (!out_nxyz || !out_n) return fail(c, MRH_ERR_INVALID_ARG, "mrh_get_normals: null argument");
+  auto& L = c->lidar;
+  auto& N = c->nrm;
+  const size_t n = L.num_normals;
+  if (n > N.h_out_cap) {
+    if (N.h_out) { (void) hipHostFree(N.h_out); N.h_out = nullptr; N.h_out_cap = 0; }
+    HIP_TRY(c, hipHostMalloc((void**) &N.h_out, n * 3 * sizeof(float), hipHostMallocDefault));
+    N.h_out_cap = n;
+  }
+  if (n) HIP_TRY(c, hipMemcpyAsync(N.h_out, L.d_normals, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  normals_fold_info(c);
+  *out_nxyz = N.h_out;
+  *out_n = n;
+  if (out_info) *out_info = N.info;
   return MRH_OK;
 }
 

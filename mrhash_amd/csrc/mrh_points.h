@@ -83,6 +83,7 @@ int mrh_upload_points(mrh_ctx* c, const float* xyz, uint64_t n) {
   rc = upload_xyz(c, xyz, n, L.d_points, L.points_cap, L.num_points);
   if (rc) return rc;
   L.d_points_cur = L.d_points;
+  L.have_cloud = true;
   if (L.layout_hint > 0) L.row_len = L.layout_hint;
   else if (L.layout_hint == 0 && n) {
     if (n != L.detect_n || ++L.detect_age >= 64) {
@@ -100,12 +101,14 @@ int mrh_set_points_device(mrh_ctx* c, const float* d_xyz, uint64_t n) {
   if (rc) return rc;
   c->lidar.d_points_cur = d_xyz;
   c->lidar.num_points = n;
+  c->lidar.have_cloud = true;
   c->lidar.row_len = c->lidar.layout_hint > 0 ? c->lidar.layout_hint : 0;  // a cloud in device memory is not looked at: mrh_set_scan_layout says how it is laid out
   return MRH_OK;
 }
 
 int mrh_upload_normals(mrh_ctx* c, const float* nxyz, uint64_t n) {
   const int rc = cloud_checks(c, "mrh_upload_normals", nxyz, n);
+  if (!rc) { c->nrm.info = {}; c->nrm.info_pending = false; }  // these normals were not estimated here (mrh_get_normals)
   return rc ? rc : upload_xyz(c, nxyz, n, c->lidar.d_normals, c->lidar.normals_cap, c->lidar.num_normals);
 }
 

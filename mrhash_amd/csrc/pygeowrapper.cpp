@@ -84,14 +84,13 @@ PYBIND11_MODULE(pygeowrapper, m) {
       // geowrapper.cpp:345-405: [N, 3] points in the sensor frame (the runners pass points[:, :3]); copied
       if (pts.ndim() != 2) throw std::runtime_error("GeoWrapper::setPointCloud|input should be a 2D numpy array");
       if (pts.shape(1) < 3) throw std::runtime_error("GeoWrapper::setPointCloud|input should have at least 3 columns (x, y, z)");
-      if (compute_normals) throw std::runtime_error("GeoWrapper::setPointCloud|normal estimation (MAD tree) is outside this library's scope");
       if (pts.shape(1) == 3) {
-        g.setPointCloud(pts.data(), (size_t) pts.shape(0), nullptr);
+        g.setPointCloud(pts.data(), (size_t) pts.shape(0), nullptr, compute_normals);
       } else {
         std::vector<float> xyz((size_t) pts.shape(0) * 3);
         auto r = pts.unchecked<2>();
         for (py::ssize_t i = 0; i < pts.shape(0); i++) { xyz[3 * i] = r(i, 0); xyz[3 * i + 1] = r(i, 1); xyz[3 * i + 2] = r(i, 2); }
-        g.setPointCloud(xyz.data(), (size_t) pts.shape(0), nullptr);
+        g.setPointCloud(xyz.data(), (size_t) pts.shape(0), nullptr, compute_normals);
       }
     }, py::arg("input_point_cloud"), py::arg("compute_normals") = false)
     .def("setPointCloud", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> pts,

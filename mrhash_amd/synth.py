@@ -244,7 +244,7 @@ def lidar_scan(scene: Scene, t: np.ndarray, q: np.ndarray, rows: int = 32, cols:
 def scan_normals(pts: np.ndarray) -> np.ndarray:
     """A normal per point of a scan, oriented towards the sensor (what the reference's MAD-tree hands out,
     geowrapper.cpp:386-388): here simply the reversed beam direction tilted by a fixed, point-dependent amount — a
-    deterministic stand-in, not an estimator (estimating normals is the caller's business, include/mrhash_hip.h)."""
+    deterministic stand-in, not an estimator (the library's estimator is mrh_estimate_normals, include/mrhash_normals.h)."""
     p = pts.astype(np.float64)
     r = np.linalg.norm(p, axis=1, keepdims=True)
     n = -p / np.maximum(r, 1e-9)
