@@ -20,6 +20,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <tuple>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -321,13 +322,13 @@ struct mrh_ctx {
     size_t buckets_lds_set = 0;
   } lidar;
   // 3DGS splat seeds (mrh_splat.h): sized for one (image shape, min pixel size)
-  QTree qt = {0, 0, 0, 0, 0};
+  size_t qt_cap = 0;  // potential nodes the device buffers below hold (regrow_all); it replaces the QTree once recorded here
   QSum* d_qt_sums = nullptr; u32* d_qt_flags = nullptr; u32* d_qt_unc = nullptr; u64* d_qt_marks = nullptr; u64* d_qt_pos = nullptr;
   mrh_splat_seed* d_qt_parked = nullptr; mrh_qtree_leaf* d_qt_leaves = nullptr;
   // what the caller takes from a seeding call is written by its last launch straight into pinned host memory (a few hundred to a few
   // thousand 20-byte seeds and two counters): one synchronisation, no transfer calls (they were two pageable read-backs, each behind
   // a synchronisation of its own: ~35 of the call's 135 us)
-  mrh_splat_seed* h_qt_seeds = nullptr; u32 qt_seed_cap = 0;
+  mrh_splat_seed* h_qt_seeds = nullptr; size_t qt_seed_cap = 0;
   u64* h_qt_out = nullptr;   // [0] totals (leaves | seeds << 32), [1] literal evaluations
   u64* d_qt_misc = nullptr;  // [0] totals (leaves | seeds << 32), [1] uncertain-node counter (low word)
   int qt_literal = 0;        // MRH_QTREE_LITERAL=1: every node error through the reference's summation order (cross-check)
@@ -510,6 +511,29 @@ int regrow_all(mrh_ctx* c, size_t& cap, const size_t cap_new, std::initializer_l
 template <typename T>
 int regrow(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes, const bool sync = true) {
   return cap_new <= cap ? MRH_OK : regrow_all(c, cap, cap_new, {{p, bytes}}, sync);
+}
+// ... whose first `keep_bytes` ARE kept (halo list, merge accumulator, exchange buffers): the new buffer first, the copy on the
+// context's stream, the old one released behind the drained stream; any step that fails leaves buffer and capacity as they were
+template <typename T>
+int regrow_keep(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes_new, const size_t keep_bytes) {
+  if (cap_new <= cap) return MRH_OK;
+  DevBuf<T> grown;  // released on an error return
+  HIP_TRY(c, hipMalloc((void**) &grown.p, bytes_new));
+  if (p && keep_bytes) HIP_TRY(c, hipMemcpyAsync(grown.p, p, keep_bytes, hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::swap(p, grown.p);  // the old buffer goes with `grown`
+  cap = cap_new;
+  return MRH_OK;
+}
+// ... and a pinned host buffer the caller reads results from (the call that filled it blocked: no synchronisation), contents not kept
+template <typename T>
+int regrow_pinned(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes) {
+  if (cap_new <= cap) return MRH_OK;
+  cap = 0;
+  if (p) { (void) hipHostFree(p); p = nullptr; }
+  HIP_TRY(c, hipHostMalloc((void**) &p, bytes, hipHostMallocDefault));
+  cap = cap_new;
+  return MRH_OK;
 }
 
 uint64_t next_pow2(uint64_t v) {
@@ -1587,6 +1611,39 @@ int send_uploads(mrh_ctx* c, hipStream_t reader) {
   return MRH_OK;
 }
 
+// ---- the non-blocking peeks (mrh_peek_free_blocks, mrh_peek_error_flags): h_peek, eight reports, one per frame mark ----
+// the first peek of a context: reports start with the next frame
+int enable_peeks(mrh_ctx* c) {
+  if (c->peek_enabled) return MRH_OK;
+  HIP_TRY(c, hipHostMalloc((void**) &c->h_peek, 64 * sizeof(int), hipHostMallocDefault));
+  memset(c->h_peek, 0, 64 * sizeof(int));
+  c->peek_enabled = true;
+  return MRH_OK;
+}
+// the newest of the last eight marks whose report has landed: 1 and {*seq, *back: marks behind the newest, 1 = none}, 0 if none has, or an error
+int newest_report(mrh_ctx* c, const char* who, uint64_t* seq_out, uint64_t* back_out) {
+  for (uint64_t back = 1; back <= 8 && back < c->frame_seq; back++) {
+    const uint64_t seq = c->frame_seq - back;
+    if (c->peek_seq[seq % 8] != seq) continue;
+    const hipError_t q = hipEventQuery(c->peek_done[seq % 8]);
+    if (q == hipErrorNotReady) continue;
+    if (q != hipSuccess) return fail(c, MRH_ERR_DEVICE, "%s: %s", who, hipGetErrorString(q));
+    if (c->peek_seq[seq % 8] != seq) continue;
+    *seq_out = seq; *back_out = back;
+    return 1;
+  }
+  return 0;
+}
+// the pool report of mark `seq` (ctr[0 .. 4]: free-list levels ... error flags) into its slot of h_peek, behind whatever is on
+// `s`; from here on the mark exists for the peeks (newest_report).  A mark that is posted again refreshes its report.
+int post_report(mrh_ctx* c, const uint64_t seq, hipStream_t s) {
+  k_report<<<1, 64, 0, s>>>(&c->tab.ctr[CTR_HEAP_FINE], c->h_peek + 8 * (seq % 8));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipEventRecord(c->peek_done[seq % 8], s));
+  c->peek_seq[seq % 8] = seq;
+  return MRH_OK;
+}
+
 // after the kernels of a frame (or of a seeding call) are enqueued: mark the ring slots they read, report the pool level
 int mark_frame(mrh_ctx* c) {
   UpSlot* used[2] = {nullptr, nullptr};
@@ -1606,11 +1663,8 @@ int mark_frame(mrh_ctx* c) {
       // sit behind the integration of an EARLIER frame only, and an event on the front stream says nothing about it at all.
       c->peek_seq[seq % 8] = 0;
       c->pendq[c->npend - 1].report_seq = seq;
-    } else {
-      k_report<<<1, 64, 0, c->stream>>>(&c->tab.ctr[CTR_HEAP_FINE], c->h_peek + 8 * (seq % 8));  // ctr[0 .. 4]
-      HIP_TRY(c, hipGetLastError());
-      HIP_TRY(c, hipEventRecord(c->peek_done[seq % 8], c->stream));
-      c->peek_seq[seq % 8] = seq;
+    } else if (const int rc = post_report(c, seq, c->stream)) {
+      return rc;
     }
   }
   if (used[0] || used[1]) {
@@ -1618,6 +1672,64 @@ int mark_frame(mrh_ctx* c) {
     HIP_TRY(c, hipEventRecord(c->frame_done[seq % 8], lazy ? c->stream_front : c->stream));
     for (UpSlot* u : used) if (u) u->last_seq = seq;
   }
+  return MRH_OK;
+}
+
+// ---- 3DGS splat seeds: GaussianContainer::extractNodesQTree + checkNodes (gaussian_data_structures.cpp:48-68, .cu:58-84), see mrh_splat.h
+int seeds_checks(mrh_ctx* c, const float qtree_thresh, const int qtree_min_pixel_size, const mrh_splat_seed** out, uint64_t* out_n) {
+  if (!out || !out_n) return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: null argument");
+  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_splat_seeds: an exchange is pending (call mrh_integrate_resume)");
+  if (!c->has_camera) return fail(c, MRH_ERR_STATE, "mrh_splat_seeds: set_camera has not been called");
+  if (c->spherical) return fail(c, MRH_ERR_UNSUPPORTED, "mrh_splat_seeds: pinhole camera only");
+  if (qtree_min_pixel_size < 0 || qtree_thresh != qtree_thresh) return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: bad quad-tree parameter");
+  if (!c->d_depth || !c->d_rgb) return fail(c, MRH_ERR_STATE, "mrh_splat_seeds: no depth / colour image");
+  const Cam& k = c->cam;
+  if (c->depth_rows != k.rows || c->depth_cols != k.cols || c->rgb_rows != k.rows || c->rgb_cols != k.cols)
+    return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: image shape differs from the camera");
+  if ((uint64_t) k.rows * (uint64_t) k.cols > (1ull << 22)) return fail(c, MRH_ERR_CAPACITY, "mrh_splat_seeds: image above 2^22 pixels");
+  return MRH_OK;
+}
+// The buffers of a tree of qt.total potential nodes.  The seven device buffers sized by the node count and d_qt_misc are one
+// regrow_all under qt_cap, reallocated whenever the count differs, not only when it grows.  A failed allocation leaves no device
+// buffer and capacity 0, so the next call allocates again whatever its image shape; the last call's leaves go with d_qt_leaves.
+// The pinned seeds only grow (regrow_pinned; they used to shrink with the tree): k_qt_scatter is told their capacity.
+int qtree_buffers(mrh_ctx* c, const QTree& qt) {
+  const size_t n = qt.total, seeds = std::min<size_t>(n, (size_t) 1 << 20);  // seeds <= leaves <= 1 000 000 (mrh_splat_seeds checks)
+  int rc = MRH_OK;
+  if (n != c->qt_cap) {
+    c->qt_n_leaves = 0;
+    c->qt_leaves_on_host = true;
+    c->qt_leaves.clear();
+    rc = regrow_all(c, c->qt_cap, n, {{c->d_qt_sums, n * sizeof(QSum)}, {c->d_qt_flags, n * sizeof(u32)}, {c->d_qt_unc, n * sizeof(u32)}, {c->d_qt_marks, n * sizeof(u64)},
+                                      {c->d_qt_pos, (n + (n + kChainTile - 1) / kChainTile + 1) * sizeof(u64)},  // + the tile sums of the marks' scan
+                                      {c->d_qt_parked, n * sizeof(mrh_splat_seed)}, {c->d_qt_leaves, n * sizeof(mrh_qtree_leaf)}, {c->d_qt_misc, 2 * sizeof(u64)}});
+  }
+  if (!rc) rc = regrow_pinned(c, c->h_qt_seeds, c->qt_seed_cap, seeds, seeds * sizeof(mrh_splat_seed));
+  if (rc) return rc;
+  if (!c->h_qt_out) HIP_TRY(c, hipHostMalloc((void**) &c->h_qt_out, 2 * sizeof(u64), hipHostMallocDefault));
+  return MRH_OK;
+}
+int launch_qtree(mrh_ctx* c, const QTree& qt, const float qtree_thresh) {
+  hipStream_t s = c->stream;
+  const u32 grid = (qt.total + 255) / 256;
+  u32* unc_count = (u32*) (c->d_qt_misc + 1);
+  // exact statistics of every potential node, four tree levels per launch
+  int L = qt.D, T = L < 4 ? L : 4;
+  k_qt_sums_bottom<<<1u << (2 * (L - T)), 256, 0, s>>>(qt, c->d_rgb, c->d_qt_sums, T, c->d_qt_misc);
+  for (L -= T; L > 0; L -= T) {
+    T = L < 4 ? L : 4;
+    k_qt_sums_up<<<1u << (2 * (L - T)), 256, 0, s>>>(qt, c->d_qt_sums, L, T);
+  }
+  // exclusive scan of the marks (mrh_sort.h): the tile sums (parked behind the positions) are cleared by k_qt_decide and added up by
+  // k_qt_emit's workgroups, then every tile scans on its own
+  const u32 tiles = (u32) ((qt.total + kChainTile - 1) / kChainTile);
+  static_assert(kChainTile % 256 == 0, "a workgroup of k_qt_emit lies inside one scan tile");
+  k_qt_decide<<<grid, 256, 0, s>>>(qt, qtree_thresh, c->d_qt_sums, c->qt_literal, c->d_qt_flags, c->d_qt_unc, unc_count, c->d_qt_pos + qt.total, tiles);
+  k_qt_literal<<<512, 256, 0, s>>>(qt, c->d_rgb, qtree_thresh, c->d_qt_unc, unc_count, c->d_qt_flags);
+  k_qt_emit<<<grid, 256, 0, s>>>(qt, c->cam, c->map, c->tab, c->d_depth, c->d_rgb, c->d_qt_flags, c->d_qt_marks, c->d_qt_parked, c->d_qt_pos + qt.total);
+  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(c->d_qt_marks, (u32) qt.total, c->d_qt_pos + qt.total, c->d_qt_pos);
+  k_qt_scatter<<<grid, 256, 0, s>>>(qt, c->d_qt_marks, c->d_qt_pos, c->d_qt_parked, c->d_qt_leaves, c->h_qt_seeds, (u32) c->qt_seed_cap, c->d_qt_misc, c->h_qt_out);
+  HIP_TRY(c, hipGetLastError());
   return MRH_OK;
 }
 
@@ -1860,13 +1972,9 @@ int launch_pending(mrh_ctx* c, const bool count_skips = false) {
     if (src) return src;
     c->zombies_possible = true;
   }
-  if (pb.report_seq && c->peek_enabled) {  // the frame's pool report (mark_frame left it to this launch): behind its integration
-    k_report<<<1, 64, 0, s>>>(&c->tab.ctr[CTR_HEAP_FINE], c->h_peek + 8 * (pb.report_seq % 8));
-    HIP_TRY(c, hipEventRecord(c->peek_done[pb.report_seq % 8], s));
-    c->peek_seq[pb.report_seq % 8] = pb.report_seq;  // from here on the mark exists for the peeks
-  }
   HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
+  // the frame's pool report (mark_frame left it to this launch): behind its integration
+  return pb.report_seq && c->peek_enabled ? post_report(c, pb.report_seq, s) : MRH_OK;
 }
 
 // Behind the pipelined frames issued so far (their integrations are all on the main stream, each behind its front half), the
@@ -1886,8 +1994,7 @@ int strict_point(mrh_ctx* c) {
   if (c->peek_enabled && c->frame_seq > 1) {
     const uint64_t seq = c->frame_seq - 1;
     if (c->peek_seq[seq % 8] == seq && c->peek_done[seq % 8]) {
-      k_report<<<1, 64, 0, c->stream>>>(&c->tab.ctr[CTR_HEAP_FINE], c->h_peek + 8 * (seq % 8));
-      HIP_TRY(c, hipEventRecord(c->peek_done[seq % 8], c->stream));
+      if (const int rc = post_report(c, seq, c->stream)) return rc;
     }
   }
   c->zombies_possible = false;
@@ -2308,70 +2415,20 @@ int mrh_sync(mrh_ctx* c) {
   return check_device_flags(c, flags);
 }
 
-// GaussianContainer::extractNodesQTree + checkNodes (gaussian_data_structures.cpp:48-68, .cu:58-84), see mrh_splat.h
 int mrh_splat_seeds(mrh_ctx* c, float qtree_thresh, int qtree_min_pixel_size, const mrh_splat_seed** out, uint64_t* out_n) {
   int rc = ensure_ready(c, "mrh_splat_seeds");
   if (rc) return rc;
-  if (!out || !out_n) return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: null argument");
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_splat_seeds: an exchange is pending (call mrh_integrate_resume)");
-  if (!c->has_camera) return fail(c, MRH_ERR_STATE, "mrh_splat_seeds: set_camera has not been called");
-  if (c->spherical) return fail(c, MRH_ERR_UNSUPPORTED, "mrh_splat_seeds: pinhole camera only");
-  if (qtree_min_pixel_size < 0 || qtree_thresh != qtree_thresh) return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: bad quad-tree parameter");
-  if (!c->d_depth || !c->d_rgb) return fail(c, MRH_ERR_STATE, "mrh_splat_seeds: no depth / colour image");
-  const Cam& k = c->cam;
-  if (c->depth_rows != k.rows || c->depth_cols != k.cols || c->rgb_rows != k.rows || c->rgb_cols != k.cols)
-    return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: image shape differs from the camera");
-  if ((uint64_t) k.rows * (uint64_t) k.cols > (1ull << 22)) return fail(c, MRH_ERR_CAPACITY, "mrh_splat_seeds: image above 2^22 pixels");
-  hipStream_t s = c->stream;
-  // depth of the potential tree: the first level whose largest rectangle (the bottom-right chain of ceil halves) can
-  // no longer split (quad_tree.cu:133-149)
-  QTree qt = {k.cols, k.rows, 0, qtree_min_pixel_size, 0};
-  for (int w = k.cols, h = k.rows; qt.D < kQtMaxDepth && !(w / 2 <= qt.min_px || h / 2 <= qt.min_px); qt.D++) { w -= w / 2; h -= h / 2; }
+  if ((rc = seeds_checks(c, qtree_thresh, qtree_min_pixel_size, out, out_n))) return rc;
+  // depth of the potential tree: the first level whose largest rectangle (the bottom-right chain of ceil halves) can no longer
+  // split (quad_tree.cu:133-149)
+  QTree qt = {c->cam.cols, c->cam.rows, 0, qtree_min_pixel_size, 0};
+  for (int w = qt.W, h = qt.H; qt.D < kQtMaxDepth && !(w / 2 <= qt.min_px || h / 2 <= qt.min_px); qt.D++) { w -= w / 2; h -= h / 2; }
   qt.total = qt_level_offset(qt.D + 1);
-  if (qt.total != c->qt.total || !c->d_qt_sums) {
-    HIP_TRY(c, hipStreamSynchronize(s));
-    auto F = [](auto*& p) { if (p) (void) hipFree(p); p = nullptr; };
-    // only the quad-tree buffers are sized by qt.total: nothing else of the context is released here
-    F(c->d_qt_sums); F(c->d_qt_flags); F(c->d_qt_unc); F(c->d_qt_marks); F(c->d_qt_pos); F(c->d_qt_parked); F(c->d_qt_leaves); F(c->d_qt_misc);
-    if (c->h_qt_seeds) { (void) hipHostFree(c->h_qt_seeds); c->h_qt_seeds = nullptr; }
-    const size_t n = qt.total;
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_sums, n * sizeof(QSum)));
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_flags, n * sizeof(u32)));
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_unc, n * sizeof(u32)));
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_marks, n * sizeof(u64)));
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_pos, (n + (n + kChainTile - 1) / kChainTile + 1) * sizeof(u64)));  // + the tile sums of the marks' scan
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_parked, n * sizeof(mrh_splat_seed)));
-    c->qt_seed_cap = (u32) std::min<size_t>(n, (size_t) 1 << 20);  // seeds <= leaves <= 1 000 000 (checked below), or the call fails
-    HIP_TRY(c, hipHostMalloc((void**) &c->h_qt_seeds, (size_t) c->qt_seed_cap * sizeof(mrh_splat_seed), hipHostMallocDefault));
-    if (!c->h_qt_out) HIP_TRY(c, hipHostMalloc((void**) &c->h_qt_out, 2 * sizeof(u64), hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_leaves, n * sizeof(mrh_qtree_leaf)));
-    HIP_TRY(c, hipMalloc((void**) &c->d_qt_misc, 2 * sizeof(u64)));
-  }
-  c->qt = qt;
-  rc = send_uploads(c, c->stream);
-  if (rc) return rc;
-  const u32 grid = (qt.total + 255) / 256;
-  u32* unc_count = (u32*) (c->d_qt_misc + 1);
-  // exact statistics of every potential node, four tree levels per launch
-  int L = qt.D, T = L < 4 ? L : 4;
-  k_qt_sums_bottom<<<1u << (2 * (L - T)), 256, 0, s>>>(qt, c->d_rgb, c->d_qt_sums, T, c->d_qt_misc);
-  for (L -= T; L > 0; L -= T) {
-    T = L < 4 ? L : 4;
-    k_qt_sums_up<<<1u << (2 * (L - T)), 256, 0, s>>>(qt, c->d_qt_sums, L, T);
-  }
-  // exclusive scan of the marks (mrh_sort.h): the tile sums (parked behind the positions) are cleared by k_qt_decide and added up by
-  // k_qt_emit's workgroups, then every tile scans on its own
-  const u32 tiles = (u32) ((qt.total + kChainTile - 1) / kChainTile);
-  static_assert(kChainTile % 256 == 0, "a workgroup of k_qt_emit lies inside one scan tile");
-  k_qt_decide<<<grid, 256, 0, s>>>(qt, qtree_thresh, c->d_qt_sums, c->qt_literal, c->d_qt_flags, c->d_qt_unc, unc_count, c->d_qt_pos + qt.total, tiles);
-  k_qt_literal<<<512, 256, 0, s>>>(qt, c->d_rgb, qtree_thresh, c->d_qt_unc, unc_count, c->d_qt_flags);
-  k_qt_emit<<<grid, 256, 0, s>>>(qt, c->cam, c->map, c->tab, c->d_depth, c->d_rgb, c->d_qt_flags, c->d_qt_marks, c->d_qt_parked, c->d_qt_pos + qt.total);
-  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(c->d_qt_marks, (u32) qt.total, c->d_qt_pos + qt.total, c->d_qt_pos);
-  k_qt_scatter<<<grid, 256, 0, s>>>(qt, c->d_qt_marks, c->d_qt_pos, c->d_qt_parked, c->d_qt_leaves, c->h_qt_seeds, c->qt_seed_cap, c->d_qt_misc, c->h_qt_out);
-  HIP_TRY(c, hipGetLastError());
-  rc = mark_frame(c);
-  if (rc) return rc;
-  HIP_TRY(c, hipStreamSynchronize(s));
+  if ((rc = qtree_buffers(c, qt))) return rc;
+  if ((rc = send_uploads(c, c->stream))) return rc;
+  if ((rc = launch_qtree(c, qt, qtree_thresh))) return rc;
+  if ((rc = mark_frame(c))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote totals and seeds into pinned memory
   const u64 h_misc[2] = {((volatile u64*) c->h_qt_out)[0], ((volatile u64*) c->h_qt_out)[1]};
   const uint64_t n_leaves = h_misc[0] & 0xFFFFFFFFull, n_seeds = h_misc[0] >> 32;
   c->qt_last_literal = (uint32_t) h_misc[1];
@@ -2384,8 +2441,8 @@ int mrh_splat_seeds(mrh_ctx* c, float qtree_thresh, int qtree_min_pixel_size, co
     fprintf(stderr, "[mrh] splat seeds: %u potential nodes, %u literal evaluations, %llu leaves, %llu seeds\n", qt.total,
             c->qt_last_literal, (unsigned long long) n_leaves, (unsigned long long) n_seeds);
   }
-  *out = c->h_qt_seeds;
   *out_n = n_seeds;
+  *out = c->h_qt_seeds;
   return MRH_OK;
 }
 
@@ -2416,18 +2473,10 @@ int mrh_get_free_blocks(mrh_ctx* c, int64_t* out_free_fine, int64_t* out_free_co
 int mrh_peek_free_blocks(mrh_ctx* c, int64_t* out_free_fine, int64_t* out_free_coarse, uint64_t* out_frames_behind) {
   int rc = ensure_device(c, "mrh_peek_free_blocks");
   if (rc) return rc;
-  if (!c->peek_enabled) {  // first call: reports start with the next frame; answer this one the blocking way
-    HIP_TRY(c, hipHostMalloc((void**) &c->h_peek, 64 * sizeof(int), hipHostMallocDefault));
-    memset(c->h_peek, 0, 64 * sizeof(int));
-    c->peek_enabled = true;
-  }
-  for (uint64_t back = 1; back <= 8 && back < c->frame_seq; back++) {
-    const uint64_t seq = c->frame_seq - back;
-    if (c->peek_seq[seq % 8] != seq) continue;
-    const hipError_t q = hipEventQuery(c->peek_done[seq % 8]);
-    if (q == hipErrorNotReady) continue;
-    if (q != hipSuccess) return fail(c, MRH_ERR_DEVICE, "mrh_peek_free_blocks: %s", hipGetErrorString(q));
-    if (c->peek_seq[seq % 8] != seq) continue;
+  if ((rc = enable_peeks(c))) return rc;  // a first call finds no report below: answered the blocking way
+  uint64_t seq = 0, back = 0;
+  if ((rc = newest_report(c, "mrh_peek_free_blocks", &seq, &back)) < 0) return rc;
+  if (rc) {
     if (out_free_fine) *out_free_fine = (int64_t) c->h_peek[8 * (seq % 8)] + 1;
     if (out_free_coarse) *out_free_coarse = (int64_t) c->h_peek[8 * (seq % 8) + 1] + 1;
     // a host-fed frame that mrh_integrate has kept back (flush_deferred) has no sequence number yet: it counts as one more frame behind
@@ -2443,24 +2492,13 @@ int mrh_peek_error_flags(mrh_ctx* c, uint32_t* out_new_flags) {
   if (rc) return rc;
   if (!out_new_flags) return MRH_ERR_INVALID_ARG;
   *out_new_flags = 0;
-  if (!c->peek_enabled) {  // reports start with the next frame
-    HIP_TRY(c, hipHostMalloc((void**) &c->h_peek, 64 * sizeof(int), hipHostMallocDefault));
-    memset(c->h_peek, 0, 64 * sizeof(int));
-    c->peek_enabled = true;
-    return MRH_OK;
-  }
-  for (uint64_t back = 1; back <= 8 && back < c->frame_seq; back++) {
-    const uint64_t seq = c->frame_seq - back;
-    if (c->peek_seq[seq % 8] != seq) continue;
-    const hipError_t q = hipEventQuery(c->peek_done[seq % 8]);
-    if (q == hipErrorNotReady) continue;
-    if (q != hipSuccess) return fail(c, MRH_ERR_DEVICE, "mrh_peek_error_flags: %s", hipGetErrorString(q));
-    const u32 flags = (u32) c->h_peek[8 * (seq % 8) + CTR_ERROR];
-    *out_new_flags = flags & ~c->flags_peeked;
-    if (*out_new_flags & ERR_POOL) c->table_dirty = true;  // as in take_device_flags: drop the keys without storage before the next frame
-    c->flags_peeked = flags;  // the device clears its flags only in mrh_sync: what is set now has been reported
-    return MRH_OK;
-  }
+  if (!c->peek_enabled) return enable_peeks(c);
+  uint64_t seq = 0, back = 0;
+  if ((rc = newest_report(c, "mrh_peek_error_flags", &seq, &back)) <= 0) return rc;
+  const u32 flags = (u32) c->h_peek[8 * (seq % 8) + CTR_ERROR];
+  *out_new_flags = flags & ~c->flags_peeked;
+  if (*out_new_flags & ERR_POOL) c->table_dirty = true;  // as in take_device_flags: drop the keys without storage before the next frame
+  c->flags_peeked = flags;  // the device clears its flags only in mrh_sync: what is set now has been reported
   return MRH_OK;
 }
 
@@ -2528,366 +2566,11 @@ int mrh_get_stats(mrh_ctx* c, mrh_stats* out) {
   return MRH_OK;
 }
 
-// Streamer, device half (streamer.cu:11-160): select by distance from the camera, copy out, free.
-int mrh_stream_out(mrh_ctx* c, const float center[3], float radius, mrh_block_desc* descs, mrh_voxel* voxels, uint64_t capacity,
-                   uint64_t* out_n) {
-  int rc = ensure_ready(c, "mrh_stream_out");
-  if (rc) return rc;
-  if (!out_n || !center) return MRH_ERR_INVALID_ARG;
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_stream_out: an exchange is pending (call mrh_integrate_resume)");
-  c->refill_flag_valid = false;  // freed coarse units change the level the next frame's refill test must see
-  int n = 0;
-  rc = compact_all(c, &n);
-  if (rc) return rc;
-  *out_n = 0;
-  if (n == 0) return MRH_OK;
-  // the selection is a handful of flops per live block: done on the host copy of the list, which is needed for the
-  // canonical (position) order anyway
-  std::vector<int4> list((size_t) n);
-  HIP_TRY(c, hipMemcpy(list.data(), c->tab.compact, (size_t) n * sizeof(int4), hipMemcpyDeviceToHost));
-  const float vs = c->map.vs;
-  std::vector<int4> sel;
-  sel.reserve((size_t) n);
-  for (const int4& e : list) {
-    const float px = (float) (e.x * kBlockSide) * vs, py = (float) (e.y * kBlockSide) * vs, pz = (float) (e.z * kBlockSide) * vs;
-    const float dx = px - center[0], dy = py - center[1], dz = pz - center[2];
-    const float d = sqrtf((dx * dx + dy * dy) + dz * dz);
-    if (radius >= 0.f && !(d >= radius)) continue;
-    sel.push_back(e);
-  }
-  *out_n = sel.size();
-  if (!descs || sel.empty()) return MRH_OK;
-  if (sel.size() > capacity) return fail(c, MRH_ERR_CAPACITY, "mrh_stream_out: capacity %llu < %zu blocks to stream out", (unsigned long long) capacity, sel.size());
-  std::sort(sel.begin(), sel.end(), [](const int4& a, const int4& b) {
-    if (a.x != b.x) return a.x < b.x;
-    if (a.y != b.y) return a.y < b.y;
-    return a.z < b.z;
-  });
-  const int ns = (int) sel.size();
-  HIP_TRY(c, hipMemcpy(c->tab.compact, sel.data(), (size_t) ns * sizeof(int4), hipMemcpyHostToDevice));
-  const int chunk = 8192;
-  DevBuf<int4> d_descs;
-  DevBuf<char> d_vox;
-  HIP_TRY(c, d_descs.alloc((size_t) chunk));
-  HIP_TRY(c, d_vox.alloc((size_t) chunk * kFineBytes));
-  for (int first = 0; first < ns; first += chunk) {
-    const int cnt = (ns - first) < chunk ? (ns - first) : chunk;
-    k_dump<<<cnt < 2048 ? cnt : 2048, 512, 0, c->stream>>>(c->tab, first, cnt, d_descs, d_vox);
-    HIP_TRY(c, hipMemcpyAsync(&descs[first], d_descs, (size_t) cnt * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
-    if (voxels) HIP_TRY(c, hipMemcpyAsync(&voxels[(size_t) first * 512], d_vox, (size_t) cnt * kFineBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  // free: garbageCollectFree's kernel over the selected list with every decision set
-  const int ctr_n = ns;
-  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], &ctr_n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  k_fill_u32<<<256, 256, 0, c->stream>>>(c->d_decision, (size_t) ns, 1u);
-  k_gc_free<false><<<256, 256, 0, c->stream>>>(c->tab, c->d_decision);
-  c->table_dirty = true;  // a bulk erase: census (and, if due, rebuild) before the next frame
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
+}  // extern "C"
 
-int mrh_dump_blocks(mrh_ctx* c, mrh_block_desc* descs, mrh_voxel* voxels, uint64_t capacity, uint64_t* out_n) {
-  int rc = ensure_ready(c, "mrh_dump_blocks");
-  if (rc) return rc;
-  if (!out_n) return MRH_ERR_INVALID_ARG;
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_dump_blocks: an exchange is pending (call mrh_integrate_resume)");  // the starve passes still need Tab::compact
-  int n = 0;
-  rc = compact_all(c, &n);
-  if (rc) return rc;
-  *out_n = (uint64_t) n;
-  if (!descs) return MRH_OK;
-  if ((uint64_t) n > capacity) return fail(c, MRH_ERR_CAPACITY, "mrh_dump_blocks: capacity %llu < %d live blocks", (unsigned long long) capacity, n);
-  const int chunk = 8192;  // 48 MiB of voxels per round trip
-  DevBuf<int4> d_descs;
-  DevBuf<char> d_vox;
-  HIP_TRY(c, d_descs.alloc((size_t) chunk));
-  HIP_TRY(c, d_vox.alloc((size_t) chunk * kFineBytes));
-  for (int first = 0; first < n; first += chunk) {
-    const int cnt = (n - first) < chunk ? (n - first) : chunk;
-    k_dump<<<cnt < 2048 ? cnt : 2048, 512, 0, c->stream>>>(c->tab, first, cnt, d_descs, d_vox);
-    HIP_TRY(c, hipMemcpyAsync(&descs[first], d_descs, (size_t) cnt * sizeof(int4), hipMemcpyDeviceToHost, c->stream));
-    if (voxels) HIP_TRY(c, hipMemcpyAsync(&voxels[(size_t) first * 512], d_vox, (size_t) cnt * kFineBytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
+#include "mrh_blocks.h"
 
-int mrh_get_voxel(mrh_ctx* c, int32_t vx, int32_t vy, int32_t vz, mrh_voxel* out, int* out_found) {
-  int rc = ensure_ready(c, "mrh_get_voxel");
-  if (rc) return rc;
-  if (!out) return MRH_ERR_INVALID_ARG;
-  k_get_voxel<<<1, 1, 0, c->stream>>>(c->map, c->tab, vx, vy, vz, c->d_misc);
-  u32 h[4];
-  HIP_TRY(c, hipMemcpyAsync(h, c->d_misc, sizeof h, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(&out->sdf, &h[0], 4);
-  memcpy(&out->sum_squared, &h[1], 4);
-  out->rgb[0] = h[2] & 0xFF; out->rgb[1] = (h[2] >> 8) & 0xFF; out->rgb[2] = (h[2] >> 16) & 0xFF;
-  out->weight = (uint8_t) (h[2] >> 24);
-  if (out_found) *out_found = (int) h[3];
-  return MRH_OK;
-}
-
-namespace {
-// flags raised by earlier frames are set aside (mrh_sync reports them) so that a call which checks its own outcome on the
-// device — import, unpack — answers for itself only
-int set_aside_flags(mrh_ctx* c) {
-  u32 flags = 0;
-  int rc = take_device_flags(c, &flags);
-  if (rc) return rc;
-  c->flags_deferred |= flags;
-  return MRH_OK;
-}
-void map_changed_in_bulk(mrh_ctx* c) {
-  c->mr_next_general = true;  // payload that has not been through a variance check
-  c->refill_flag_valid = false;
-  c->mr_summaries_valid = false;
-  c->table_dirty = true;
-}
-}  // namespace
-
-// room on the coarse free list for `need` coarse blocks, in allocateMemoryLow's portions (vds.cu:860-871: k_refill): an import or a
-// merge into a context whose frames have not refilled the list yet (vds.cu:885-891 does it at the start of a frame).  Blocks.
-static int ensure_coarse_units(mrh_ctx* c, const uint64_t need) {
-  if (!c->tab.multi_res || need == 0) return MRH_OK;
-  hipStream_t s = c->stream;
-  int lev[2] = {0, 0};  // CTR_HEAP_FINE, CTR_HEAP_COARSE are adjacent: stack tops, free count = top + 1
-  HIP_TRY(c, hipMemcpyAsync(lev, &c->tab.ctr[CTR_HEAP_FINE], 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  int64_t fine_free = (int64_t) lev[0] + 1, coarse_free = (int64_t) lev[1] + 1;
-  while (coarse_free < (int64_t) need && c->low_blocks_to_allocate > 0 && fine_free > (int64_t) c->low_blocks_to_allocate) {
-    HIP_TRY(c, hipMemsetAsync(c->d_flag, 0xFF, sizeof(int), s));  // any non-zero flag: refill
-    k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, s>>>(c->tab, c->low_blocks_to_allocate, c->d_flag);
-    fine_free -= c->low_blocks_to_allocate;
-    coarse_free += 8 * (int64_t) c->low_blocks_to_allocate;
-  }
-  c->refill_flag_valid = false;
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
-
-int mrh_import_blocks(mrh_ctx* c, const mrh_block_desc* descs, const mrh_voxel* voxels, uint64_t n) {
-  int rc = ensure_ready(c, "mrh_import_blocks");
-  if (rc) return rc;
-  if (n == 0) return MRH_OK;
-  if (!descs || !voxels) return fail(c, MRH_ERR_INVALID_ARG, "mrh_import_blocks: null argument");
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_import_blocks: an exchange is pending (call mrh_integrate_resume)");
-  rc = set_aside_flags(c);
-  if (rc) return rc;
-  if (c->tab.multi_res) {
-    uint64_t need = 0;
-    for (uint64_t k = 0; k < n; k++) need += descs[k].resolution != 0;
-    rc = ensure_coarse_units(c, need);
-    if (rc) return rc;
-  }
-  map_changed_in_bulk(c);
-  // two staging buffers, the copies on their own stream: the host-to-device copy of chunk i + 1 (the caller's memory is
-  // pageable: the runtime stages it) runs under the insert kernel of chunk i; one synchronisation at the end
-  const uint64_t chunk = 4096;  // 24 MiB of voxels
-  struct Pipe {
-    hipStream_t copy = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
-    ~Pipe() {
-      if (copy) { (void) hipStreamSynchronize(copy); (void) hipStreamDestroy(copy); }
-      for (hipEvent_t e : copied) if (e) (void) hipEventDestroy(e);
-      for (hipEvent_t e : done) if (e) (void) hipEventDestroy(e);
-    }
-  } pipe;
-  DevBuf<int4> d_descs[2];
-  DevBuf<char> d_vox[2];
-  const int nbuf = n > chunk ? 2 : 1;
-  HIP_TRY(c, hipStreamCreateWithFlags(&pipe.copy, hipStreamNonBlocking));
-  for (int b = 0; b < nbuf; b++) {
-    HIP_TRY(c, d_descs[b].alloc(chunk));
-    HIP_TRY(c, d_vox[b].alloc(chunk * (size_t) kFineBytes));
-    HIP_TRY(c, hipEventCreateWithFlags(&pipe.copied[b], hipEventDisableTiming));
-    HIP_TRY(c, hipEventCreateWithFlags(&pipe.done[b], hipEventDisableTiming));
-  }
-  uint64_t it = 0;
-  for (uint64_t first = 0; first < n; first += chunk, it++) {
-    const uint64_t cnt = (n - first) < chunk ? (n - first) : chunk;
-    const int b = (int) (it & 1);
-    if (it >= 2) HIP_TRY(c, hipStreamWaitEvent(pipe.copy, pipe.done[b], 0));  // the kernel that read this buffer two chunks ago
-    HIP_TRY(c, hipMemcpyAsync(d_descs[b], &descs[first], cnt * sizeof(int4), hipMemcpyHostToDevice, pipe.copy));
-    HIP_TRY(c, hipMemcpyAsync(d_vox[b], &voxels[first * 512], cnt * (size_t) kFineBytes, hipMemcpyHostToDevice, pipe.copy));
-    HIP_TRY(c, hipEventRecord(pipe.copied[b], pipe.copy));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, pipe.copied[b], 0));
-    k_import<kImportPlain><<<(int) (cnt < 2048 ? cnt : 2048), 512, 0, c->stream>>>(c->map, c->tab, c->fast.summary, (int) cnt, (const char*) (int4*) d_descs[b], sizeof(int4),
-                                                                                   (const char*) d_vox[b], (size_t) kFineBytes, nullptr, nullptr);
-    HIP_TRY(c, hipEventRecord(pipe.done[b], c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  u32 flags = 0;
-  rc = take_device_flags(c, &flags);
-  if (rc) return rc;
-  return check_device_flags(c, flags);
-}
-
-// ---- multi-GPU block exchange (include/mrhash_hip.h) -----------------------------------------------------------------
-
-int mrh_set_sharding(mrh_ctx* c, int shard_rank, int shard_count, int shard_chunk_log2) {
-  if (!c) return MRH_ERR_INVALID_ARG;
-  if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(c, MRH_ERR_INVALID_ARG, "mrh_set_sharding: rank %d of %d", shard_rank, shard_count);
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_set_sharding: an exchange is pending (call mrh_integrate_resume)");
-  {
-    const int frc = ensure_ready(c, "mrh_set_sharding");  // the last pipelined frame is integrated under the ownership it was allocated with
-    if (frc) return frc;
-  }
-  c->p.shard_rank = shard_rank; c->p.shard_count = shard_count; c->p.shard_chunk_log2 = shard_chunk_log2;
-  c->map.shard_rank = shard_rank;
-  c->map.shard_count = shard_count;
-  c->map.shard_chunk_log2 = (shard_chunk_log2 > 0 && shard_chunk_log2 < 16) ? shard_chunk_log2 : 3;
-  return MRH_OK;
-}
-
-namespace {
-// live blocks matching a predicate -> Tab::compact[0, n)
-int select_blocks(mrh_ctx* c, int sel_mode, int rank_arg, int* out_n) {
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_COMPACT], 0, sizeof(int), s));
-  k_select_blocks<<<512, 256, 0, s>>>(c->map, c->tab, sel_mode, rank_arg);
-  int n = 0;
-  HIP_TRY(c, hipMemcpyAsync(&n, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipGetLastError());
-  *out_n = n;
-  return MRH_OK;
-}
-// frees Tab::compact[0, n) (garbageCollectFree's kernel with every decision set)
-int free_compact(mrh_ctx* c, int n) {
-  if (n <= 0) return MRH_OK;
-  hipStream_t s = c->stream;
-  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], &n, sizeof(int), hipMemcpyHostToDevice, s));
-  k_fill_u32<<<256, 256, 0, s>>>(c->d_decision, (size_t) n, 1u);
-  k_gc_free<false><<<256, 256, 0, s>>>(c->tab, c->d_decision);
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipGetLastError());
-  map_changed_in_bulk(c);
-  return MRH_OK;
-}
-}  // namespace
-
-int mrh_pack_blocks(mrh_ctx* c, int mode, int rank_arg, const mrh_block_record** out_records, uint64_t* out_n, int* out_is_device_memory) {
-  int rc = ensure_ready(c, "mrh_pack_blocks");
-  if (rc) return rc;
-  if (!out_records || !out_n) return MRH_ERR_INVALID_ARG;
-  if (mode != MRH_PACK_HALO && mode != MRH_PACK_OWNER) return fail(c, MRH_ERR_INVALID_ARG, "mrh_pack_blocks: bad mode %d", mode);
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_pack_blocks: an exchange is pending (call mrh_integrate_resume)");
-  int n = 0;
-  rc = select_blocks(c, mode == MRH_PACK_HALO ? kSelHalo : kSelOwner, rank_arg, &n);
-  if (rc) return rc;
-  if (out_is_device_memory) *out_is_device_memory = 1;
-  *out_n = (uint64_t) n;
-  *out_records = nullptr;
-  if (n == 0) return MRH_OK;
-  const size_t bytes = (size_t) n * sizeof(mrh_block_record);
-  if (bytes > c->pack_cap) {  // select_blocks blocked: nothing reads the old buffer
-    rc = regrow(c, c->d_pack, c->pack_cap, bytes + bytes / 4, bytes + bytes / 4, false);
-    if (rc) return rc;
-  }
-  k_pack_records<<<n < 4096 ? n : 4096, 512, 0, c->stream>>>(c->tab, 0, n, c->d_pack);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipGetLastError());
-  *out_records = (const mrh_block_record*) c->d_pack;
-  return MRH_OK;
-}
-
-int mrh_unpack_blocks(mrh_ctx* c, int mode, const mrh_block_record* records, uint64_t n, int is_device_memory, uint64_t* out_taken) {
-  int rc = ensure_ready(c, "mrh_unpack_blocks");
-  if (rc) return rc;
-  if (out_taken) *out_taken = 0;
-  if (mode != MRH_UNPACK_HALO && mode != MRH_UNPACK_MERGE) return fail(c, MRH_ERR_INVALID_ARG, "mrh_unpack_blocks: bad mode %d", mode);
-  if (n == 0) return MRH_OK;
-  if (!records) return fail(c, MRH_ERR_INVALID_ARG, "mrh_unpack_blocks: null argument");
-  if (n > 0x7FFFFFFFull) return fail(c, MRH_ERR_CAPACITY, "mrh_unpack_blocks: %llu records in one call", (unsigned long long) n);
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_unpack_blocks: an exchange is pending (call mrh_integrate_resume)");
-  rc = set_aside_flags(c);
-  if (rc) return rc;
-  hipStream_t s = c->stream;
-  DevBuf<char> staged;
-  const char* d_rec = (const char*) records;
-  if (!is_device_memory) {  // host records (tests over gloo): one staged copy
-    HIP_TRY(c, staged.alloc((size_t) n * sizeof(mrh_block_record)));
-    HIP_TRY(c, hipMemcpyAsync(staged, records, (size_t) n * sizeof(mrh_block_record), hipMemcpyHostToDevice, s));
-    d_rec = staged;
-  }
-  if (!c->d_taken) HIP_TRY(c, hipMalloc((void**) &c->d_taken, sizeof(u32)));
-  HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
-  if (mode == MRH_UNPACK_HALO && c->halo_upper + n > c->halo_cap) {  // room for every record of this call on the halo list
-    const size_t cap = (c->halo_upper + n) + (c->halo_upper + n) / 2;
-    int4* grown = nullptr;
-    HIP_TRY(c, hipMalloc((void**) &grown, cap * sizeof(int4)));
-    if (c->d_halo && c->halo_upper) HIP_TRY(c, hipMemcpyAsync(grown, c->d_halo, c->halo_upper * sizeof(int4), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (c->d_halo) HIP_TRY(c, hipFree(c->d_halo));
-    c->d_halo = grown;
-    c->halo_cap = cap;
-  }
-  map_changed_in_bulk(c);
-  const int grid = (int) (n < 4096 ? n : 4096);
-  const size_t stride = sizeof(mrh_block_record);
-  // a merge into a variance-adaptive map: room on the coarse free list for every coarse record of the call, in
-  // allocateMemoryLow's portions (vds.cu:860-871: k_refill), and a list for the fine slots that make way for coarse records
-  DevBuf<u32> released;
-  if (mode == MRH_UNPACK_MERGE && c->tab.multi_res) {
-    HIP_TRY(c, released.alloc((size_t) n + 1));
-    HIP_TRY(c, hipMemsetAsync(released, 0, sizeof(u32), s));
-    k_count_coarse_records<<<64, 256, 0, s>>>(d_rec, stride, (int) n, c->d_taken);  // d_taken doubles as the counter, zeroed again below
-    u32 need = 0;
-    HIP_TRY(c, hipMemcpyAsync(&need, c->d_taken, sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
-    rc = ensure_coarse_units(c, need);
-    if (rc) return rc;
-  }
-  if (mode == MRH_UNPACK_HALO) {
-    k_import<kImportHalo><<<grid, 512, 0, s>>>(c->map, c->tab, c->fast.summary, (int) n, d_rec, stride, d_rec + sizeof(mrh_block_desc), stride, c->d_halo, c->d_taken);
-    c->halo_upper += n;
-  } else {
-    k_import<kImportMerge><<<grid, 512, 0, s>>>(c->map, c->tab, c->fast.summary, (int) n, d_rec, stride, d_rec + sizeof(mrh_block_desc), stride, nullptr, c->d_taken,
-                                                (u32*) released);
-    if (released.p) k_release_fine<<<1, 256, 0, s>>>(c->tab, released);
-  }
-  u32 taken = 0;
-  HIP_TRY(c, hipMemcpyAsync(&taken, c->d_taken, sizeof(u32), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipGetLastError());
-  if (out_taken) *out_taken = taken;
-  u32 flags = 0;
-  rc = take_device_flags(c, &flags);
-  if (rc) return rc;
-  return check_device_flags(c, flags);
-}
-
-int mrh_drop_blocks(mrh_ctx* c, int mode, uint64_t* out_dropped) {
-  int rc = ensure_ready(c, "mrh_drop_blocks");
-  if (rc) return rc;
-  if (out_dropped) *out_dropped = 0;
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_drop_blocks: an exchange is pending (call mrh_integrate_resume)");
-  int n = 0;
-  if (mode == MRH_DROP_HALO) {
-    HIP_TRY(c, hipMemcpyAsync(&n, &c->tab.ctr[CTR_HALO], sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->tab.compact, c->d_halo, (size_t) n * sizeof(int4), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_HALO], 0, sizeof(int), c->stream));
-    c->halo_upper = 0;
-  } else if (mode == MRH_DROP_FOREIGN || mode == MRH_DROP_ALL) {
-    rc = select_blocks(c, mode == MRH_DROP_FOREIGN ? kSelForeign : kSelAll, 0, &n);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_HALO], 0, sizeof(int), c->stream));  // halo blocks are foreign: they go with the rest
-    c->halo_upper = 0;
-  } else {
-    return fail(c, MRH_ERR_INVALID_ARG, "mrh_drop_blocks: bad mode %d", mode);
-  }
-  rc = free_compact(c, n);
-  if (rc) return rc;
-  if (out_dropped) *out_dropped = (uint64_t) n;
-  return MRH_OK;
-}
+extern "C" {
 
 int mrh_selftest_division(mrh_ctx* c, uint64_t samples, uint64_t seed, uint64_t* out_mismatches) {
   int rc = ensure_ready(c, "mrh_selftest_division");
@@ -2973,11 +2656,7 @@ int mrh_raycast(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major
   const size_t bytes = npix * (sizeof(float) * 4 + 3);
   rc_ = regrow(c, c->d_ray, c->ray_cap, npix, bytes, false);  // the previous raycast has finished (it blocked): nothing reads the old buffers
   if (rc_) return rc_;
-  if (npix > c->h_ray_cap) {
-    if (c->h_ray) { (void) hipHostFree(c->h_ray); c->h_ray = nullptr; c->h_ray_cap = 0; }
-    HIP_TRY(c, hipHostMalloc((void**) &c->h_ray, bytes, hipHostMallocDefault));
-    c->h_ray_cap = npix;
-  }
+  if ((rc_ = regrow_pinned(c, c->h_ray, c->h_ray_cap, npix, bytes))) return rc_;
   const bool want_n = out_normals && (p->outputs & MRH_RAYCAST_NORMALS), want_c = out_rgb && (p->outputs & MRH_RAYCAST_COLORS);
   float* d_depth = (float*) c->d_ray;
   float* d_normals = (float*) (c->d_ray + npix * sizeof(float));
@@ -3142,17 +2821,13 @@ int mrh_estimate_normals(mrh_ctx* c, const mrh_normals_params* p, mrh_normals_in
 }
 
 int mrh_get_normals(mrh_ctx* c, const float** out_nxyz, uint64_t* out_n, mrh_normals_info* out_info) {
-  const int rc = ensure_device(c, "mrh_get_normals");
+  int rc = ensure_device(c, "mrh_get_normals");
   if (rc) return rc;
   if (!out_nxyz || !out_n) return fail(c, MRH_ERR_INVALID_ARG, "mrh_get_normals: null argument");
   auto& L = c->lidar;
   auto& N = c->nrm;
   const size_t n = L.num_normals;
-  if (n > N.h_out_cap) {
-    if (N.h_out) { (void) hipHostFree(N.h_out); N.h_out = nullptr; N.h_out_cap = 0; }
-    HIP_TRY(c, hipHostMalloc((void**) &N.h_out, n * 3 * sizeof(float), hipHostMallocDefault));
-    N.h_out_cap = n;
-  }
+  if ((rc = regrow_pinned(c, N.h_out, N.h_out_cap, n, n * 3 * sizeof(float)))) return rc;
   if (n) HIP_TRY(c, hipMemcpyAsync(N.h_out, L.d_normals, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   normals_fold_info(c);

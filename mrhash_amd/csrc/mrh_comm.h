@@ -138,18 +138,11 @@ int comm_small(mrh_comm* m, size_t bytes) {
   return MRH_OK;
 }
 
-// grow-only device buffer of the context (contents up to `keep` bytes survive)
-int ctx_grow(mrh_ctx* c, char*& p, size_t& cap, const size_t need, const size_t keep) {
-  if (need <= cap) return MRH_OK;
-  const size_t ncap = need + need / 4;
-  char* grown = nullptr;
-  HIP_TRY(c, hipMalloc((void**) &grown, ncap));
-  if (p && keep) HIP_TRY(c, hipMemcpyAsync(grown, p, keep, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (p) HIP_TRY(c, hipFree(p));
-  p = grown;
-  cap = ncap;
-  return MRH_OK;
+// room for `bytes` in an exchange buffer of the context (d_xsend / d_xrecv): at least 256 bytes, a quarter of head room.  Nothing is
+// kept, yet it grows as ctx_grow did (regrow_keep: new buffer first, drained stream, then the old one goes), not free-first as regrow
+int exchange_room(mrh_ctx* c, char*& p, size_t& cap, const size_t bytes) {
+  const size_t need = std::max<size_t>(bytes, 256);
+  return need <= cap ? MRH_OK : regrow_keep(c, p, cap, need + need / 4, need + need / 4, 0);
 }
 
 // every rank's `n_words` 64-bit words -> all[world * n_words] on the host (device staging in the communicator, the
@@ -169,7 +162,7 @@ int ctx_allgather_u64(mrh_ctx* c, const uint64_t* mine, const size_t n_words, ui
 
 // Every rank contributes the status of its local steps as word 0 of a small all-gather (plus `n_words` payload words); the
 // call fails on EVERY rank if it failed on any, so that no rank walks into a data collective its peers will never join (a
-// pack error, an out-of-memory in ctx_grow, a broken owner partition on one rank used to leave the others hanging inside
+// pack error, an out-of-memory in exchange_room, a broken owner partition on one rank used to leave the others hanging inside
 // ncclSend / ncclRecv, which have no time limit).  all: world * (1 + n_words) words, rank r's at r * (1 + n_words).
 int ctx_agree(mrh_ctx* c, const int local_rc, const char* who, const uint64_t* mine, const size_t n_words, std::vector<uint64_t>& all) {
   mrh_comm* m = c->comm;
@@ -468,7 +461,7 @@ int mrh_comm_exchange_halo(mrh_ctx* c, uint64_t* out_taken) {
   std::vector<uint64_t> off((size_t) world, 0);
   const bool self = comm_self_loop();
   for (int r = 0; r < world; r++) { off[r] = total_in; if (r != rank || self) total_in += counts[r]; }
-  rc = ctx_grow(c, c->d_xrecv, c->xrecv_cap, std::max<size_t>(total_in * rec, 256), 0);
+  rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, total_in * rec);
   rc = ctx_agree(c, rc, "mrh_comm_exchange_halo", nullptr, 0, agreed);  // the receive buffer exists on every rank
   if (rc) return rc;
   if (world > 1 || self) {
@@ -510,7 +503,7 @@ int mrh_comm_merge_submaps(mrh_ctx* c, int chunk_log2, mrh_comm_merge_info* out)
     if ((r2 = clk.mark())) return r2;
     int n_all = 0;
     if ((r2 = select_blocks(c, kSelAll, 0, &n_all))) return r2;
-    if ((r2 = ctx_grow(c, c->d_xsend, c->xsend_cap, std::max<size_t>((size_t) n_all * rec, 256), 0))) return r2;
+    if ((r2 = exchange_room(c, c->d_xsend, c->xsend_cap, (size_t) n_all * rec))) return r2;
     uint64_t packed = 0;
     for (int dest = 0; dest < world; dest++) {
       int n = 0;
@@ -518,7 +511,7 @@ int mrh_comm_merge_submaps(mrh_ctx* c, int chunk_log2, mrh_comm_merge_info* out)
       out_off[dest] = packed;
       out_counts[dest] = (uint64_t) n;
       if (packed + (uint64_t) n > (uint64_t) n_all) return fail(c, MRH_ERR_STATE, "mrh_comm_merge_submaps: the owner partition does not add up");
-      if (n) k_pack_records<<<n < 4096 ? n : 4096, 512, 0, c->stream>>>(c->tab, 0, n, c->d_xsend + packed * rec);
+      pack_selected(c, n, c->d_xsend + packed * rec);
       packed += (uint64_t) n;
     }
     HIP_TRY(c, hipGetLastError());
@@ -542,7 +535,7 @@ int mrh_comm_merge_submaps(mrh_ctx* c, int chunk_log2, mrh_comm_merge_info* out)
     in_off[src] = total_in;
     if (src != rank || self) total_in += in_counts[src];
   }
-  rc = ctx_grow(c, c->d_xrecv, c->xrecv_cap, std::max<size_t>(total_in * rec, 256), 0);
+  rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, total_in * rec);
   rc = ctx_agree(c, rc, "mrh_comm_merge_submaps", nullptr, 0, agreed);
   if (rc) return restore_sharding(rc);
   if ((rc = clk.mark())) return rc;
@@ -610,14 +603,14 @@ int mrh_comm_gather_mesh(mrh_ctx* c, int root, uint64_t* out_triangles) {
   // metadata travels through device staging (20 bytes a block), the triangles from soup to soup.  The triangle area starts on a
   // 256-byte boundary: the run merge reads it with 16-byte loads (k_permute_runs), and 20 * tot_b is only 4-byte aligned.
   const size_t meta_mine = (size_t) nb * 20, meta_all = (size_t) tot_b * 20, meta_span = (meta_all + 255) & ~(size_t) 255;
-  rc = ctx_grow(c, c->d_xsend, c->xsend_cap, std::max<size_t>(meta_mine, 256), 0);
+  rc = exchange_room(c, c->d_xsend, c->xsend_cap, meta_mine);
   if (!rc && nb) {
     hipError_t e = hipMemcpyAsync(c->d_xsend, my_d.data(), nb * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(c->d_xsend + nb * 16, my_c.data(), nb * 4, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) rc = fail(c, MRH_ERR_DEVICE, "mrh_comm_gather_mesh: staging the block metadata failed: %s", hipGetErrorString(e));
   }
   const size_t tri = sizeof(mrh_triangle);
-  if (!rc && rank == root) rc = ctx_grow(c, c->d_xrecv, c->xrecv_cap, std::max<size_t>(meta_span + tot_t * tri, 256), 0);
+  if (!rc && rank == root) rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, meta_span + tot_t * tri);
   rc = ctx_agree(c, rc, "mrh_comm_gather_mesh", nullptr, 0, agreed);  // buffers exist everywhere before anybody sends
   if (rc) return rc;
   char* d_meta = c->d_xrecv;             // root: [rank r's descs | counts] at boff[r] * 20

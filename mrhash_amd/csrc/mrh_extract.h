@@ -631,14 +631,9 @@ int soup_to_host(mrh_ctx* c, const u64 total) {
 int deliver_soup(mrh_ctx* c, const u64 total) {
   hipStream_t s = c->stream;
   if (!c->merge_on) return c->mesh_on_host ? MRH_OK : process_triangles_device(c, c->d_soup, total);
-  if (c->acc_n + total > c->acc_cap) {
-    const size_t cap = (c->acc_n + total) + (c->acc_n + total) / 2;
-    mrh_triangle* grown = nullptr;
-    HIP_TRY(c, hipMalloc((void**) &grown, cap * sizeof(mrh_triangle)));
-    if (c->acc_n) HIP_TRY(c, hipMemcpyAsync(grown, c->d_acc, c->acc_n * sizeof(mrh_triangle), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    if (c->d_acc) HIP_TRY(c, hipFree(c->d_acc));
-    c->d_acc = grown; c->acc_cap = cap;
+  const size_t room = c->acc_n + total, cap = room + room / 2;
+  if (room > c->acc_cap) {
+    if (const int rc = regrow_keep(c, c->d_acc, c->acc_cap, cap, cap * sizeof(mrh_triangle), c->acc_n * sizeof(mrh_triangle))) return rc;
   }
   HIP_TRY(c, hipMemcpyAsync(c->d_acc + c->acc_n, c->d_soup, total * sizeof(mrh_triangle), hipMemcpyDeviceToDevice, s));
   c->acc_n += total;

@@ -651,6 +651,39 @@ def test_stream_out_and_import_match_oracle(hip, oracle):
     assert a.stats().occupied_fine == 0 and len(n_all) == len(b.stream_out((0, 0, 0), -1.0)[0])
 
 
+def test_block_io_across_chunk_boundaries(hip, oracle):
+    """mrh_dump_blocks / mrh_stream_out copy out in chunks of 8 192 blocks, mrh_import_blocks copies in through two staging buffers
+    of 4 096: a map of 8 883 live blocks (six frames of the 640 x 480 stream) takes two dump chunks and three import chunks, the
+    third of which waits for the kernel that read its buffer.  Dump, a partial and a full stream-out, and the import of both
+    parts in non-canonical order, each against the oracle; the import must restore the first dump byte for byte."""
+    a, b = _pair(hip, oracle, synth.REPLICA_640, synth.REPLICA_PARAMS, 16384)
+    for f in synth.replica_stream(6):
+        pu.feed(a, f)
+        pu.feed(b, f)
+    a.sync()
+    (d0a, v0a), (d0b, v0b) = a.dump_blocks(), b.dump_blocks()
+    assert len(d0b) > 8192, "the map no longer crosses a chunk boundary"
+    assert d0a.tobytes() == d0b.tobytes() and v0a.tobytes() == v0b.tobytes()
+    # the median distance of the block origins: about half of the map leaves
+    (dfa, vfa), (dfb, vfb) = a.stream_out((0, 0, 0), 2.875), b.stream_out((0, 0, 0), 2.875)
+    assert dfa.tobytes() == dfb.tobytes() and vfa.tobytes() == vfb.tobytes()
+    assert len(dfb) > 1000 and len(d0b) - len(dfb) > 1000
+    pu.compare_maps(a, b)
+    (dna, vna), (dnb, vnb) = a.stream_out((0, 0, 0), -1.0), b.stream_out((0, 0, 0), -1.0)
+    assert dna.tobytes() == dnb.tobytes() and vna.tobytes() == vnb.tobytes()
+    assert len(dnb) == len(d0b) - len(dfb) and a.stats().occupied_fine == 0
+    # far part first: not in position order
+    a.import_blocks(np.concatenate([dfa, dna]), np.concatenate([vfa, vna]))
+    b.import_blocks(np.concatenate([dfb, dnb]), np.concatenate([vfb, vnb]))
+    for e in (a, b):
+        d1, v1 = e.dump_blocks()
+        assert d1.tobytes() == d0b.tobytes() and v1.tobytes() == v0b.tobytes()
+        assert e.stats().error_flags == 0
+    assert a.free_blocks() == b.free_blocks()
+    a.close()
+    b.close()
+
+
 def test_gc_and_starve_at_full_resolution(hip, oracle):
     """640x480, GC every frame, starve on frames 2 and 4: the frames where GC is decided inside k_back, the starve
     frames (k_back without GC -> k_starve -> k_summarize_all -> k_free_lists) and the hand-over between them."""

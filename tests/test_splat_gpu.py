@@ -181,3 +181,34 @@ def test_first_seeding_call_and_a_camera_change_leave_the_other_buffers_alone(hi
     pu.compare_maps(a, b)
     a.close()
     b.close()
+
+
+def test_seeding_with_alternating_image_shapes(hip, oracle):
+    """One context seeded under two image shapes in turn (A, B, A, B): the quad-tree buffers are sized by the potential node
+    count of the shape, so every call reallocates them — smaller, larger, smaller — and no call may find the size of another
+    shape recorded over its buffers.  Seeds and leaves against the oracle after every call, the mesh at the end."""
+    a = pu.make_engine(hip, synth.CFG1, dict(synth.CFG1_PARAMS), 16384)
+    b = pu.make_engine(oracle, synth.CFG1, dict(synth.CFG1_PARAMS), 16384)
+    p = capi.Params(num_sdf_blocks=16384, **synth.CFG1_PARAMS)
+    KA, KB = synth.CFG1, synth.Intrinsics(96.0, 96.0, 48.0, 40.0, 80, 96)
+    rng = np.random.default_rng(3)
+    counts = []
+    for i, zc in enumerate((None, 1.51)):
+        fa = synth.cfg1_sphere() if zc is None else synth.cfg1_sphere(zc=zc)
+        depth = (1.2 + 0.1 * rng.random((KB.rows, KB.cols))).astype(F32)
+        rgb = synth.textured_image(KB.rows, KB.cols, seed=2 + i)
+        for e in (a, b):
+            e.set_camera(KA.fx, KA.fy, KA.cx, KA.cy, KA.rows, KA.cols, p.min_depth, p.max_depth)
+            pu.feed(e, fa)
+        counts.append(_same(a, b, 0.002, 1))
+        for e in (a, b):
+            e.set_camera(KB.fx, KB.fy, KB.cx, KB.cy, KB.rows, KB.cols, 0.01, 30.0)
+            e.set_pose(np.eye(3, dtype=F32), np.zeros(3, F32))
+            e.upload_depth(depth)
+            e.upload_rgb(rgb)
+            assert not e.integrate()
+        counts.append(_same(a, b, 0.001, 1))
+    assert all(leaves > 0 for leaves, _ in counts) and counts[0][1] > 0
+    pu.compare_meshes(a, b)
+    a.close()
+    b.close()
