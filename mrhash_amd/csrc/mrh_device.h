@@ -197,25 +197,28 @@ __device__ __forceinline__ v2f div_rr2(v2f a, v2f b, v2f r) {
 }
 
 // ---- wave64 reductions on the VALU (DPP), result wave-uniform in an SGPR: no LDS traffic, no NaN canonicalisation
-#define MRH_DPP_STEP(OP, x, ctrl, rmask) x = OP(x, (u32) __builtin_amdgcn_update_dpp((int) (x), (int) (x), ctrl, rmask, 0xF, false))
+// `old` of the DPP move is the operation's IDENTITY (not x): the compiler then folds move and operation into one
+// v_min_u32_dpp / v_max_u32_dpp per step.  A lane that a row_mask switches off receives the identity instead of its own x,
+// and OP(x, identity) == OP(x, x) == x: the value of every lane after every step is what it was with old = x.
+#define MRH_DPP_STEP(OP, ID, x, ctrl, rmask) x = OP(x, (u32) __builtin_amdgcn_update_dpp((int) (ID), (int) (x), ctrl, rmask, 0xF, false))
 __device__ __forceinline__ u32 umin_(u32 a, u32 b) { return a < b ? a : b; }
 __device__ __forceinline__ u32 umax_(u32 a, u32 b) { return a > b ? a : b; }
 __device__ __forceinline__ u32 wave_min_u32(u32 x) {
-  MRH_DPP_STEP(umin_, x, 0xB1, 0xF);   // quad_perm [1,0,3,2]
-  MRH_DPP_STEP(umin_, x, 0x4E, 0xF);   // quad_perm [2,3,0,1]
-  MRH_DPP_STEP(umin_, x, 0x141, 0xF);  // row_half_mirror
-  MRH_DPP_STEP(umin_, x, 0x140, 0xF);  // row_mirror
-  MRH_DPP_STEP(umin_, x, 0x142, 0xA);  // row_bcast:15 -> rows 1, 3
-  MRH_DPP_STEP(umin_, x, 0x143, 0xC);  // row_bcast:31 -> rows 2, 3
+  MRH_DPP_STEP(umin_, 0xFFFFFFFFu, x, 0xB1, 0xF);   // quad_perm [1,0,3,2]
+  MRH_DPP_STEP(umin_, 0xFFFFFFFFu, x, 0x4E, 0xF);   // quad_perm [2,3,0,1]
+  MRH_DPP_STEP(umin_, 0xFFFFFFFFu, x, 0x141, 0xF);  // row_half_mirror
+  MRH_DPP_STEP(umin_, 0xFFFFFFFFu, x, 0x140, 0xF);  // row_mirror
+  MRH_DPP_STEP(umin_, 0xFFFFFFFFu, x, 0x142, 0xA);  // row_bcast:15 -> rows 1, 3
+  MRH_DPP_STEP(umin_, 0xFFFFFFFFu, x, 0x143, 0xC);  // row_bcast:31 -> rows 2, 3
   return (u32) __builtin_amdgcn_readlane((int) x, 63);
 }
 __device__ __forceinline__ u32 wave_max_u32(u32 x) {
-  MRH_DPP_STEP(umax_, x, 0xB1, 0xF);
-  MRH_DPP_STEP(umax_, x, 0x4E, 0xF);
-  MRH_DPP_STEP(umax_, x, 0x141, 0xF);
-  MRH_DPP_STEP(umax_, x, 0x140, 0xF);
-  MRH_DPP_STEP(umax_, x, 0x142, 0xA);
-  MRH_DPP_STEP(umax_, x, 0x143, 0xC);
+  MRH_DPP_STEP(umax_, 0u, x, 0xB1, 0xF);
+  MRH_DPP_STEP(umax_, 0u, x, 0x4E, 0xF);
+  MRH_DPP_STEP(umax_, 0u, x, 0x141, 0xF);
+  MRH_DPP_STEP(umax_, 0u, x, 0x140, 0xF);
+  MRH_DPP_STEP(umax_, 0u, x, 0x142, 0xA);
+  MRH_DPP_STEP(umax_, 0u, x, 0x143, 0xC);
   return (u32) __builtin_amdgcn_readlane((int) x, 63);
 }
 

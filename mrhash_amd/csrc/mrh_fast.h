@@ -88,6 +88,14 @@ struct Proj4 {
   int row[4], col[4];
   u32 mask;  // bit k: voxel k projects into the image (camera.cuh:131-147)
 };
+// Bit k of Proj4::mask as a predicate, restated from the voxel's depth, row and column: k_back evaluates it where it is used.  A
+// predicate is a lane mask in a scalar register pair — no VALU instruction packs it into bits or takes it out again —, and one
+// evaluated late does not occupy that pair across the footprint staging.
+template <bool SPH>
+__device__ __forceinline__ bool proj_ok(const Cam& c, const Proj4& P, const int k) {
+  const bool depth_ok = SPH ? !(P.pcz[k] < c.min_depth || P.pcz[k] > c.max_depth) : !(P.pcz[k] <= c.min_depth || P.pcz[k] > c.max_depth);
+  return depth_ok && (u32) P.row[k] < (u32) c.rows && (u32) P.col[k] < (u32) c.cols;
+}
 
 __device__ __forceinline__ Proj4 project4(const Cam& c, const Map& m, const int4 ent, const int q) {
   Proj4 P;
@@ -110,7 +118,7 @@ __device__ __forceinline__ Proj4 project4(const Cam& c, const Map& m, const int4
     const float rz = rcp_refined(Z);
     const int row = f2i_hw((div_rr(c.fy * Y, Z, rz) + c.cy) + 0.5f);
     const int col = f2i_hw((div_rr(c.fx * X, Z, rz) + c.cx) + 0.5f);
-    const bool ok = depth_ok && row >= 0 && col >= 0 && row < c.rows && col < c.cols;
+    const bool ok = depth_ok && (u32) row < (u32) c.rows && (u32) col < (u32) c.cols;  // 0 <= row < rows, 0 <= col < cols (rows, cols > 0)
     P.row[k] = row;
     P.col[k] = col;
     P.mask |= ok ? (1u << k) : 0u;
@@ -144,7 +152,7 @@ __device__ __forceinline__ Proj4 project4_sph(const Cam& c, const Map& m, const 
     const float el = mrh_asinf(Z / range);
     const int row = f2i_hw((c.fy * el + c.cy) + 0.5f);
     const int col = f2i_hw((c.fx * az + c.cx) + 0.5f);
-    const bool ok = depth_ok && row >= 0 && col >= 0 && row < c.rows && col < c.cols;
+    const bool ok = depth_ok && (u32) row < (u32) c.rows && (u32) col < (u32) c.cols;  // 0 <= row < rows, 0 <= col < cols (rows, cols > 0)
     P.row[k] = row;
     P.col[k] = col;
     P.mask |= ok ? (1u << k) : 0u;
@@ -152,26 +160,47 @@ __device__ __forceinline__ Proj4 project4_sph(const Cam& c, const Map& m, const 
   return P;
 }
 
-// which of the 4 voxels get written: depth valid and sdf > -truncation (vds.cu:1134-1145)
+// sdf = depth - voxel depth (unclamped) and the truncation of the pixel's depth for the 4 voxels, two per instruction (each half
+// rounds like the scalar instruction): computed once by update4, read again by blend4
+struct Sdf4 {
+  v2f sd[2], trn[2];
+};
+// which of the 4 voxels get written: in the image (`ok`), depth valid and sdf > -truncation (vds.cu:1134-1145)
 template <typename PT>
-__device__ __forceinline__ u32 update_mask4(const Cam& c, const Map& m, const PT& P, const float (&d)[4]) {
-  u32 mask = P.mask;
+__device__ __forceinline__ void update4(const Cam& c, const Map& m, const PT& P, const bool (&ok)[4], const float (&d)[4], Sdf4& g,
+                                        bool (&upd)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; k += 2) {
+    const v2f dd = mk2(d[k], d[k + 1]);
+    g.trn[k >> 1] = splat2(m.trunc) + splat2(m.trunc_scale) * dd;  // get_truncation
+    g.sd[k >> 1] = dd - mk2(P.pcz[k], P.pcz[k + 1]);
+  }
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const bool depth_bad = (d[k] == 0.f) || (d[k] > c.max_int_dist);
-    const float sdf = d[k] - P.pcz[k];
-    const float trn = get_truncation(d[k], m.trunc, m.trunc_scale);
-    if (depth_bad || sdf <= -trn) mask &= ~(1u << k);
+    const float sdf = (k & 1) ? g.sd[k >> 1].y : g.sd[k >> 1].x;
+    const float trn = (k & 1) ? g.trn[k >> 1].y : g.trn[k >> 1].x;
+    upd[k] = ok[k] && !(depth_bad || sdf <= -trn);
   }
-  return mask;
+}
+// the same as a bit mask
+template <typename PT>
+__device__ __forceinline__ u32 update_mask4(const Cam& c, const Map& m, const PT& P, const float (&d)[4]) {
+  Sdf4 g;
+  bool upd[4];
+  const bool ok[4] = {(P.mask & 1u) != 0, (P.mask & 2u) != 0, (P.mask & 4u) != 0, (P.mask & 8u) != 0};
+  update4(c, m, P, ok, d, g, upd);
+  return (upd[0] ? 1u : 0u) | (upd[1] ? 2u : 0u) | (upd[2] ? 4u : 0u) | (upd[3] ? 8u : 0u);
 }
 
 // running weighted mean, colour blend, weight clamp, variance term (vds.cu:1147-1180, vhu.cuh:167-181), two voxels
 // per instruction where the arithmetic is plain fp32 (mrh_device.h, v2f).  The clamp `sd >= 0 ? min(t, sd) :
 // max(-t, sd)` is one v_med3_f32 (t >= 0 is checked at mrh_create; a NaN sd yields -t on both sides).
-template <bool SAFEDIV, typename PT>
-__device__ __forceinline__ void blend4(const Map& m, const PT& P, const u32 mask, const float (&d)[4], const u32 (&cpx)[4],
-                                       float (&s)[4], u32 (&w)[4], float (&ss)[4]) {
+// `g`, `upd`: update4's sdf, truncation and verdicts.  s, w: the voxels of `upd` are replaced, the others stay.  ss: the same with
+// KEEP_SS; without it every entry receives its variance term and the caller reads those of `upd` only (no select).
+template <bool SAFEDIV, bool KEEP_SS>
+__device__ __forceinline__ void blend4(const Map& m, const Sdf4& g, const bool (&upd)[4], const u32 (&cpx)[4], float (&s)[4], u32 (&w)[4],
+                                       float (&ss)[4]) {
   const u32 w1 = (u32) (m.weight_sample & 0xFF);
   const u32 wmax = (u32) (m.weight_max & 0xFF);
   const v2f half_vs = splat2(m.vs / 2), rh = splat2(m.r_half_vs), w1f = splat2((float) w1);
@@ -179,18 +208,19 @@ __device__ __forceinline__ void blend4(const Map& m, const PT& P, const u32 mask
   constexpr bool two = SAFEDIV, two_w = SAFEDIV;
 #pragma unroll
   for (int k = 0; k < 4; k += 2) {
-    const v2f dd = mk2(d[k], d[k + 1]);
-    const v2f trn = splat2(m.trunc) + splat2(m.trunc_scale) * dd;  // get_truncation
-    v2f sd = dd - mk2(P.pcz[k], P.pcz[k + 1]);
+    const v2f trn = g.trn[k >> 1];
+    v2f sd = g.sd[k >> 1];
     sd = mk2(__builtin_amdgcn_fmed3f(sd.x, -trn.x, trn.x), __builtin_amdgcn_fmed3f(sd.y, -trn.y, trn.y));
     const v2f s0 = mk2(s[k], s[k + 1]);
     const u32 old0 = w[k], old1 = w[k + 1];
     const u32 w00 = old0 >> 24, w01 = old1 >> 24;
     const v2f curr_mean = mk2(w00 > 0 ? s0.x : sd.x, w01 > 0 ? s0.y : sd.y);
     const v2f delta = div_cr2(sd - curr_mean, half_vs, rh, two);
-    const v2f wsum = mk2((float) (int) (w00 + w1), (float) (int) (w01 + w1));
+    // (float) (w0 + w1) as the sum of the two converted weights: both are integers <= 255, so the float sum is exact
+    const v2f w0f = mk2((float) w00, (float) w01);
+    const v2f wsum = w0f + w1f;
     // weight sums are integers <= 510: for those, v_rcp_f32 + one Newton step already IS the correctly rounded reciprocal
-    const v2f sn = div_cr2(s0 * mk2((float) w00, (float) w01) + sd * w1f, wsum, rcp_refined2(wsum), two_w);
+    const v2f sn = div_cr2(s0 * w0f + sd * w1f, wsum, rcp_refined2(wsum), two_w);
     const v2f delta2 = div_cr2(sd - sn, half_vs, rh, two);
     const v2f sq = splat2(0.f) + delta * delta2;
 #pragma unroll
@@ -203,11 +233,10 @@ __device__ __forceinline__ void blend4(const Map& m, const PT& P, const u32 mask
       const u32 c0x = (w0 == 0) ? c1x : (old & 0x00FFFFFFu);
       const u32 rgbn = (c0x | c1x) - (((c0x ^ c1x) >> 1) & 0x007F7F7Fu);
       const u32 wn = (w0 + w1) < wmax ? (w0 + w1) : wmax;
-      if ((mask >> (k + j)) & 1u) {
-        s[k + j] = j ? sn.y : sn.x;
-        w[k + j] = rgbn | (wn << 24);
-        ss[k + j] = j ? sq.y : sq.x;
-      }
+      const bool u = upd[k + j];
+      s[k + j] = u ? (j ? sn.y : sn.x) : s[k + j];
+      w[k + j] = u ? (rgbn | (wn << 24)) : w[k + j];
+      ss[k + j] = (u || !KEEP_SS) ? (j ? sq.y : sq.x) : ss[k + j];
     }
   }
 }
@@ -228,10 +257,14 @@ struct TileRegs {
   float dv[4];
   u32 cv[4];
 };
+// Row of footprint pixel p: r = floor((p + 0.5) / w).  (p + 0.5) / w is at least 0.5 / w away from an integer and the product with
+// the hardware reciprocal (1 ulp) is off by less than p * 2^-21 / w, so for p < 2^20 the truncation gives the same r as a
+// correctly rounded 1 / w does.
+__device__ __forceinline__ float tile_inv_w(const int4 bb) { return __builtin_amdgcn_rcpf((float) bb.z); }
 __device__ __forceinline__ void tile_issue(const Cam& c, const Fast& f, const int4 bb, const int lane, TileRegs& tr) {
   const int npx = bb.z * bb.w;
   if (npx <= 0) return;
-  const float inv_w = 1.0f / (float) bb.z;
+  const float inv_w = tile_inv_w(bb);
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const int p = min(lane + 64 * j, npx - 1);
@@ -255,7 +288,7 @@ __device__ __forceinline__ float tile_commit(const Cam& c, const Map& m, const F
     reach = __uint_as_float(umax_(__float_as_uint(reach), __float_as_uint(pixel_reach(c, m, tr.dv[j]))));
   }
   if (npx > 256) {
-    const float inv_w = 1.0f / (float) bb.z;
+    const float inv_w = tile_inv_w(bb);
 #pragma unroll 1
     for (int p0 = 256 + lane; p0 < npx; p0 += 128) {
       float dv[2];
@@ -285,8 +318,8 @@ __device__ __forceinline__ float tile_commit(const Cam& c, const Map& m, const F
 // without a tile) take ONE wave-uniform fallback branch with direct gathers.
 template <int NB>
 __device__ __forceinline__ void tile_lookup(const Fast& f, const int cols, const int4 bb, const uint2* tile, const Proj4 (&P)[NB],
-                                            float (&d)[NB][4], u32 (&cpx)[NB][4]) {
-  u32 miss = 0;
+                                            const bool (&ok)[NB][4], float (&d)[NB][4], u32 (&cpx)[NB][4]) {
+  bool miss[NB][4], any_miss = false;  // predicates, not bits: they stay lane masks in scalar registers
   u32 li[NB][4];
 #pragma unroll
   for (int b = 0; b < NB; b++)
@@ -294,8 +327,10 @@ __device__ __forceinline__ void tile_lookup(const Fast& f, const int cols, const
     for (int k = 0; k < 4; k++) {
       const u32 lr = (u32) (P[b].row[k] - bb.y), lc = (u32) (P[b].col[k] - bb.x);
       const bool in = lr < (u32) bb.w && lc < (u32) bb.z;
-      li[b][k] = in ? lr * (u32) bb.z + lc : 0u;
-      if (!in && ((P[b].mask >> k) & 1u)) miss |= 1u << (b * 4 + k);
+      // a 24-bit multiply-add and a select, no branch: inside the footprint lr * w + lc < w * h <= kTileMaxPx, outside the product is not used
+      li[b][k] = in ? __umul24(lr, (u32) bb.z) + lc : 0u;
+      miss[b][k] = !in && ok[b][k];
+      any_miss = any_miss || miss[b][k];
     }
 #pragma unroll
   for (int b = 0; b < NB; b++)
@@ -305,12 +340,12 @@ __device__ __forceinline__ void tile_lookup(const Fast& f, const int cols, const
       d[b][k] = __uint_as_float(px.x);
       cpx[b][k] = px.y;
     }
-  if (__ballot(miss != 0)) {
+  if (__ballot(any_miss)) {
 #pragma unroll
     for (int b = 0; b < NB; b++)
 #pragma unroll
       for (int k = 0; k < 4; k++)
-        if ((miss >> (b * 4 + k)) & 1u) {
+        if (miss[b][k]) {
           const u32 pix = (u32) (__mul24(P[b].row[k], cols) + P[b].col[k]);  // miss implies the voxel is in the image
           const uint2 v = f.dcx[pix];
           d[b][k] = __uint_as_float(v.x);

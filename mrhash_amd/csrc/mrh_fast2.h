@@ -626,7 +626,10 @@ __device__ __forceinline__ void back_range(const Cam& c, const Map& m, const Tab
     // (convexity, +-1 px slack).  If d + trunc(d) + 1e-4 <= zmin for every valid footprint pixel, then
     // fl(d - pc.z) <= -trunc(d) for every voxel (1e-4 >> the rounding of the two sums), i.e. integrateDepthMapKernel
     // (vds.cu:1134-1145) updates nothing: the block, and therefore its stored summary, stay as they are.
-    const bool skip = bb.z != 0 && __uint_as_float(wave_max_u32(__float_as_uint(reach))) + 1e-4f <= zmin;  // wave-uniform
+    // "Every pixel" is one per-lane test and a ballot, not a max-reduction of `reach`: x -> fl(x + 1e-4) is monotone and
+    // `reach` is never NaN (pixel_reach returns 0, d + trunc(d) for d > 0, or FLT_MAX), so the wave's largest reach passes
+    // the test exactly when every lane's does.
+    const bool skip = bb.z != 0 && __ballot(!(reach + 1e-4f <= zmin)) == 0;  // wave-uniform
     float mn;
     u32 mx;
 #ifdef MRH_TRACE
@@ -642,7 +645,12 @@ __device__ __forceinline__ void back_range(const Cam& c, const Map& m, const Tab
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       MRH_TS(3);
-      tile_lookup<2>(f, c.cols, bb, tile, P, d, cpx);
+      bool ok[2][4];
+#pragma unroll
+      for (int b = 0; b < 2; b++)
+#pragma unroll
+        for (int k = 0; k < 4; k++) ok[b][k] = proj_ok<SPH>(c, P[b], k);
+      tile_lookup<2>(f, c.cols, bb, tile, P, ok, d, cpx);
       __builtin_amdgcn_wave_barrier();
       MRH_TS(4);
       u32 mnb = 0x7F7FFFFFu;  // bits of min |sdf| over weighted voxels: |x| >= 0, so unsigned order == float order, and
@@ -654,25 +662,28 @@ __device__ __forceinline__ void back_range(const Cam& c, const Map& m, const Tab
         u32 w[4] = {W[b].x, W[b].y, W[b].z, W[b].w};
         float ss[4] = {0.f, 0.f, 0.f, 0.f};
         if (MULTI) { ss[0] = Q[b].x; ss[1] = Q[b].y; ss[2] = Q[b].z; ss[3] = Q[b].w; }
-        const u32 mask = update_mask4(c, m, P[b], d[b]);
+        Sdf4 g;
+        bool upd[4];
+        update4(c, m, P[b], ok[b], d[b], g, upd);
+        const bool any = upd[0] || upd[1] || upd[2] || upd[3], all = upd[0] && upd[1] && upd[2] && upd[3];
 #ifdef MRH_TRACE
-        trace_upd += __popc(mask);
+        trace_upd += (u32) upd[0] + (u32) upd[1] + (u32) upd[2] + (u32) upd[3];
 #endif
-        blend4<SAFEDIV>(m, P[b], mask, d[b], cpx[b], s, w, ss);
+        blend4<SAFEDIV, MULTI>(m, g, upd, cpx[b], s, w, ss);  // !MULTI: ss[k] is read below for the voxels of `upd` only
         if (MULTI) {  // (sum_squared, rgbw) of this lane's voxels q * 4 + k for the variance check below
           W[b] = make_uint4(w[0], w[1], w[2], w[3]);
           Q[b] = make_float4(ss[0], ss[1], ss[2], ss[3]);
         }
-        if (mask) {
+        if (any) {
           ps[q] = make_float4(s[0], s[1], s[2], s[3]);
           pw[q] = make_uint4(w[0], w[1], w[2], w[3]);
-          if (mask == 0xF) {
+          if (all) {
             pq[q] = make_float4(ss[0], ss[1], ss[2], ss[3]);
           } else {
             float* pqs = (float*) (pq + q);
 #pragma unroll
             for (int k = 0; k < 4; k++)
-              if (mask & (1u << k)) pqs[k] = ss[k];
+              if (upd[k]) pqs[k] = ss[k];
           }
         }
 #pragma unroll

@@ -1,8 +1,18 @@
 #!/bin/bash
-# VALU instruction / activity counters of the bench kernels (own rocprofv3 pass, no tracing).  usage: pmc_valu.sh <tag> [lib.so]
-cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
-LIB=${2:-mrhash_amd/csrc/libmrhash_hip.so}
-OUT=gpurun_out/pmc_valu_${1:-x}; rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_BUSY_CYCLES --output-format csv -d $OUT/pmc_sq -o p -- python tools/bench_with_lib.py $LIB --steps 60 --warmup 10 --full --no-cpu > $OUT/log.txt 2>&1
-python tools/summarize_pmc.py $OUT | grep -A1 -E "k_back<true, false, false>|k_front<false, false>"
-rm -rf $OUT/pmc_sq
+# VALU / SALU instruction counters of the frame's two kernels per dispatch at the driver's command (bench.py --pmc-inner --steps 20
+# --warmup 5), one rocprofv3 --pmc pass of its own per library build, nothing traced beside it.  The counts are deterministic: this is
+# the check of every change to k_back's instruction stream (profiles/r07/README.md).
+#   usage: tools/pmc_valu.sh name1 [name2 ...]   (mrhash_amd/csrc/libmrhash_<name>.so; "hip" is the product build, others come from
+#   python -m mrhash_amd.build variant <name>)
+cd "$(dirname "$0")/.." || exit 1
+export TMPDIR=/tmp
+for n in "$@"; do
+  OUT=$(mktemp -d)
+  timeout -k 10 240 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAVES --output-format csv -d $OUT/pmc_sq -o p -- \
+    python tools/bench_with_lib.py mrhash_amd/csrc/libmrhash_$n.so --pmc-inner --steps 20 --warmup 5 > $OUT/log.txt 2>&1
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "## $n: rocprofv3 exit $rc"; tail -20 $OUT/log.txt; exit $rc; fi  # nothing more runs on the device after a failure
+  echo "## $n"
+  python tools/summarize_pmc.py $OUT | grep -A1 -E "k_back<|k_front<"
+  rm -rf $OUT
+done
