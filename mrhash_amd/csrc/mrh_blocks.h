@@ -273,7 +273,7 @@ int mrh_unpack_blocks(mrh_ctx* c, int mode, const mrh_block_record* records, uin
     HIP_TRY(c, hipMemcpyAsync(staged, records, (size_t) n * sizeof(mrh_block_record), hipMemcpyHostToDevice, s));
     d_rec = staged;
   }
-  if (!c->d_taken) HIP_TRY(c, hipMalloc((void**) &c->d_taken, sizeof(u32)));
+  if (!c->d_taken) HIP_TRY(c, dev_alloc(c, c->d_taken, sizeof(u32)));
   HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
   const size_t room = c->halo_upper + n, cap = room + room / 2;  // the halo list takes every record of the call behind its entries
   if (mode == MRH_UNPACK_HALO && room > c->halo_cap) {

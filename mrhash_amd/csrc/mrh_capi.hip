@@ -1,26 +1,16 @@
 // mrh_capi.hip — implementation of the C ABI (include/mrhash_hip.h) on top of the gfx950 kernels.
 //
-// Host side of the thin HIP layer: owns the device buffers, enqueues the per-frame kernel chain on one
-// stream with no host round trip, and only synchronises in the calls that hand data back.
+// Host side of the thin HIP layer: enqueues the per-frame kernel chain with no host round trip, and only synchronises in the
+// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the integrate paths, the splat, raycast
+// and normals glue.  The context and its lifetime: mrh_context.h; the copy pool: mrh_hostcopy.h; uploads, frame marks, peeks:
+// mrh_upload.h; extraction, scans, block I/O, RCCL: mrh_extract.h, mrh_points.h, mrh_blocks.h, mrh_comm.h.  One translation unit.
 // There is NO CPU fallback in this file: without a HIP device mrh_create fails with MRH_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <sys/mman.h>
-#if !defined(__HIP_DEVICE_COMPILE__)
-#include <immintrin.h>
-#define MRH_CPU_RELAX() _mm_pause()
-#else
-#define MRH_CPU_RELAX() ((void) 0)  // host code as the device pass sees it
-#endif
 
 #include <algorithm>
 #include <array>
-#include <atomic>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <tuple>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -28,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -50,597 +41,11 @@
 
 using namespace mrh;
 
-constexpr int kPipeRing = 6;  // = mrh::kListSets: frames in flight + 2
+#include "mrh_context.h"
+#include "mrh_hostcopy.h"
+#include "mrh_upload.h"
 
 namespace {
-
-thread_local std::string g_create_err;
-
-struct EvPair {
-  hipEvent_t a, b;
-};
-
-struct UpSlot {
-  void* h = nullptr;            // pinned staging
-  void* d = nullptr;            // device image
-  size_t cap = 0;
-  hipEvent_t copied = nullptr;  // H2D out of `h` done (copy stream)
-  bool copied_rec = false;
-  uint64_t last_seq = 0;        // newest frame_done mark of a frame that read `d` (0: none)
-};
-struct UpRing {
-  UpSlot s[3];
-  int cur = -1;                 // slot holding the current image; -1: none, or a caller's device pointer
-  hipStream_t stream = nullptr; // this ring's copy stream
-  hipEvent_t last_copy = nullptr;  // newest copy event of this ring
-  bool waited[2] = {false, false}; // ... has been waited for by {main, front} stream
-};
-
-// Host result buffer of the blocking calls (triangle soup, V / F / C): grow-only, never zero-filled, PINNED.
-// A device-to-host copy into pageable memory is pinned and unpinned by the runtime around every call, page by page: with
-// transparent huge pages behind the buffer that is cheap (tools/micro/d2h_paths.hip: 128 MB in 2.4 ms), with 4 KiB pages it
-// doubles the copy (30 MB of V / F / C: 0.57 -> 1.5 ms) — and which of the two a malloc'ed buffer gets depends on what the
-// process freed before (glibc raises its mmap threshold after the first large free; the next buffer then comes from the heap,
-// where MADV_HUGEPAGE does nothing for pages that already exist).  Pinned once, the copy runs at link speed every time, and a
-// kernel can write the buffer (k_copy_out).  The pinned memory is an anonymous 2 MiB-aligned mapping advised to huge pages,
-// touched, and registered (hipHostRegister): 1.5 ms for 36 MB where hipHostMalloc takes 5-9 ms (tools/micro/pinned_alloc_cost.hip)
-// — what a context's FIRST extraction pays.  If the registration is refused the mapping stays as a pageable buffer (dev == nullptr:
-// copies go through hipMemcpyAsync).
-template <typename T>
-struct HostVec {
-  T* p = nullptr;    // host pointer
-  T* dev = nullptr;  // the same memory as the device sees it (nullptr: not registered)
-  bool pin = true;   // false: a plain huge-page mapping the device never touches (V / C doubles, filled by the host's widening)
-  size_t n = 0, cap = 0;
-  size_t span = 0, head = 0;  // the mapping: its size and the bytes between its base and p
-  HostVec() = default;
-  HostVec(const HostVec&) = delete;
-  HostVec& operator=(const HostVec&) = delete;
-  ~HostVec() { release(); }
-  void release() {
-    if (!p) return;
-    if (dev) (void) hipHostUnregister((void*) p);
-    (void) munmap((void*) ((char*) p - head), span);
-    p = nullptr; dev = nullptr; cap = 0; span = 0; head = 0;
-  }
-  T* data() { return p; }
-  const T* data() const { return p; }
-  size_t size() const { return n; }
-  bool empty() const { return n == 0; }
-  void clear() { n = 0; }
-  const T& operator[](size_t i) const { return p[i]; }
-  bool pin_pending = false;  // mapped and faulted in by reserve_unpinned, not registered yet: the next resize_discard registers it
-  // the mapping alone: mmap + huge-page advice + first touch.  No HIP call — safe on a helper thread next to a frame loop (a
-  // hipHostRegister on another thread holds the runtime's lock for its whole 1-2 ms: round 6 measured the frame loop at a quarter
-  // of its rate with the registration on a helper thread)
-  void map_(const size_t count, const bool touch) {
-    release();
-    const size_t want = count + count / 8;  // head room: a map that grows a little keeps its buffer
-    const size_t bytes = ((want * sizeof(T) + (2u << 20) - 1) >> 21) << 21;
-    const size_t sp = bytes + (2u << 20);
-    void* m = mmap(nullptr, sp, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (m == MAP_FAILED) throw std::bad_alloc();
-    // the whole span is kept (the unaligned head stays untouched, i.e. unbacked): one munmap releases it
-    char* aligned = (char*) (((uintptr_t) m + (2u << 20) - 1) & ~(uintptr_t) ((2u << 20) - 1));
-    (void) madvise(aligned, bytes, MADV_HUGEPAGE);
-    // fault the pages in (as huge pages) before they are pinned; a buffer the device never sees is faulted in by whoever
-    // writes it first — the widening threads, side by side (47 MB of V / C at the driver's workload: zeroing them here, on one
-    // thread, was most of a context's first extraction) — unless the prewarm asks for it
-    if (touch) for (size_t o = 0; o < bytes; o += 4096) ((volatile char*) aligned)[o] = 0;
-    span = sp;
-    head = (size_t) (aligned - (char*) m);
-    p = (T*) aligned;
-    dev = nullptr;
-    cap = bytes / sizeof(T);
-  }
-  void register_() {
-    pin_pending = false;
-    void* d = nullptr;
-    const size_t bytes = cap * sizeof(T);
-    if (hipHostRegister((void*) p, bytes, hipHostRegisterDefault) == hipSuccess && hipHostGetDevicePointer(&d, (void*) p, 0) == hipSuccess && d) {
-      dev = (T*) d;
-    } else {
-      (void) hipGetLastError();
-      (void) hipHostUnregister((void*) p);
-      (void) hipGetLastError();
-      dev = nullptr;
-    }
-  }
-  // capacity for `count` elements, faulted in, registration left to the first resize_discard (helper thread: no HIP call)
-  void reserve_unpinned(const size_t count) {
-    if (count <= cap) return;
-    map_(count, true);
-    pin_pending = pin;
-    n = 0;
-  }
-  // contents are NOT preserved when the buffer grows
-  void resize_discard(size_t count) {
-    if (count > cap) {
-      map_(count, pin);
-      pin_pending = false;
-      if (pin) register_();
-    } else if (pin_pending) {
-      register_();
-    }
-    n = count;
-  }
-  void assign(const T* a, const T* b) {
-    resize_discard((size_t) (b - a));
-    if (n) memcpy(p, a, n * sizeof(T));
-  }
-};
-
-}  // namespace
-
-struct mrh_ctx {
-  mrh_params p;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  Cam cam;
-  Map map;
-  Tab tab;
-  bool has_camera = false;
-  bool spherical = false;
-  // images.  Host uploads (mrh_upload_depth / _rgb) go through a ring of three slots per image kind — pinned staging +
-  // device buffer — on a second stream, so the copy of frame N+1 overlaps the kernels of frame N; the frame's kernels
-  // wait for the newest copy event, a slot is rewritten only after the last frame that read it (frame_done event).
-  UpRing up_depth, up_rgb;
-  // A frame of host images is LAUNCHED one mrh_integrate late (round 5): by then its two transfers have completed and the frame's
-  // kernels need no cross-stream wait — a wait that is enqueued while its event is still pending costs the waiting stream ~6 us
-  // of idle time, and a host-fed frame had two of them in front of its 41 us of kernels.  mrh_integrate checks what it can,
-  // keeps {pose, image pointers, ring state} and returns; the next mrh_integrate — or whichever other entry point needs the map
-  // (ensure_ready) — runs the frame first, with those inputs swapped in.  MRH_DEFER_UPLOADS=0 launches at once.
-  struct DeferredFrame {
-    bool on = false;
-    int n_inval = 0;
-    Cam cam;
-    const float* d_depth = nullptr; const uint8_t* d_rgb = nullptr;
-    int depth_rows = 0, depth_cols = 0, rgb_rows = 0, rgb_cols = 0;
-    struct Ring { int cur; hipEvent_t last_copy; bool waited[2]; } ring[2];
-  } deferred;
-  int defer_uploads = 1;
-  bool copy_ready = false;             // copy stream and frame marks exist
-  hipEvent_t frame_done[8] = {};       // recorded behind the kernels that READ a frame's ring slots (front stream for a pipelined frame): slot reuse
-  hipEvent_t peek_done[8] = {};        // recorded on the main stream behind the k_report of a mark: what the non-blocking peeks query
-  uint64_t frame_seq = 1;
-  // pool level for the host without a read-back stall (mrh_peek_free_blocks): a 2-int D2H per frame into pinned memory
-  int* h_peek = nullptr;               // [8][8] pinned: ctr[0 .. 4] = free-list levels ... error flags per report
-  // grow-only device scratch of the extraction (0: block list / counts / per-voxel counts, 1: mesh post-process, 2: V / C / F):
-  // a mesh of a million triangles needs ~400 MB of temporaries, and hipMalloc + hipFree of those cost more than the kernels
-  void* arena[3] = {nullptr, nullptr, nullptr};
-  size_t arena_cap[3] = {0, 0, 0};
-  uint64_t peek_seq[8] = {};
-  bool peek_enabled = false;
-  const float* d_depth = nullptr;
-  const uint8_t* d_rgb = nullptr;
-  int depth_rows = 0, depth_cols = 0, rgb_rows = 0, rgb_cols = 0;
-  // scratch
-  u32* d_decision = nullptr;
-  u64* d_zbuf = nullptr;  // 2 * npix
-  size_t zbuf_n = 0;
-  // starve frames on the two-launch path (mrh_fast2.h: k_starve_z / k_starve_tail): two PAIRS of z-buffers, the tail launch of
-  // one starve frame puts the other pair back to "empty" for the next
-  u64* d_zfused = nullptr;  // 2 pairs x 2 x npix
-  size_t zfused_n = 0;
-  bool zfused_clean[2] = {false, false};
-  size_t zfused_clean_npix = 0;  // the image size the clean pairs were cleared for (a pair holds zbuf0 | zbuf1 at THAT size)
-  int zfused_next = 0;
-  bool starve_fused = true;  // MRH_STARVE_FUSED=0: the eight launches of rounds 1-5 (k_starve<0,1,2>, k_summarize_visible, k_free_lists)
-  bool starve_serial = false;  // MRH_STARVE_SERIAL=1: starve frames leave the pipeline (and keep the three fused launches)
-  uint64_t n_starve_fused = 0;
-  int4* d_realloc = nullptr;
-  int4* d_reint = nullptr;
-  int* d_flag = nullptr;
-  u64* d_upd_partials = nullptr;
-  u32* d_misc = nullptr;  // 4 words for k_get_voxel
-  float* d_rcp_w = nullptr;  // Fast::rcp_w
-  Fast fast;              // fast path buffers
-  // ---- pipelined frames (integrate_single_res_frame; MRH_PIPE=0: every frame serial, the two launches on the main stream) ----
-  // The front half of a frame (k_front<..., LAZY>) is launched on `stream_front`, its integration (k_back<..., LZ = 2>) on the
-  // main stream behind one event; the front stream never waits for the main one, so the front half of frame g + 1 runs next to
-  // the integration of frame g.  Up to kPipeRing - 1 frames are in flight, each with its own {depth, colour} image, lists,
-  // list-counter set and want stamps.  Everything that is not a pipelined frame meets the map only after k_reclaim.
-  int pipe = 1;
-  int pipe_grid = 1024;                     // workgroups of a pipelined integration: ONE resident generation (4 per CU x 256 CUs).  With 2048 the
-                                            // second generation competes with the front half's workgroups for the slots the first one frees: 37.3 against
-                                            // 34.8 us per frame (MRH_PIPE_GRID; the serial launch keeps 2048)
-  int pipe_uploads = 0;                     // MRH_PIPE_UPLOADS=1: pipeline frames whose images came through mrh_upload_* too
-  int pipe_period = 64;                     // the reclaim (and one serial frame) every so many pipelined frames; MRH_PIPE_PERIOD.  (32 until
-                                            // round 6: a period boundary costs the pipeline ~60 us, the zombies it bounds are also bounded by the
-                                            // pool test below (zombies <= pool / 8); 64 — the census period — gave +4 % at 100 steps, 128 no more)
-  bool pipe_always_wait = false;            // MRH_PIPE_ALWAYS_WAIT=1: a pipelined integration always carries its wait packet (A/B)
-  // the pipelining state (ensure_pipe_state: a context with `pipe` set, at its first single-resolution frame) — the front stream,
-  // its events, ring slots 1 .. kPipeRing - 1, the want stamps, h_levels and Fast::zlist
-  hipStream_t stream_front = nullptr;
-  hipEvent_t ev_front[kPipeRing] = {};
-  uint2* pipe_dcx[kPipeRing] = {};          // {cleaned depth, packed colour} of a frame (written by k_front), per ring slot; without the pipelining
-  size_t pipe_npix = 0;                     // state [0] alone, which every serial frame uses (ensure_frame_dcx)
-  int4* ring_vis[kPipeRing] = {}; int4* ring_bbox[kPipeRing] = {}; int4* ring_cfree[kPipeRing] = {}; float* ring_zmin[kPipeRing] = {};  // [0]: unused (ring_lists)
-  u32* want_ring = nullptr;                 // kPipeRing x slots stamps
-  int* h_levels = nullptr;                  // pinned {fine free-list level, zombies, sequence number of the last integration that started}
-  uint64_t pipe_seq = 0;                    // single-resolution frames issued (pipelined or not)
-  uint64_t pipe_base = 0;                   // every frame below this sequence number is known complete (host synchronised)
-  int lazy_run = 0;                         // pipelined frames since the last reclaim
-  bool zombies_possible = false;
-  bool last_frame_lazy = false;
-  bool flushed_since_frame = false;          // an entry point other than the per-frame ones ran since the last frame
-  int sync_streak = 0;
-  bool front_needs_sync = false;            // the main stream changed the table / free list behind the front stream's back
-  // the integration of the newest pipelined frame is enqueued by the NEXT mrh_integrate (or by whichever other entry point comes
-  // first): by then its front half has usually finished, the host sees that (hipEventQuery) and the main stream needs no
-  // cross-stream wait in front of the launch — such a wait costs ~6 us of idle main stream per frame on this runtime
-  struct PendingBack {
-    bool on = false;
-    Cam cam;
-    Fast f;
-    Lists L;
-    int set = 0, zero_set = 0, ring = 0, seq = 0;
-    u32 stamp = 0;
-    float thr = 0.f;
-    bool free_ = false, profile = false, safe_div = false, count_zombies = false, sph = false;
-    bool starve = false;  // a starve frame: behind the integration (which collects nothing) the three fused starve launches
-    EvPair ev = {nullptr, nullptr};
-    uint64_t report_seq = 0;  // frame mark whose pool report was written before this integration ran (refreshed behind it)
-  };
-  static constexpr int kPendMax = 3;
-  PendingBack pendq[kPendMax];            // oldest first
-  int npend = 0;
-  int pipe_defer = 1;                     // integrations kept back (MRH_PIPE_DEFER, 1 .. kPendMax - 1): the older a front half, the surer it has finished
-  uint64_t dbg_waits = 0;
-  double dbg_spin_us = 0, dbg_api_us = 0; uint64_t dbg_lazy_frames = 0;  // MRH_DEBUG: where the host's time in a pipelined frame goes
-  int4* d_cfree = nullptr;
-  float* d_cloud = nullptr; size_t cloud_n = 0;  // spherical camera: getDepth(cloud) image of the current frame (k_cloud_depth)
-  bool frame_general = false;       // this frame ran through the general kernels (mrh_kernels.h): GC by k_gc_identify / k_gc_free
-  bool fast_summaries_stale = false;  // single-resolution map: a general frame left Fast::summary behind
-  // LiDAR scans (mrh_points.h).  Nothing here is touched by mrh_reset: the counters are zero between scans, buckets_dirty covers a failed one
-  struct Lidar {
-    // ---- the cloud of the next scan
-    float* d_points = nullptr;        // owned copy (mrh_upload_points) ...
-    const float* d_points_cur = nullptr;  // ... or the caller's device pointer (mrh_set_points_device)
-    size_t points_cap = 0, num_points = 0;
-    float* d_normals = nullptr; size_t normals_cap = 0, num_normals = 0;  // one normal per point (mrh_upload_normals, mrh_estimate_normals)
-    bool have_cloud = false;          // a scan has been handed over (mrh_upload_points / mrh_set_points_device), n = 0 included
-    int layout_hint = 0;    // mrh_set_scan_layout / MRH_SCAN_ROW_LEN: > 0 points per row of the caller's organised scans, 0 find out (host clouds), < 0 none
-    int row_len = 0;        // ... of the CURRENT cloud (0: not organised, or not known)
-    uint64_t detect_n = 0;  // the look at a host cloud is repeated when the cloud's size changes and every 64th upload (a sensor keeps its layout;
-    int detect_len = 0, detect_age = 0;  // the look itself costs the calling thread ~20 us of cache misses, more than the order wins per scan)
-    int patch_log2 = 4;     // MRH_SCAN_PATCH_LOG2: columns (log2) of the beam patch a walk workgroup takes from an organised scan; 8 = 256 consecutive points
-    // ---- the sorted path (mrh_lidar.h): per-point counts, two (key, sdf) record buffers, the sort's scratch
-    u32* d_pt_counts = nullptr; u32* d_pt_offsets = nullptr; size_t pt_cap = 0;
-    u32* h_sorted_report = nullptr;   // pinned {hwm, last offset, last count, sequence}: the one report of a sorted scan
-    u32 sorted_seq = 0;
-    void* d_rec_keys[2] = {nullptr, nullptr}; float* d_rec_vals[2] = {nullptr, nullptr}; size_t rec_cap = 0, rec_key_bytes = 0;
-    void* d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
-    // ---- the voxel buckets (mrh_scan.h): per-voxel counters + block stamps (allocated with the first scan), stash, placed records, chunks
-    Scan buckets = {};
-    int use_buckets = 1;           // MRH_LIDAR_BUCKETS=0: scans through the sorted records of mrh_lidar.h (cross-check)
-    int buckets_scratch = 0;       // the counters and stamps — 0: not tried yet, 1: allocated, -1: do not fit / not applicable (sorted path)
-    bool buckets_dirty = false;    // a scan failed half way: the counters are cleared before the next one
-    size_t buckets_rec_cap = 0, buckets_wg_cap = 0;
-    u32* d_buckets_ctr = nullptr;  // two sets of SC_N counters: a scan zeroes the next one's
-    u32 buckets_seq = 0;
-    size_t buckets_lds_set = 0;
-  } lidar;
-  // 3DGS splat seeds (mrh_splat.h): sized for one (image shape, min pixel size)
-  size_t qt_cap = 0;  // potential nodes the device buffers below hold (regrow_all); it replaces the QTree once recorded here
-  QSum* d_qt_sums = nullptr; u32* d_qt_flags = nullptr; u32* d_qt_unc = nullptr; u64* d_qt_marks = nullptr; u64* d_qt_pos = nullptr;
-  mrh_splat_seed* d_qt_parked = nullptr; mrh_qtree_leaf* d_qt_leaves = nullptr;
-  // what the caller takes from a seeding call is written by its last launch straight into pinned host memory (a few hundred to a few
-  // thousand 20-byte seeds and two counters): one synchronisation, no transfer calls (they were two pageable read-backs, each behind
-  // a synchronisation of its own: ~35 of the call's 135 us)
-  mrh_splat_seed* h_qt_seeds = nullptr; size_t qt_seed_cap = 0;
-  u64* h_qt_out = nullptr;   // [0] totals (leaves | seeds << 32), [1] literal evaluations
-  u64* d_qt_misc = nullptr;  // [0] totals (leaves | seeds << 32), [1] uncertain-node counter (low word)
-  int qt_literal = 0;        // MRH_QTREE_LITERAL=1: every node error through the reference's summation order (cross-check)
-  uint32_t qt_last_literal = 0;
-  std::vector<mrh_qtree_leaf> qt_leaves;
-  uint64_t qt_n_leaves = 0;            // leaves of the last mrh_splat_seeds, still on the device (d_qt_leaves) until someone asks
-  bool qt_leaves_on_host = true;
-  int mr_fused = 1;          // MRH_MR_FUSED=0: multi-resolution maps always through the general kernels (mrh_kernels.h)
-  bool mr_next_general = true;    // the next multi-resolution frame must take the general path (frame 0 / after a starve frame / after an import)
-  bool mr_summaries_valid = false;  // fast.summary / summary_c describe every live block (the general kernels do not maintain them)
-  bool frame_fused_mr = false;
-  bool refill_flag_valid = false;  // d_flag holds the refill test for the next fused frame (taken by k_mr_tail)
-  int mesh_on_host = 0;      // MRH_MESH_HOST=1: mesh post-process with the host restatement instead of mrh_mesh.h
-  float* d_zmin = nullptr;   // per visible-list entry (Lists::zmin)
-  uint64_t fast_frames = 0;  // fast-path frames issued: parity selects the list-counter set
-  int frame_parity = 0;
-  u64* d_cnt_partials = nullptr;
-  int fused_grid = 2048;  // x 4 waves
-  int sweep_wgs_mr = 1024; // the same for multi-resolution maps (9x the descriptors); MRH_SWEEP_WGS_MR
-  int sweep_wgs = 128;    // descriptor-sweep workgroups appended to the allocation launch (k_front)
-  bool frame_gc_inline = false;
-  int integrate_grid = 1024;
-  int low_blocks_to_allocate = 0;
-  uint64_t num_blocks = 0, slots = 0, max_triangles = 0;
-  uint64_t frames = 0;
-  int pending = 0;           // sharded starve frames: 1 after pass 0, 2 after pass 1
-  int pending_max_frames = 0;
-  // mesh (host)
-  HostVec<mrh_triangle> tris;   // host copy of the soup: only when the caller of mrh_extract_triangles asks for it
-  std::vector<mrh_block_desc> tri_blocks;
-  std::vector<uint32_t> tri_counts;
-  // ... of the last extraction, still on the device (arena slot 0) until mrh_get_triangle_blocks asks
-  int tri_dev_n = 0;
-  const int4* d_tri_sorted = nullptr;
-  const u32* d_tri_counts = nullptr;
-  u64* h_mc = nullptr;  // pinned: triangle total of the extraction in flight
-  hipEvent_t ev_mc_total = nullptr;  // ... has landed
-  u32* d_mc_recs = nullptr; size_t mc_rec_cap = 0;  // corner records of the count pass (mrh_mc.h McRecords), grow-only
-  uint64_t mc_rec_fallbacks = 0;                    // extractions whose records did not fit (emitted by k_mc<emit> instead)
-  HostVec<double> V, C;
-  HostVec<int32_t> F;
-  // V and C cross the link in fp32 (k_stage_out) and are widened by the host while the rest is still on its way (widen_from_staging)
-  HostVec<float> V32, C32;     // pinned staging
-  HostVec<u32> stage_ctl;      // pinned: [0..5] {vertices, faces, epoch} as three u64, [16..] one flag word per 64 KiB chunk of V32, then of C32
-  u32 stage_epoch = 0;
-  void* mesh_clean_base = nullptr;  // arena slot 1 as the last extraction left it: the first mesh_clean_words words are 0xFFFFFFFF
-  size_t mesh_clean_words = 0;
-  // The host side of a context's FIRST extraction — four pinned mappings (mmap + first touch + hipHostRegister: ~0.9 ms for the
-  // 20 MB of a 0.5 M-triangle mesh) and the 24 MB of doubles the caller sees — used to be paid inside that call, after a
-  // synchronisation that told it the sizes: 2.8 ms where every later extraction takes 0.85, and a one-shot extractMesh (what
-  // every runner of the reference does) only ever makes the first.  A context that fuses frames will be asked for its mesh: at
-  // the end of its THIRD mrh_integrate — a context is still allocating and warming up there — those buffers are sized from the
-  // live blocks (64 vertices a block: twice what the rooms of the benchmarks yield, so a map that keeps growing still fits).
-  // The first extraction then finds its staging ready and runs like any other; if the estimate was short, it grows the
-  // buffers as before.  Done in the calling thread, once: a helper thread was built first (round 6) and slowed the frame loop
-  // by 8 % for as long as it was faulting pages in, at whichever frame it was started.  MRH_PREWARM=0 switches it off.
-  bool prewarm_on = true, prewarm_done = false;
-  uint64_t n_extractions = 0;
-  bool f64_link = false;       // MRH_MESH_F64_LINK=1: V / C widened on the device and copied as doubles (the round-3 path; A/B, tests)
-  // profiling
-  int profile = 0;
-  std::vector<EvPair> ev_pool;
-  std::vector<EvPair> ev_pending;
-  std::vector<EvPair> ev_pending_front;  // the allocation launch (k_front) of profiled fast-path frames
-  float sum_ms = 0.f, last_ms = 0.f;
-  uint64_t n_ms = 0;
-  float sum_front_ms = 0.f;
-  uint64_t n_front_ms = 0;
-  uint64_t prev_total_updated = 0, prev_inserted = 0, prev_freed = 0, total_compact = 0;
-  uint64_t last_triangles = 0;
-  // hash-table upkeep (mrh_kernels.h: k_table_census / k_rehash_*)
-  int census_period = 64;          // frames between two censuses; MRH_REHASH_PERIOD
-  int census_force = 0;            // MRH_REHASH_FORCE=1: every census rebuilds (tests)
-  uint64_t frames_since_census = 0;
-  bool table_dirty = false;        // bulk erase / insert since the last census (stream-out, import, drop): census before the next frame
-  // device error flags: `flags_seen` = union of everything taken off the device since create / reset (stats),
-  // `flags_deferred` = taken but not yet returned to the caller by mrh_sync, `flags_peeked` = already returned by a peek
-  u32 flags_seen = 0, flags_deferred = 0, flags_peeked = 0;
-  // multi-GPU block exchange
-  char* d_pack = nullptr; size_t pack_cap = 0;      // mrh_pack_blocks result (records)
-  mrh_triangle* d_soup = nullptr; size_t soup_cap = 0, soup_n = 0;  // triangle soup of the last extraction / run merge (mrh_get_triangles_device)
-  int4* d_halo = nullptr; size_t halo_cap = 0, halo_upper = 0;  // blocks brought in by MRH_UNPACK_HALO (upper bound of the device count)
-  u32* d_taken = nullptr;
-  // marching cubes timing (mrh_stats)
-  hipEvent_t mc_ev[4] = {};
-  float last_mc_count_ms = 0.f, last_mc_emit_ms = 0.f;
-  uint64_t last_mc_blocks = 0;
-  // MeshExtractor::merge_mesh_ (mrh_mesh_merge_begin / _end): the soups of the extractions in between, back to back
-  bool merge_on = false;
-  mrh_triangle* d_acc = nullptr; size_t acc_cap = 0, acc_n = 0;
-  // RCCL (mrh_comm.h): the communicator this context is attached to, exchange buffers, phase clocks
-  mrh_comm* comm = nullptr;
-  char* d_xsend = nullptr; size_t xsend_cap = 0;
-  char* d_xrecv = nullptr; size_t xrecv_cap = 0;
-  hipEvent_t comm_ev[5] = {};
-  mrh_comm_phases comm_phases = {};
-  std::vector<EvPair> comm_ev_pool, comm_ev_pending;
-  // raycasting (mrh_raycast.h): the images of mrh_raycast, grow-only — device [depth f32 | normals 3 x f32 | rgb 3 x u8] per
-  // pixel and the pinned host copy the caller reads
-  char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
-  char* h_ray = nullptr; size_t h_ray_cap = 0;
-  // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of
-  // every point, grow-only; two sets of counters, a scan's last launch zeroes the next one's
-  struct Normals {
-    NrmTab tab = {};
-    size_t cap = 0;                // points the scratch holds
-    u64* d_ctr = nullptr;          // [2][NC_N]
-    u32 seq = 0;
-    bool dirty = false;            // a call failed between its first and its last launch: table and counters are cleared first
-    int fold = 1;                  // MRH_NORMALS_FOLD=0: k_normals_accumulate<false> (A/B, tests)
-    u64* h_ctr = nullptr;          // pinned [NC_N]: the counters of the last mrh_estimate_normals, copied behind its kernels
-    mrh_normals_info info = {};    // ... as the caller sees them; `points` = 0 and info_pending = false: none
-    bool info_pending = false;     // h_ctr has not been folded into `info` yet
-    float* h_out = nullptr; size_t h_out_cap = 0;  // pinned: what mrh_get_normals hands out
-  } nrm;
-  std::string err;
-};
-
-static int comm_allreduce_zbuf(mrh_ctx* c, mrh::u64* buf, size_t n);  // mrh_comm.h
-static void comm_release(mrh_ctx* c);
-static bool comm_matches_sharding(const mrh_ctx* c, int* comm_rank, int* comm_world);
-
-namespace {
-
-int fail(mrh_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  else g_create_err = buf;
-  return code;
-}
-
-#define HIP_TRY(ctx, expr)                                                                                   \
-  do {                                                                                                       \
-    hipError_t e__ = (expr);                                                                                 \
-    if (e__ != hipSuccess) return fail(ctx, MRH_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-  } while (0)
-
-// device scratch that is released on every path out of a function (error returns included)
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void**) &p, n * sizeof(T)); }
-  operator T*() const { return p; }
-};
-
-// Grow-only device buffers of the context whose contents are NOT kept.  The old buffers are released before the new ones are
-// allocated (the peak is one buffer, not two), behind a drained stream unless the caller knows that nothing reads them
-// (sync = false), and `cap` is zero for as long as a pointer is null: an allocation that fails leaves "no buffer, capacity 0",
-// never a recorded capacity over a null pointer.  `members` grow together under the one capacity: all of them, or none.
-// Sizing — what is compared, head room, what else a grow resets — is the call site's.
-struct GrowMember {
-  void** p; size_t bytes;
-  template <typename T> GrowMember(T*& q, size_t b) : p((void**) &q), bytes(b) {}
-};
-int regrow_all(mrh_ctx* c, size_t& cap, const size_t cap_new, std::initializer_list<GrowMember> members, const bool sync = true) {
-  cap = 0;
-  if (sync) HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (const GrowMember& m : members) {
-    if (*m.p) HIP_TRY(c, hipFree(*m.p));
-    *m.p = nullptr;
-  }
-  for (const GrowMember& m : members) {
-    const hipError_t e = hipMalloc(m.p, m.bytes);
-    if (e == hipSuccess) continue;
-    for (const GrowMember& f : members) { if (*f.p) (void) hipFree(*f.p); *f.p = nullptr; }
-    return fail(c, MRH_ERR_DEVICE, "hipMalloc of %zu bytes failed: %s", m.bytes, hipGetErrorString(e));
-  }
-  cap = cap_new;
-  return MRH_OK;
-}
-// one buffer of `bytes` bytes recorded as `cap_new`, if `cap_new` does not fit in `cap`
-template <typename T>
-int regrow(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes, const bool sync = true) {
-  return cap_new <= cap ? MRH_OK : regrow_all(c, cap, cap_new, {{p, bytes}}, sync);
-}
-// ... whose first `keep_bytes` ARE kept (halo list, merge accumulator, exchange buffers): the new buffer first, the copy on the
-// context's stream, the old one released behind the drained stream; any step that fails leaves buffer and capacity as they were
-template <typename T>
-int regrow_keep(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes_new, const size_t keep_bytes) {
-  if (cap_new <= cap) return MRH_OK;
-  DevBuf<T> grown;  // released on an error return
-  HIP_TRY(c, hipMalloc((void**) &grown.p, bytes_new));
-  if (p && keep_bytes) HIP_TRY(c, hipMemcpyAsync(grown.p, p, keep_bytes, hipMemcpyDeviceToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  std::swap(p, grown.p);  // the old buffer goes with `grown`
-  cap = cap_new;
-  return MRH_OK;
-}
-// ... and a pinned host buffer the caller reads results from (the call that filled it blocked: no synchronisation), contents not kept
-template <typename T>
-int regrow_pinned(mrh_ctx* c, T*& p, size_t& cap, const size_t cap_new, const size_t bytes) {
-  if (cap_new <= cap) return MRH_OK;
-  cap = 0;
-  if (p) { (void) hipHostFree(p); p = nullptr; }
-  HIP_TRY(c, hipHostMalloc((void**) &p, bytes, hipHostMallocDefault));
-  cap = cap_new;
-  return MRH_OK;
-}
-
-uint64_t next_pow2(uint64_t v) {
-  uint64_t r = 1;
-  while (r < v) r <<= 1;
-  return r;
-}
-
-void free_all(mrh_ctx* c) {
-  if (!c) return;
-  (void) hipSetDevice(c->device);
-  for (UpRing* r : {&c->up_depth, &c->up_rgb})
-    if (r->stream) { (void) hipStreamSynchronize(r->stream); (void) hipStreamDestroy(r->stream); }
-  if (c->stream_front) (void) hipStreamSynchronize(c->stream_front);
-  if (c->stream) (void) hipStreamSynchronize(c->stream);
-  auto F = [](void* p) { if (p) (void) hipFree(p); };
-  F(c->want_ring); F(c->fast.zlist);
-  for (int i = 0; i < kPipeRing; i++) { F(c->pipe_dcx[i]); if (i) { F(c->ring_vis[i]); F(c->ring_bbox[i]); F(c->ring_cfree[i]); F(c->ring_zmin[i]); } if (c->ev_front[i]) (void) hipEventDestroy(c->ev_front[i]); }
-  if (c->h_levels) (void) hipHostFree(c->h_levels);
-  if (c->stream_front) { (void) hipStreamSynchronize(c->stream_front); (void) hipStreamDestroy(c->stream_front); }
-  F(c->tab.keys); F(c->tab.vals); F(c->tab.heap_fine); F(c->tab.heap_coarse); F(c->tab.desc_fine); F(c->tab.desc_coarse);
-  F(c->tab.pool); F(c->tab.compact); F(c->tab.ctr); F(c->tab.prof);
-  for (UpRing* r : {&c->up_depth, &c->up_rgb})
-    for (UpSlot& u : r->s) {
-      if (u.h) (void) hipHostFree(u.h);
-      F(u.d);
-      if (u.copied) (void) hipEventDestroy(u.copied);
-    }
-  for (hipEvent_t e : c->frame_done) if (e) (void) hipEventDestroy(e);
-  for (hipEvent_t e : c->peek_done) if (e) (void) hipEventDestroy(e);
-  if (c->h_peek) (void) hipHostFree(c->h_peek);
-  if (c->h_mc) (void) hipHostFree(c->h_mc);
-  if (c->lidar.h_sorted_report) (void) hipHostFree(c->lidar.h_sorted_report);
-  for (void* a : c->arena) if (a) (void) hipFree(a);
-  F(c->d_decision); F(c->d_zbuf); F(c->d_zfused); F(c->d_realloc); F(c->d_reint); F(c->d_flag);
-  F(c->d_upd_partials); F(c->d_misc); F(c->d_rcp_w); F(c->d_cfree); F(c->d_zmin); F(c->lidar.d_points); F(c->lidar.d_pt_counts); F(c->lidar.d_pt_offsets); F(c->lidar.d_rec_keys[0]); F(c->lidar.d_rec_keys[1]); F(c->lidar.d_rec_vals[0]); F(c->lidar.d_rec_vals[1]); F(c->lidar.d_sort_tmp); F(c->lidar.buckets.vcnt); F(c->lidar.buckets.bstamp); F(c->lidar.buckets.st_meta); F(c->lidar.buckets.st_sdf); F(c->lidar.buckets.st_grp); F(c->lidar.buckets.wgdesc); F(c->lidar.buckets.rec); F(c->lidar.buckets.chunks); F(c->lidar.d_buckets_ctr); F(c->fast.summary); F(c->fast.summary_c); F(c->fast.bbox); F(c->d_cnt_partials);
-  F(c->d_pack); F(c->d_halo); F(c->d_taken); F(c->d_cloud); F(c->lidar.d_normals); F(c->d_soup); F(c->d_mc_recs);
-  for (hipEvent_t e : c->mc_ev) if (e) (void) hipEventDestroy(e);
-  if (c->ev_mc_total) (void) hipEventDestroy(c->ev_mc_total);
-  comm_release(c);
-  F(c->d_xsend); F(c->d_xrecv); F(c->d_acc);
-  for (hipEvent_t e : c->comm_ev) if (e) (void) hipEventDestroy(e);
-  for (auto& e : c->comm_ev_pool) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
-  for (auto& e : c->comm_ev_pending) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
-  F(c->d_qt_sums); F(c->d_qt_flags); F(c->d_qt_unc); F(c->d_qt_marks); F(c->d_qt_pos); F(c->d_qt_parked); F(c->d_qt_leaves); F(c->d_qt_misc);
-  F(c->d_ray);
-  if (c->h_ray) (void) hipHostFree(c->h_ray);
-  F(c->nrm.tab.keys); F(c->nrm.tab.sums); F(c->nrm.tab.cell); F(c->nrm.tab.list); F(c->nrm.tab.pt_slot); F(c->nrm.tab.partial); F(c->nrm.d_ctr);
-  if (c->nrm.h_ctr) (void) hipHostFree(c->nrm.h_ctr);
-  if (c->nrm.h_out) (void) hipHostFree(c->nrm.h_out);
-  if (c->h_qt_seeds) (void) hipHostFree(c->h_qt_seeds);
-  if (c->h_qt_out) (void) hipHostFree(c->h_qt_out);
-  for (int i = 0; i < c->npend; i++) if (c->pendq[i].profile) c->ev_pool.push_back(c->pendq[i].ev);
-  c->npend = 0;
-  for (auto& e : c->ev_pool) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
-  for (auto& e : c->ev_pending) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
-  for (auto& e : c->ev_pending_front) { (void) hipEventDestroy(e.a); (void) hipEventDestroy(e.b); }
-  if (c->stream) (void) hipStreamDestroy(c->stream);
-}
-
-// (re)initialises every device structure to the empty map (voxel_data_structures.cpp:58-87 + ctor counters)
-int init_buffers(mrh_ctx* c) {
-  hipStream_t s = c->stream;
-  c->mr_next_general = true;
-  c->refill_flag_valid = false;
-  c->mr_summaries_valid = false;
-  c->fast_frames = 0;
-  if (c->stream_front) HIP_TRY(c, hipStreamSynchronize(c->stream_front));
-  for (int i = 0; i < c->npend; i++) if (c->pendq[i].profile) c->ev_pool.push_back(c->pendq[i].ev);
-  c->npend = 0;  // a reset map has nothing left to integrate
-  c->pipe_seq = 0;
-  c->pipe_base = 0;
-  c->lazy_run = 0;
-  c->zombies_possible = false;
-  c->front_needs_sync = false;
-  if (c->h_levels) { c->h_levels[0] = (int) c->num_blocks - 1; c->h_levels[1] = 0; c->h_levels[2] = -1; }
-  if (c->want_ring) HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), s));
-  const Tab& t = c->tab;
-  k_init_table<<<1024, 256, 0, s>>>(t.keys, c->slots);
-  k_init_heap<<<1024, 256, 0, s>>>(t.heap_fine, (u32) c->num_blocks, getenv("MRH_DEBUG_HEAP_DESCENDING") ? 1 : 0);
-  HIP_TRY(c, hipMemsetAsync(t.vals, 0, c->slots * sizeof(u32), s));
-  HIP_TRY(c, hipMemsetAsync(t.desc_fine, 0, c->num_blocks * sizeof(int4), s));
-  if (t.multi_res) HIP_TRY(c, hipMemsetAsync(t.desc_coarse, 0, c->num_blocks * 8 * sizeof(int4), s));
-  HIP_TRY(c, hipMemsetAsync(t.pool, 0, c->num_blocks * (size_t) kFineBytes, s));
-  int h_ctr[CTR_COUNT];
-  memset(h_ctr, 0, sizeof h_ctr);
-  h_ctr[CTR_HEAP_FINE] = (int) c->num_blocks - 1;  // voxel_data_structures.cuh:91-92
-  h_ctr[CTR_HEAP_COARSE] = -1;                     // :94-95
-  HIP_TRY(c, hipMemcpyAsync(t.ctr, h_ctr, sizeof h_ctr, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemsetAsync(t.prof, 0, PROF_COUNT * sizeof(u64), s));
-  HIP_TRY(c, hipMemsetAsync(c->d_upd_partials, 0, (size_t) c->integrate_grid * sizeof(u64), s));
-  HIP_TRY(c, hipMemsetAsync(c->d_cnt_partials, 0, (size_t) 32768 * 4 * sizeof(u64), s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  c->frames = 0;
-  c->frames_since_census = 0;
-  c->table_dirty = false;
-  c->flags_seen = c->flags_deferred = c->flags_peeked = 0;
-  c->halo_upper = 0;
-  c->prev_total_updated = c->prev_inserted = c->prev_freed = c->total_compact = 0;
-  c->sum_ms = c->last_ms = 0.f;
-  c->n_ms = 0;
-  c->sum_front_ms = 0.f;
-  c->n_front_ms = 0;
-  c->tris.clear(); c->V.clear(); c->C.clear(); c->F.clear();
-  c->last_triangles = 0;
-  return MRH_OK;
-}
 
 int drain_events(mrh_ctx* c) {
   for (auto& e : c->ev_pending) {
@@ -713,11 +118,9 @@ int ensure_device(mrh_ctx* c, const char* who) {
   if (e != hipSuccess) return fail(c, MRH_ERR_DEVICE, "%s: hipSetDevice failed: %s", who, hipGetErrorString(e));
   return MRH_OK;
 }
-int strict_point(mrh_ctx* c);
 // every entry point except the per-frame ones (setters, mrh_integrate, the non-blocking peeks): behind the pipelined frames issued
 // so far, the zombies nobody wanted leave the table, so that whatever the call reads, changes or waits for is exactly the map two
 // serial launches per frame would have left
-int flush_deferred(mrh_ctx* c);
 int ensure_ready(mrh_ctx* c, const char* who) {
   int rc = ensure_device(c, who);
   if (rc) return rc;
@@ -734,7 +137,7 @@ int ensure_ready(mrh_ctx* c, const char* who) {
 enum HMcSlot { HMC_TRIANGLES = 0, HMC_RECORDS = 1, HMC_VERTICES = 2, HMC_FACES = 3, HMC_COMPACT = 4, HMC_SLOTS = 8 };
 int ensure_h_mc(mrh_ctx* c) {
   if (c->h_mc) return MRH_OK;
-  HIP_TRY(c, hipHostMalloc((void**) &c->h_mc, HMC_SLOTS * sizeof(u64), hipHostMallocDefault));
+  HIP_TRY(c, pinned_alloc(c, c->h_mc, HMC_SLOTS * sizeof(u64)));
   memset(c->h_mc, 0, HMC_SLOTS * sizeof(u64));
   return MRH_OK;
 }
@@ -928,6 +331,9 @@ int starve_and_tail(mrh_ctx* c, int max_num_frames) {
 }  // namespace
 
 #include "mrh_extract.h"
+#include "mrh_points.h"
+#include "mrh_blocks.h"
+#include "mrh_comm.h"
 
 extern "C" {
 
@@ -963,180 +369,18 @@ const char* mrh_last_error(const mrh_ctx* ctx) { return ctx ? ctx->err.c_str() :
 
 int mrh_create(const mrh_params* p, mrh_ctx** out) {
   if (!p || !out) return fail(nullptr, MRH_ERR_INVALID_ARG, "mrh_create: null argument");
-  if (p->abi_version != MRH_ABI_VERSION) return fail(nullptr, MRH_ERR_INVALID_ARG, "mrh_create: abi_version mismatch");
-  if (!(p->virtual_voxel_size > 0.f)) return fail(nullptr, MRH_ERR_INVALID_ARG, "mrh_create: virtual_voxel_size must be > 0");
-  if (!(p->sdf_truncation >= 0.f) || !(p->sdf_truncation_scale >= 0.f))
-    return fail(nullptr, MRH_ERR_INVALID_ARG, "mrh_create: sdf_truncation and sdf_truncation_scale must be >= 0");
-  if (p->voxel_extents_scale != 0 && p->voxel_extents_scale != 1)
-    return fail(nullptr, MRH_ERR_UNSUPPORTED, "mrh_create: voxel_extents_scale != 1 is incoherent in the reference (vhu.cuh:90-92 vs 138-140)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, MRH_ERR_NO_DEVICE, "mrh_create: no HIP device visible");
-  if (p->device_id < 0 || p->device_id >= ndev) return fail(nullptr, MRH_ERR_INVALID_ARG, "mrh_create: device_id %d out of range (%d devices)", p->device_id, ndev);
-  if (p->shard_count > 1 && (p->shard_rank < 0 || p->shard_rank >= p->shard_count))
-    return fail(nullptr, MRH_ERR_INVALID_ARG, "mrh_create: shard_rank out of range");
-
+  int rc = create_checks(p);
+  if (rc) return rc;
   mrh_ctx* c = new mrh_ctx();
-  c->p = *p;
-  if (c->p.integration_weight_max == 0) c->p.integration_weight_max = 255;
-  if (c->p.voxel_extents_scale == 0) c->p.voxel_extents_scale = 1;
-  if (c->p.shard_count < 1) c->p.shard_count = 1;
-  c->device = p->device_id;
-  memset(&c->tab, 0, sizeof c->tab);
-  memset(&c->cam, 0, sizeof c->cam);
-#define CREATE_TRY(expr)                                                                                         \
-  do {                                                                                                           \
-    hipError_t e__ = (expr);                                                                                     \
-    if (e__ != hipSuccess) {                                                                                     \
-      fail(nullptr, MRH_ERR_DEVICE, "mrh_create: %s failed: %s", #expr, hipGetErrorString(e__));                 \
-      free_all(c);                                                                                               \
-      delete c;                                                                                                  \
-      return MRH_ERR_DEVICE;                                                                                     \
-    }                                                                                                            \
-  } while (0)
-  CREATE_TRY(hipSetDevice(c->device));
-  CREATE_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-
-  // capacities: geowrapper.cpp:37-54 when not given explicitly
-  size_t free_b = 0, total_b = 0;
-  CREATE_TRY(hipMemGetInfo(&free_b, &total_b));
-  const double to_alloc = (double) free_b * 0.70;  // SDFBlocks_ratio
-  c->num_blocks = p->num_sdf_blocks ? p->num_sdf_blocks : (uint64_t) ((to_alloc * 0.70) / (12.0 * 512.0));
-  if (c->num_blocks >= (1ull << 28)) c->num_blocks = (1ull << 28) - 1;  // 31-bit coarse unit ids
-  c->max_triangles = p->max_triangles ? p->max_triangles : (uint64_t) ((to_alloc * 0.25) / 72.0);
-  c->slots = next_pow2(p->hash_slots ? p->hash_slots : 4 * c->num_blocks);
-  if (c->slots < 1024) c->slots = 1024;
-  c->low_blocks_to_allocate = (int) ((float) c->num_blocks * 0.1f);  // voxel_data_structures.cuh:57-61
-
-  Tab& t = c->tab;
-  t.slot_mask = (u32) (c->slots - 1);
-  t.max_probe = 512;
-  t.cap_blocks = (u32) c->num_blocks;
-  t.multi_res = p->sdf_var_threshold > 0.f ? 1u : 0u;
-  CREATE_TRY(hipMalloc((void**) &t.keys, c->slots * sizeof(u64)));
-  CREATE_TRY(hipMalloc((void**) &t.vals, c->slots * sizeof(u32)));
-  CREATE_TRY(hipMalloc((void**) &t.heap_fine, (c->num_blocks + 1) * sizeof(u32)));
-  CREATE_TRY(hipMalloc((void**) &t.desc_fine, c->num_blocks * sizeof(int4)));
-  if (t.multi_res) {
-    CREATE_TRY(hipMalloc((void**) &t.heap_coarse, (c->num_blocks * 8 + 9) * sizeof(u32)));
-    CREATE_TRY(hipMalloc((void**) &t.desc_coarse, c->num_blocks * 8 * sizeof(int4)));
-    CREATE_TRY(hipMalloc((void**) &c->d_realloc, c->num_blocks * sizeof(int4)));
-    CREATE_TRY(hipMalloc((void**) &c->d_reint, c->num_blocks * sizeof(int4)));
+  if (!(rc = size_map(c, p)) && !(rc = alloc_map(c)) && !(rc = probe_arithmetic(c))) {
+    read_switches(c);
+    rc = init_buffers(c);
   }
-  CREATE_TRY(hipMalloc((void**) &t.pool, c->num_blocks * (size_t) kFineBytes));
-  CREATE_TRY(hipMalloc((void**) &t.compact, c->num_blocks * (t.multi_res ? 9 : 1) * sizeof(int4)));
-  CREATE_TRY(hipMalloc((void**) &c->d_decision, c->num_blocks * (t.multi_res ? 9 : 1) * sizeof(u32)));
-  CREATE_TRY(hipMalloc((void**) &t.ctr, CTR_COUNT * sizeof(int)));
-  CREATE_TRY(hipMalloc((void**) &t.prof, PROF_COUNT * sizeof(u64)));
-  CREATE_TRY(hipMalloc((void**) &c->d_flag, sizeof(int)));
-  CREATE_TRY(hipMalloc((void**) &c->d_misc, 4 * sizeof(u32)));
-  CREATE_TRY(hipMalloc((void**) &c->d_upd_partials, (size_t) c->integrate_grid * sizeof(u64)));
-  CREATE_TRY(hipMalloc((void**) &c->d_cnt_partials, (size_t) 32768 * 4 * sizeof(u64)));  // max MRH_FUSED_GRID
-  memset(&c->fast, 0, sizeof c->fast);
-  CREATE_TRY(hipMalloc((void**) &c->fast.summary, c->num_blocks * sizeof(uint2)));
-  c->fast.zlist_cap = (u32) c->num_blocks;
-  if (const char* g = getenv("MRH_ZLIST_CAP")) { const int v = atoi(g); if (v > 0 && (uint64_t) v < c->num_blocks) c->fast.zlist_cap = (u32) v; }
-  const size_t list_cap = c->num_blocks * (t.multi_res ? 9 : 1);  // visible / free lists may hold coarse units, too
-  CREATE_TRY(hipMalloc((void**) &c->fast.bbox, list_cap * sizeof(int4)));
-  if (t.multi_res) CREATE_TRY(hipMalloc((void**) &c->fast.summary_c, c->num_blocks * 8 * sizeof(uint2)));
-#ifdef MRH_TRACE
-  CREATE_TRY(hipMalloc((void**) &c->fast.trace, c->num_blocks * 8 * sizeof(u64)));
-  CREATE_TRY(hipMemset(c->fast.trace, 0, c->num_blocks * 8 * sizeof(u64)));
-#endif
-  CREATE_TRY(hipMalloc((void**) &c->d_cfree, list_cap * sizeof(int4)));
-  CREATE_TRY(hipMalloc((void**) &c->d_zmin, list_cap * sizeof(float)));
-#undef CREATE_TRY
-
-  Map& m = c->map;
-  m.vs = p->virtual_voxel_size;
-  m.trunc = p->sdf_truncation;
-  m.trunc_scale = p->sdf_truncation_scale;
-  m.var_threshold = p->sdf_var_threshold;
-  m.mc_threshold = p->marching_cubes_threshold;
-  m.weight_sample = p->integration_weight_sample & 0xFF;
-  m.weight_max = c->p.integration_weight_max & 0xFF;
-  m.min_weight_threshold = p->min_weight_threshold;
-  m.shard_rank = c->p.shard_rank;
-  m.shard_count = c->p.shard_count;
-  m.shard_chunk_log2 = (p->shard_chunk_log2 > 0 && p->shard_chunk_log2 < 16) ? p->shard_chunk_log2 : 3;
-  {  // where is voxel -> block an arithmetic shift?  (mrh_device.h: world_to_block_fast)
-    const u32 init = 1u << 23;
-    u32 first_bad = 0;
-    if (hipMemcpy(c->d_misc, &init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) first_bad = 1;
-    k_block_shift_limit<<<(1 << 23) / 256, 256, 0, c->stream>>>(m.vs, c->d_misc);
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&first_bad, c->d_misc, sizeof first_bad, hipMemcpyDeviceToHost) != hipSuccess) first_bad = 1;
-    int lim = 1;
-    while ((u32) (lim << 1) <= first_bad && lim < (1 << 22)) lim <<= 1;  // largest power of two <= first mismatch
-    m.block_shift_limit = first_bad <= 1 ? 0 : lim;
-    if (getenv("MRH_DEBUG")) fprintf(stderr, "[mrhash_hip] voxel->block is a shift for |v| < %d (first mismatch at %u, voxel size %g)\n", m.block_shift_limit, first_bad, (double) m.vs);
-  }
-
-  {  // correctly rounded reciprocals for the short divisions of the running mean (mrh_device.h: div_cr)
-    auto rn_reciprocal = [](float b) {  // fp64 quotient, then the nearest of the three neighbouring floats (b * c is exact in fp64)
-      const float c0 = (float) (1.0 / (double) b);
-      float best = c0;
-      double err = std::fabs(1.0 - (double) c0 * (double) b);
-      for (float t : {std::nextafter(c0, 0.f), std::nextafter(c0, INFINITY)}) {
-        const double e = std::fabs(1.0 - (double) t * (double) b);
-        if (e < err) { err = e; best = t; }
-      }
-      return best;
-    };
-    // weight sums: the kernels use v_rcp_f32 + one Newton step; for the integers 1 .. 510 that must be RN(1 / w)
-    std::vector<float> dev(kRcpWeightEntries, 0.f);
-    bool ok = hipMalloc((void**) &c->d_rcp_w, dev.size() * sizeof(float)) == hipSuccess;
-    if (ok) {
-      k_rcp_weights<<<(kRcpWeightEntries + 255) / 256, 256, 0, c->stream>>>(c->d_rcp_w);
-      ok = hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(dev.data(), c->d_rcp_w, dev.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    int w_bad = ok ? 0 : 1;
-    for (int w = 1; ok && w <= 510; w++) w_bad += dev[w] != rn_reciprocal((float) w);
-    m.wsum_two_steps = w_bad ? 1 : 0;
-    const float half_vs = m.vs / 2;
-    m.r_half_vs = rn_reciprocal(half_vs);
-    u32 bad = 1;
-    if (hipMemset(c->d_misc, 0, sizeof(u32)) == hipSuccess) {
-      k_check_div_cr<<<4096, 256, 0, c->stream>>>(half_vs, m.r_half_vs, c->d_misc);
-      if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&bad, c->d_misc, sizeof bad, hipMemcpyDeviceToHost) != hipSuccess) bad = 1;
-    }
-    m.half_vs_two_steps = bad ? 1 : 0;
-    if (const char* g = getenv("MRH_SAFE_DIV")) { if (atoi(g)) m.half_vs_two_steps = 1; }  // force the fallback instantiation (tests)
-    if (getenv("MRH_DEBUG")) fprintf(stderr, "[mrhash_hip] division by vs / 2 with one residual step: %u mismatches over the working range -> %s; refined reciprocals of the weight sums: %d not correctly rounded\n", bad, bad ? "two steps" : "one step", w_bad);
-  }
-
-  if (const char* g = getenv("MRH_FUSED_GRID")) {  // tuning knob: workgroups (x4 waves) of the fused integrate kernel
-    const int v = atoi(g);
-    if (v > 0 && v <= 32768) c->fused_grid = v;
-  }
-  if (const char* g = getenv("MRH_DEFER_UPLOADS")) c->defer_uploads = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_PIPE")) c->pipe = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_STARVE_FUSED")) c->starve_fused = atoi(g) != 0;
-  c->starve_serial = getenv("MRH_STARVE_SERIAL") != nullptr;
-  c->pipe_always_wait = getenv("MRH_PIPE_ALWAYS_WAIT") != nullptr;
-  if (const char* g = getenv("MRH_PREWARM")) c->prewarm_on = atoi(g) != 0;
-  if (const char* g = getenv("MRH_PIPE_GRID")) { const int v = atoi(g); if (v > 0 && v <= 32768) c->pipe_grid = v; }
-  if (const char* g = getenv("MRH_PIPE_DEFER")) { const int v = atoi(g); if (v >= 1 && v < mrh_ctx::kPendMax) c->pipe_defer = v; }
-  if (const char* g = getenv("MRH_PIPE_UPLOADS")) c->pipe_uploads = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_PIPE_PERIOD")) { const int v = atoi(g); if (v > 0) c->pipe_period = v; }
-  if (const char* g = getenv("MRH_SWEEP_WGS")) { const int v = atoi(g); if (v > 0 && v <= 4096) c->sweep_wgs = v; }
-  if (const char* g = getenv("MRH_MESH_HOST")) c->mesh_on_host = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_MESH_F64_LINK")) c->f64_link = atoi(g) != 0;
-  c->V.pin = c->C.pin = c->f64_link;  // fp32 link: the doubles are written by the host only
-  if (const char* g = getenv("MRH_QTREE_LITERAL")) c->qt_literal = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_MR_FUSED")) c->mr_fused = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_SCAN_ROW_LEN")) c->lidar.layout_hint = atoi(g);
-  if (const char* g = getenv("MRH_SCAN_PATCH_LOG2")) { const int v = atoi(g); if (v >= 0 && v <= 8) c->lidar.patch_log2 = v; }
-  if (const char* g = getenv("MRH_LIDAR_BUCKETS")) c->lidar.use_buckets = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_NORMALS_FOLD")) c->nrm.fold = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_SCAN_SEQ_START")) c->lidar.buckets_seq = (u32) strtoul(g, nullptr, 0);  // tests: scans next to the wrap of the block stamps
-  if (const char* g = getenv("MRH_REHASH_PERIOD")) { const int v = atoi(g); if (v > 0) c->census_period = v; }
-  if (const char* g = getenv("MRH_REHASH_FORCE")) c->census_force = atoi(g) ? 1 : 0;
-  if (const char* g = getenv("MRH_REHASH_OFF")) { if (atoi(g)) c->census_period = -1; }  // no upkeep at all (tests: shows what it prevents)
-  if (const char* g = getenv("MRH_SWEEP_WGS_MR")) { const int v = atoi(g); if (v > 0 && v <= 4096) c->sweep_wgs_mr = v; }
-  int rc = init_buffers(c);
-  if (rc != MRH_OK) {
-    g_create_err = c->err;
+  if (rc) {  // the one failure path: whatever the stages allocated is in the ledger
+    g_create_err = "mrh_create: " + c->err;
     free_all(c);
     delete c;
+    (void) hipGetLastError();  // reported above: the next context's launch checks must not find it
     return rc;
   }
   // identity pose; camera must be set by the caller (geowrapper.cpp:80 installs a 1x1 placeholder)
@@ -1233,448 +477,6 @@ int mrh_set_pose(mrh_ctx* c, const float R[9], const float t[3]) {
 
 namespace {
 
-// Host copy into pinned staging with non-temporal stores: the destination is read next by the DMA engine, not by this
-// core, so write-allocating it through the cache only costs bandwidth (tools/micro/staging_copy.hip: 1.2 MB in 28.5 us
-// vs 40.9 us with memcpy, cold pageable source).
-#if !defined(__HIP_DEVICE_COMPILE__)
-__attribute__((target("avx2"))) void copy_streaming_avx2(void* dst, const void* src, size_t n) {
-  const __m256i* s = (const __m256i*) src;
-  __m256i* d = (__m256i*) dst;  // pinned allocations are page-aligned
-  const size_t v = n / 32;
-  for (size_t i = 0; i < v; i++) _mm256_stream_si256(d + i, _mm256_loadu_si256(s + i));
-  _mm_sfence();
-  if (n & 31) memcpy((char*) dst + v * 32, (const char*) src + v * 32, n & 31);
-}
-// floats -> doubles with non-temporal stores (the doubles are read by the caller later, not by this core)
-__attribute__((target("avx2"))) void widen_floats_avx2(double* dst, const float* src, size_t n) {
-  const size_t v = n / 8;
-  for (size_t i = 0; i < v; i++) {
-    const __m256 f = _mm256_loadu_ps(src + i * 8);
-    _mm256_stream_pd(dst + i * 8, _mm256_cvtps_pd(_mm256_castps256_ps128(f)));
-    _mm256_stream_pd(dst + i * 8 + 4, _mm256_cvtps_pd(_mm256_extractf128_ps(f, 1)));
-  }
-  _mm_sfence();
-  for (size_t i = v * 8; i < n; i++) dst[i] = (double) src[i];
-}
-void widen_floats(double* dst, const float* src, size_t n) {
-  static const bool avx2 = __builtin_cpu_supports("avx2");
-  if (avx2 && ((uintptr_t) dst & 31) == 0) widen_floats_avx2(dst, src, n);
-  else for (size_t i = 0; i < n; i++) dst[i] = (double) src[i];
-}
-void copy_chunk(void* dst, const void* src, size_t n) {
-  static const bool avx2 = __builtin_cpu_supports("avx2");
-  if (avx2 && n >= (64u << 10) && ((uintptr_t) dst & 31) == 0) copy_streaming_avx2(dst, src, n);
-  else memcpy(dst, src, n);
-}
-
-// The setter's copy of a 640x480 frame (1.2 MB depth + 0.9 MB colour) is what bounds the host-input path: one core moves
-// it at ~28 GB/s with streaming stores, 75 us per frame against 45 us of GPU work.  A small pool of helper threads shares
-// every copy (128 KiB chunks handed out by an atomic counter; the calling thread works too).  The helpers spin for a short
-// while after a job, so that in a frame loop the next upload finds them awake, and sleep on a condition variable
-// otherwise.  One pool per process, started by the first large upload, MRH_COPY_THREADS=0 turns it off.
-struct CopyPool {
-  static constexpr size_t kChunk = 128u << 10;
-  struct Job {
-    std::atomic<char*> dst{nullptr}; std::atomic<const char*> src{nullptr}; std::atomic<size_t> bytes{0}, nchunks{0};
-    // widening jobs (widen_from_staging): two parts of `bytes` bytes of floats each, chunk i < nchunks / 2 belongs to part 0;
-    // a chunk is taken up when its flag word equals `epoch` (flags == nullptr: at once)
-    std::atomic<int> widen{0};
-    std::atomic<char*> dst2{nullptr}; std::atomic<const char*> src2{nullptr};
-    std::atomic<const volatile uint32_t*> flags{nullptr}, flags2{nullptr};
-    std::atomic<uint32_t> epoch{0};
-  };
-  static constexpr size_t kWidenChunk = 64u << 10;  // = kStageChunk: bytes of floats per flag
-  static constexpr size_t kMaxStates = 1u << 16;    // chunks of one widening job that carry a state (beyond: the job waits for every helper)
-  std::atomic<int> abort_widen{0};
-  std::atomic<int64_t> spin_until_ns{0};  // helpers do not go to sleep before this time (widen_prewake)
-  static int64_t now_ns() { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-  std::mutex m;
-  std::condition_variable cv;
-  std::vector<std::thread> threads;
-  std::atomic<uint64_t> generation{0};  // bumped once per job, after the job's tickets are out
-  // Chunk tickets carry the job they belong to: (generation << 32) | next chunk.  A helper that saw generation g and was
-  // descheduled can only ever claim a chunk of job g, and only while job g is unfinished (an unclaimed chunk of g exists):
-  // it can neither consume a ticket of a later job nor count a chunk into its `done`.  The descriptor of job g lives in
-  // jobs[g & 1], which is rewritten only by job g + 2, i.e. after g and g + 1 have both completed.
-  std::atomic<uint64_t> ticket{0};
-  std::atomic<size_t> done{0};
-  std::atomic<int> sleepers{0};
-  // A WIDENING job does not wait for its helpers (round 5): every chunk has a state {0 not done, 2 done}, and when the tickets
-  // have run out the submitting thread REDOES whatever is not done after a short grace — the bytes are the same whoever writes
-  // them ((double) (float) of pinned staging that nothing rewrites meanwhile) —, so a helper that claimed a chunk and then lost
-  // its core costs the call one chunk of work instead of the scheduler's time slice (tools/stress_extract.py: tail of hundreds of
-  // ms with the host oversubscribed).  Such a straggler may still be reading the staging and writing the doubles after the call
-  // has returned: `inflight` counts the helpers between "about to claim" and "finished", and whoever is about to rewrite the
-  // staging, release or regrow the arrays, or publish another job waits for it to reach zero first (quiesce()).
-  // Upload jobs (copy()) keep waiting for every chunk: their source is the CALLER's buffer, which is free on return.
-  std::atomic<int> inflight{0};
-  std::unique_ptr<std::atomic<uint8_t>[]> state{new std::atomic<uint8_t>[kMaxStates]};
-  std::atomic<uint64_t> redone{0};  // chunks the submitting thread redid (MRH_DEBUG / tools/stress_extract.py)
-  Job jobs[2];
-  bool started = false;
-
-  void quiesce() {
-    while (inflight.load(std::memory_order_seq_cst) != 0) MRH_CPU_RELAX();
-  }
-  // claims the next chunk of job g; false: none left (or the tickets belong to another job)
-  bool claim(const uint64_t g, const Job& j, size_t& i) {
-    uint64_t cur = ticket.load(std::memory_order_acquire);
-    for (;;) {
-      if ((cur >> 32) != (g & 0xFFFFFFFFull)) return false;  // another job's tickets: not ours to take
-      i = (size_t) (cur & 0xFFFFFFFFull);
-      if (i >= j.nchunks.load(std::memory_order_relaxed)) return false;
-      if (ticket.compare_exchange_weak(cur, cur + 1, std::memory_order_acq_rel, std::memory_order_acquire)) return true;
-    }
-  }
-  void work(const uint64_t g) {  // helpers
-    Job& j = jobs[g & 1];
-    for (;;) {
-      inflight.fetch_add(1, std::memory_order_seq_cst);  // BEFORE the claim: a submitter that sees zero knows nobody holds a chunk
-      size_t i;
-      if (!claim(g, j, i)) { inflight.fetch_sub(1, std::memory_order_seq_cst); break; }
-      // chunk i of job g is ours: nobody rewrites the descriptor before `inflight` is back at zero
-      if (j.widen.load(std::memory_order_relaxed)) {
-        if (widen_chunk(j, i, nullptr, nullptr) && i < kMaxStates) state[i].store(2, std::memory_order_release);
-      } else {
-        const size_t off = i * kChunk, len = std::min(kChunk, j.bytes.load(std::memory_order_relaxed) - off);
-        copy_chunk(j.dst.load(std::memory_order_relaxed) + off, j.src.load(std::memory_order_relaxed) + off, len);
-      }
-      done.fetch_add(1, std::memory_order_acq_rel);
-      inflight.fetch_sub(1, std::memory_order_seq_cst);
-    }
-  }
-  // has the flag of chunk i of a widening job arrived?
-  static bool chunk_landed(const Job& j, const size_t i) {
-    const size_t half = j.nchunks.load(std::memory_order_relaxed) / 2;
-    const volatile uint32_t* fl = i >= half ? j.flags2.load(std::memory_order_relaxed) : j.flags.load(std::memory_order_relaxed);
-    return !fl || fl[i >= half ? i - half : i] == j.epoch.load(std::memory_order_relaxed);
-  }
-  // one chunk of a widening job; the submitting thread passes `drained` and gives up (abort_widen) when the stream has run dry
-  // without the chunk's flag.  false: not widened (given up)
-  bool widen_chunk(Job& j, const size_t i, bool (*drained)(void*), void* arg) {
-    const size_t half = j.nchunks.load(std::memory_order_relaxed) / 2;
-    const int part = i >= half ? 1 : 0;
-    const size_t lc = i - (part ? half : 0);
-    const volatile uint32_t* fl = part ? j.flags2.load(std::memory_order_relaxed) : j.flags.load(std::memory_order_relaxed);
-    if (fl) {
-      const uint32_t epoch = j.epoch.load(std::memory_order_relaxed);
-      for (uint32_t spins = 1; fl[lc] != epoch; spins++) {
-        if (abort_widen.load(std::memory_order_relaxed)) return false;
-        MRH_CPU_RELAX();
-        if (drained && (spins & 1023u) == 0 && drained(arg)) {
-          // the stream has run dry: everything the launch wrote is visible, or about to be — only a flag that stays away is an error
-          const int64_t t = now_ns();
-          while (fl[lc] != epoch && now_ns() - t < 200000000) MRH_CPU_RELAX();
-          if (fl[lc] == epoch) break;
-          abort_widen.store(1, std::memory_order_relaxed);
-          return false;
-        }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    const size_t bytes = j.bytes.load(std::memory_order_relaxed);
-    const size_t off = lc * kWidenChunk, len = std::min(kWidenChunk, bytes - off);
-    const float* src = (const float*) ((part ? j.src2.load(std::memory_order_relaxed) : j.src.load(std::memory_order_relaxed)) + off);
-    double* dst = (double*) ((part ? j.dst2.load(std::memory_order_relaxed) : j.dst.load(std::memory_order_relaxed)) + 2 * off);
-    widen_floats(dst, src, len / sizeof(float));
-    return true;
-  }
-  // both parts of a widening job through the pool (the calling thread works too); false: gave up on a flag
-  bool widen(double* const dst[2], const float* const src[2], const volatile uint32_t* const flags[2], const uint32_t epoch, const size_t nfloat,
-             bool (*drained)(void*), void* arg) {
-    if (!started) start();
-    const size_t bytes = nfloat * sizeof(float);
-    const size_t per = (bytes + kWidenChunk - 1) / kWidenChunk, nc = 2 * per;
-    if (nc == 0) return true;
-    quiesce();  // a straggler of the previous widening job still reads its descriptor
-    abort_widen.store(0, std::memory_order_relaxed);
-    const uint64_t g = generation.load(std::memory_order_relaxed) + 1;  // one submitter at a time (g_copy_mutex)
-    Job& j = jobs[g & 1];
-    j.dst.store((char*) dst[0], std::memory_order_relaxed); j.src.store((const char*) src[0], std::memory_order_relaxed);
-    j.dst2.store((char*) dst[1], std::memory_order_relaxed); j.src2.store((const char*) src[1], std::memory_order_relaxed);
-    j.flags.store(flags[0], std::memory_order_relaxed); j.flags2.store(flags[1], std::memory_order_relaxed);
-    j.epoch.store(epoch, std::memory_order_relaxed);
-    j.bytes.store(bytes, std::memory_order_relaxed); j.nchunks.store(nc, std::memory_order_relaxed);
-    j.widen.store(1, std::memory_order_relaxed);
-    const bool stateful = nc <= kMaxStates;
-    for (size_t i = 0; i < std::min(nc, kMaxStates); i++) state[i].store(0, std::memory_order_relaxed);
-    done.store(0, std::memory_order_relaxed);
-    ticket.store((g & 0xFFFFFFFFull) << 32, std::memory_order_release);
-    generation.store(g, std::memory_order_release);
-    if (sleepers.load(std::memory_order_acquire) > 0) { std::lock_guard<std::mutex> lk(m); cv.notify_all(); }
-    {  // work(g) with the stream check in the flag wait
-      size_t i;
-      while (claim(g, j, i)) {
-        if (widen_chunk(j, i, drained, arg) && i < kMaxStates) state[i].store(2, std::memory_order_release);
-        done.fetch_add(1, std::memory_order_acq_rel);
-      }
-    }
-    if (stateful) {
-      // The tickets are out; at most one chunk per helper is still under way.  In chunk order: wait for it while it can still be
-      // on its way (the flag has not arrived, or arrived less than a grace of 40 us ago — a chunk is ~10 us of work), then redo it.
-      for (size_t i = 0; i < nc && !abort_widen.load(std::memory_order_relaxed); i++) {
-        int64_t landed_at = 0;
-        uint32_t spins = 0;
-        while (state[i].load(std::memory_order_acquire) != 2) {
-          if (abort_widen.load(std::memory_order_relaxed)) break;
-          if (!chunk_landed(j, i)) {  // nobody can have widened it yet: the wait is for the device (with the stream check)
-            if (drained && (++spins & 1023u) == 0 && drained(arg)) {
-              const int64_t t = now_ns();
-              while (!chunk_landed(j, i) && now_ns() - t < 200000000) MRH_CPU_RELAX();
-              if (!chunk_landed(j, i)) { abort_widen.store(1, std::memory_order_relaxed); break; }
-            }
-            MRH_CPU_RELAX();
-            continue;
-          }
-          const int64_t now = now_ns();
-          if (!landed_at) landed_at = now;
-          if (now - landed_at > 40000) {  // its helper lost its core (or is slow): the same bytes, written here
-            if (widen_chunk(j, i, drained, arg)) { state[i].store(2, std::memory_order_release); redone.fetch_add(1, std::memory_order_relaxed); }
-            break;
-          }
-          MRH_CPU_RELAX();
-        }
-      }
-    } else {
-      while (done.load(std::memory_order_acquire) < nc && !abort_widen.load(std::memory_order_relaxed)) MRH_CPU_RELAX();
-    }
-    // (the descriptor keeps `widen` set: a straggler reads it after this call has returned; the next job rewrites it behind quiesce())
-    return abort_widen.load(std::memory_order_relaxed) == 0;
-  }
-  // wake the helpers now and keep them spinning for a millisecond: a widening job is on its way
-  void prewake() {
-    if (!started) start();
-    spin_until_ns.store(now_ns() + 1500000, std::memory_order_relaxed);
-    if (sleepers.load(std::memory_order_acquire) > 0) {
-      quiesce();
-      const uint64_t g = generation.load(std::memory_order_relaxed) + 1;  // an empty job: nothing to claim
-      Job& j = jobs[g & 1];
-      j.widen.store(0, std::memory_order_relaxed);
-      j.bytes.store(0, std::memory_order_relaxed); j.nchunks.store(0, std::memory_order_relaxed);
-      done.store(0, std::memory_order_relaxed);
-      ticket.store((g & 0xFFFFFFFFull) << 32, std::memory_order_release);
-      generation.store(g, std::memory_order_release);
-      std::lock_guard<std::mutex> lk(m); cv.notify_all();
-    }
-  }
-  void helper() {
-    uint64_t seen = generation.load(std::memory_order_acquire);
-    for (;;) {
-      // wait for the next job: spin ~100 us (a frame loop submits every 40-100 us), then sleep
-      const auto t0 = std::chrono::steady_clock::now();
-      uint64_t g;
-      int spins = 0;
-      while ((g = generation.load(std::memory_order_acquire)) == seen) {
-        MRH_CPU_RELAX();
-        if ((++spins & 255) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(150) &&
-            now_ns() > spin_until_ns.load(std::memory_order_relaxed)) {
-          std::unique_lock<std::mutex> lk(m);
-          sleepers.fetch_add(1);
-          cv.wait(lk, [&] { return generation.load(std::memory_order_acquire) != seen; });
-          sleepers.fetch_sub(1);
-        }
-      }
-      seen = g;
-      work(g);
-    }
-  }
-  void start() {
-    started = true;
-    int n = 3;
-    if (const char* e = getenv("MRH_COPY_THREADS")) n = atoi(e);
-    const int hw = (int) std::thread::hardware_concurrency();
-    if (hw > 0 && n > hw - 1) n = hw - 1;
-    for (int i = 0; i < n; i++) {
-      threads.emplace_back([this] { helper(); });
-      threads.back().detach();  // they sleep on the condition variable when idle; the pool lives as long as the process
-    }
-  }
-  void copy(void* d, const void* s_, size_t n) {
-    if (!started) start();
-    if (threads.empty() || n < 4 * kChunk) { copy_chunk(d, s_, n); return; }
-    quiesce();  // a straggler of a widening job still reads that job's descriptor
-    const size_t nc = (n + kChunk - 1) / kChunk;
-    const uint64_t g = generation.load(std::memory_order_relaxed) + 1;  // one submitter at a time (g_copy_mutex)
-    Job& j = jobs[g & 1];
-    j.dst.store((char*) d, std::memory_order_relaxed); j.src.store((const char*) s_, std::memory_order_relaxed);
-    j.bytes.store(n, std::memory_order_relaxed); j.nchunks.store(nc, std::memory_order_relaxed);
-    j.widen.store(0, std::memory_order_relaxed);
-    done.store(0, std::memory_order_relaxed);  // no ticket of an earlier job is outstanding: they all completed before their copy() returned
-    ticket.store((g & 0xFFFFFFFFull) << 32, std::memory_order_release);
-    generation.store(g, std::memory_order_release);
-    if (sleepers.load(std::memory_order_acquire) > 0) { std::lock_guard<std::mutex> lk(m); cv.notify_all(); }
-    size_t i;
-    while (claim(g, j, i)) {
-      const size_t off = i * kChunk, len = std::min(kChunk, n - off);
-      copy_chunk((char*) d + off, (const char*) s_ + off, len);
-      done.fetch_add(1, std::memory_order_acq_rel);
-    }
-    while (done.load(std::memory_order_acquire) < nc) MRH_CPU_RELAX();  // the source is the caller's: nobody may still read it on return
-  }
-};
-CopyPool* copy_pool() {
-  static CopyPool* pool = new CopyPool();  // never destroyed: detached helpers may still be parked on it at exit
-  return pool;
-}
-std::mutex g_copy_mutex;  // one job at a time (contexts on different host threads share the pool)
-void copy_to_staging(void* dst, const void* src, size_t n) {
-  std::lock_guard<std::mutex> lk(g_copy_mutex);
-  copy_pool()->copy(dst, src, n);
-}
-bool widen_from_staging(double* const dst[2], const float* const src[2], const volatile u32* const flags[2], u32 epoch, size_t nfloat,
-                        bool (*drained)(void*), void* arg) {
-  std::lock_guard<std::mutex> lk(g_copy_mutex);
-  return copy_pool()->widen(dst, src, flags, epoch, nfloat, drained, arg);
-}
-void widen_prewake() {
-  std::lock_guard<std::mutex> lk(g_copy_mutex);
-  copy_pool()->prewake();
-}
-// no helper is still reading a staging buffer or writing a result array of an earlier widening job (CopyPool: `inflight`)
-void widen_quiesce() {
-  std::lock_guard<std::mutex> lk(g_copy_mutex);
-  copy_pool()->quiesce();
-}
-uint64_t widen_redone() { return copy_pool()->redone.load(std::memory_order_relaxed); }
-#else
-void copy_to_staging(void* dst, const void* src, size_t n);
-bool widen_from_staging(double* const dst[2], const float* const src[2], const volatile u32* const flags[2], u32 epoch, size_t nfloat,
-                        bool (*drained)(void*), void* arg) { return false; }
-void widen_prewake() {}
-void widen_quiesce() {}
-uint64_t widen_redone() { return 0; }
-#endif
-
-// one host image into the next slot of its ring: wait until the slot is free, copy into pinned staging (the caller's
-// buffer is free on return), enqueue the H2D on the copy stream
-int upload_image(mrh_ctx* c, UpRing& ring, const void* src, const size_t bytes, const void** out_dev) {
-  if (!c->copy_ready) {
-    // One copy stream per image kind: the depth and the colour image of a frame then move through two SDMA engines side by
-    // side (64 us per frame instead of 77 on one stream).  A copy kernel pulling the pinned buffer over PCIe is faster on its
-    // own (48 GB/s against 25-30, tools/micro/h2d_paths.hip) but finds no wave slots while k_back fills every SIMD's
-    // registers, neither with stream priority nor with CU masks (tools/micro/cu_mask_overlap.hip: a masked stream costs the
-    // big kernel 14 %): measured at 73-75 us per frame inside the library, and dropped.
-    for (UpRing* r : {&c->up_depth, &c->up_rgb}) HIP_TRY(c, hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : c->frame_done) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->copy_ready = true;
-  }
-  const int next = (ring.cur + 1) % 3;
-  // a frame that mrh_integrate kept back (flush_deferred) has not marked its slots yet: before the ring comes round to one of them, it runs
-  if (c->deferred.on && next == c->deferred.ring[&ring == &c->up_rgb ? 1 : 0].cur) {
-    const int frc = flush_deferred(c);
-    if (frc < 0) return frc;
-  }
-  UpSlot& u = ring.s[next];
-  if (u.last_seq) HIP_TRY(c, hipEventSynchronize(c->frame_done[u.last_seq % 8]));  // this mark or a later one of the same stream
-  if (u.copied_rec) HIP_TRY(c, hipEventSynchronize(u.copied));
-  if (bytes > u.cap) {
-    if (u.h) HIP_TRY(c, hipHostFree(u.h));
-    if (u.d) HIP_TRY(c, hipFree(u.d));
-    u.h = u.d = nullptr; u.cap = 0;
-    HIP_TRY(c, hipHostMalloc(&u.h, bytes, hipHostMallocDefault));
-    HIP_TRY(c, hipMalloc(&u.d, bytes));
-    u.cap = bytes;
-    if (!u.copied) HIP_TRY(c, hipEventCreateWithFlags(&u.copied, hipEventDisableTiming));
-  }
-  copy_to_staging(u.h, src, bytes);
-  // (Round 5 measured the two runtime calls below on a thread of their own, so that the caller is back in its code ~10 us earlier:
-  // uploads alone 56 -> 43 us per frame, but a FRAME stays at 62-64 us — mrh_integrate then waits for that thread to have
-  // recorded the event before it can enqueue the stream wait, and the chain staging -> copy call -> stream wait -> launches is
-  // on the caller's critical path whoever makes the calls.  Removed again; profiles/r05/README.md.)
-  HIP_TRY(c, hipMemcpyAsync(u.d, u.h, bytes, hipMemcpyHostToDevice, ring.stream));
-  HIP_TRY(c, hipEventRecord(u.copied, ring.stream));
-  u.copied_rec = true;
-  u.last_seq = 0;
-  ring.last_copy = u.copied;  // a ring's copies are ordered on its stream: the newest event covers the earlier ones
-  ring.waited[0] = ring.waited[1] = false;
-  ring.cur = next;
-  *out_dev = u.d;
-  return MRH_OK;
-}
-
-// before kernels that read the images: `reader` — the stream those kernels are launched on: the front stream for a pipelined
-// frame (its integration reads the cleaned copy the front half wrote), the main stream otherwise — waits for the newest uploads
-int send_uploads(mrh_ctx* c, hipStream_t reader) {
-  const int w = (reader == c->stream) ? 0 : 1;
-  for (UpRing* r : {&c->up_depth, &c->up_rgb})
-    if (r->last_copy && !r->waited[w]) {
-      // a transfer the host already sees complete needs no wait packet (a kernel launched from here on reads what it wrote)
-      const hipError_t q = hipEventQuery(r->last_copy);
-      if (q == hipErrorNotReady) {
-        (void) hipGetLastError();
-        HIP_TRY(c, hipStreamWaitEvent(reader, r->last_copy, 0));
-      } else if (q != hipSuccess) {
-        return fail(c, MRH_ERR_DEVICE, "image transfer: %s", hipGetErrorString(q));
-      }
-      r->waited[w] = true;
-    }
-  return MRH_OK;
-}
-
-// ---- the non-blocking peeks (mrh_peek_free_blocks, mrh_peek_error_flags): h_peek, eight reports, one per frame mark ----
-// the first peek of a context: reports start with the next frame
-int enable_peeks(mrh_ctx* c) {
-  if (c->peek_enabled) return MRH_OK;
-  HIP_TRY(c, hipHostMalloc((void**) &c->h_peek, 64 * sizeof(int), hipHostMallocDefault));
-  memset(c->h_peek, 0, 64 * sizeof(int));
-  c->peek_enabled = true;
-  return MRH_OK;
-}
-// the newest of the last eight marks whose report has landed: 1 and {*seq, *back: marks behind the newest, 1 = none}, 0 if none has, or an error
-int newest_report(mrh_ctx* c, const char* who, uint64_t* seq_out, uint64_t* back_out) {
-  for (uint64_t back = 1; back <= 8 && back < c->frame_seq; back++) {
-    const uint64_t seq = c->frame_seq - back;
-    if (c->peek_seq[seq % 8] != seq) continue;
-    const hipError_t q = hipEventQuery(c->peek_done[seq % 8]);
-    if (q == hipErrorNotReady) continue;
-    if (q != hipSuccess) return fail(c, MRH_ERR_DEVICE, "%s: %s", who, hipGetErrorString(q));
-    if (c->peek_seq[seq % 8] != seq) continue;
-    *seq_out = seq; *back_out = back;
-    return 1;
-  }
-  return 0;
-}
-// the pool report of mark `seq` (ctr[0 .. 4]: free-list levels ... error flags) into its slot of h_peek, behind whatever is on
-// `s`; from here on the mark exists for the peeks (newest_report).  A mark that is posted again refreshes its report.
-int post_report(mrh_ctx* c, const uint64_t seq, hipStream_t s) {
-  k_report<<<1, 64, 0, s>>>(&c->tab.ctr[CTR_HEAP_FINE], c->h_peek + 8 * (seq % 8));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipEventRecord(c->peek_done[seq % 8], s));
-  c->peek_seq[seq % 8] = seq;
-  return MRH_OK;
-}
-
-// after the kernels of a frame (or of a seeding call) are enqueued: mark the ring slots they read, report the pool level
-int mark_frame(mrh_ctx* c) {
-  UpSlot* used[2] = {nullptr, nullptr};
-  if (c->up_depth.cur >= 0 && c->d_depth == c->up_depth.s[c->up_depth.cur].d) used[0] = &c->up_depth.s[c->up_depth.cur];
-  if (c->up_rgb.cur >= 0 && c->d_rgb == c->up_rgb.s[c->up_rgb.cur].d) used[1] = &c->up_rgb.s[c->up_rgb.cur];
-  if (!used[0] && !used[1] && !c->peek_enabled) return MRH_OK;
-  const uint64_t seq = c->frame_seq++;
-  if (!c->frame_done[0])
-    for (hipEvent_t& e : c->frame_done) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  const bool lazy = c->last_frame_lazy && c->npend;  // the frame's integration is not enqueued yet (launch_pending)
-  if (c->peek_enabled) {
-    if (!c->peek_done[0])
-      for (hipEvent_t& e : c->peek_done) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (lazy) {
-      // The report of a pipelined frame is written behind its integration, by launch_pending; until then the mark does not
-      // exist for the peeks (they fall back to an older one and say how many frames behind it is).  A report launched here would
-      // sit behind the integration of an EARLIER frame only, and an event on the front stream says nothing about it at all.
-      c->peek_seq[seq % 8] = 0;
-      c->pendq[c->npend - 1].report_seq = seq;
-    } else if (const int rc = post_report(c, seq, c->stream)) {
-      return rc;
-    }
-  }
-  if (used[0] || used[1]) {
-    // the raw images of a pipelined frame are read by its front half, on the front stream (its integration reads the cleaned copy)
-    HIP_TRY(c, hipEventRecord(c->frame_done[seq % 8], lazy ? c->stream_front : c->stream));
-    for (UpSlot* u : used) if (u) u->last_seq = seq;
-  }
-  return MRH_OK;
-}
-
 // ---- 3DGS splat seeds: GaussianContainer::extractNodesQTree + checkNodes (gaussian_data_structures.cpp:48-68, .cu:58-84), see mrh_splat.h
 int seeds_checks(mrh_ctx* c, const float qtree_thresh, const int qtree_min_pixel_size, const mrh_splat_seed** out, uint64_t* out_n) {
   if (!out || !out_n) return fail(c, MRH_ERR_INVALID_ARG, "mrh_splat_seeds: null argument");
@@ -1706,7 +508,7 @@ int qtree_buffers(mrh_ctx* c, const QTree& qt) {
   }
   if (!rc) rc = regrow_pinned(c, c->h_qt_seeds, c->qt_seed_cap, seeds, seeds * sizeof(mrh_splat_seed));
   if (rc) return rc;
-  if (!c->h_qt_out) HIP_TRY(c, hipHostMalloc((void**) &c->h_qt_out, 2 * sizeof(u64), hipHostMallocDefault));
+  if (!c->h_qt_out) HIP_TRY(c, pinned_alloc(c, c->h_qt_out, 2 * sizeof(u64)));
   return MRH_OK;
 }
 int launch_qtree(mrh_ctx* c, const QTree& qt, const float qtree_thresh) {
@@ -1843,11 +645,6 @@ int flush_deferred(mrh_ctx* c) {
   }
   return rc;
 }
-}  // namespace
-}  // extern "C++"
-
-extern "C++" {
-namespace {
 
 int take_event_pair(mrh_ctx* c, EvPair& e) {
   if (!c->ev_pool.empty()) { e = c->ev_pool.back(); c->ev_pool.pop_back(); return MRH_OK; }
@@ -1858,7 +655,7 @@ int take_event_pair(mrh_ctx* c, EvPair& e) {
     e = c->ev_pool.back(); c->ev_pool.pop_back();
     return MRH_OK;
   }
-  HIP_TRY(c, hipEventCreate(&e.a)); HIP_TRY(c, hipEventCreate(&e.b));
+  HIP_TRY(c, event_new(c, e.a, true)); HIP_TRY(c, event_new(c, e.b, true));
   return MRH_OK;
 }
 
@@ -2008,20 +805,21 @@ int strict_point(mrh_ctx* c) {
 int ensure_pipe_state(mrh_ctx* c) {
   if (c->stream_front) return MRH_OK;
   const size_t cap = c->num_blocks;
+  // the stream comes last: it is what says "the state exists", and a step that failed is taken again by the next call
+  // (hipEventDisableSystemFence on these events — they order two streams of one device — was measured in round 5: no difference)
+  for (hipEvent_t& e : c->ev_front) if (!e) HIP_TRY(c, event_new(c, e, false));
+  for (int i = 1; i < kPipeRing; i++) {
+    if (!c->ring_vis[i]) HIP_TRY(c, dev_alloc(c, c->ring_vis[i], cap * sizeof(int4)));
+    if (!c->ring_bbox[i]) HIP_TRY(c, dev_alloc(c, c->ring_bbox[i], cap * sizeof(int4)));
+    if (!c->ring_cfree[i]) HIP_TRY(c, dev_alloc(c, c->ring_cfree[i], cap * sizeof(int4)));
+    if (!c->ring_zmin[i]) HIP_TRY(c, dev_alloc(c, c->ring_zmin[i], cap * sizeof(float)));
+  }
+  if (!c->fast.zlist) HIP_TRY(c, dev_alloc(c, c->fast.zlist, cap * sizeof(int4)));
+  if (!c->want_ring) HIP_TRY(c, dev_alloc(c, c->want_ring, (size_t) kPipeRing * c->slots * sizeof(u32)));
+  HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), c->stream));  // stamps start at 1
+  if (!c->h_levels) HIP_TRY(c, pinned_alloc(c, c->h_levels, 4 * sizeof(int)));
   // (a high-priority front stream, a ring of eight and integrations deferred by two calls were measured: no difference)
   HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_front, hipStreamNonBlocking));
-  // (hipEventDisableSystemFence on these events — they order two streams of one device — was measured in round 5: no difference)
-  for (hipEvent_t& e : c->ev_front) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (int i = 1; i < kPipeRing; i++) {
-    HIP_TRY(c, hipMalloc((void**) &c->ring_vis[i], cap * sizeof(int4)));
-    HIP_TRY(c, hipMalloc((void**) &c->ring_bbox[i], cap * sizeof(int4)));
-    HIP_TRY(c, hipMalloc((void**) &c->ring_cfree[i], cap * sizeof(int4)));
-    HIP_TRY(c, hipMalloc((void**) &c->ring_zmin[i], cap * sizeof(float)));
-  }
-  HIP_TRY(c, hipMalloc((void**) &c->fast.zlist, cap * sizeof(int4)));
-  HIP_TRY(c, hipMalloc((void**) &c->want_ring, (size_t) kPipeRing * c->slots * sizeof(u32)));
-  HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), c->stream));  // stamps start at 1
-  if (!c->h_levels) HIP_TRY(c, hipHostMalloc((void**) &c->h_levels, 4 * sizeof(int), hipHostMallocDefault));
   c->h_levels[0] = (int) c->num_blocks - 1; c->h_levels[1] = 0; c->h_levels[2] = -1;
   c->tab.h_levels = c->h_levels;
   c->front_needs_sync = true;  // the memset above
@@ -2037,10 +835,10 @@ int ensure_frame_dcx(mrh_ctx* c, const size_t npix) {
   }
   if (c->stream_front) HIP_TRY(c, hipStreamSynchronize(c->stream_front));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (uint2*& d : c->pipe_dcx) { if (d) HIP_TRY(c, hipFree(d)); d = nullptr; }
+  for (uint2*& d : c->pipe_dcx) HIP_TRY(c, dev_free(c, d));
   c->pipe_npix = 0;
   const int n = c->stream_front ? kPipeRing : 1;
-  for (int i = 0; i < n; i++) HIP_TRY(c, hipMalloc((void**) &c->pipe_dcx[i], npix * sizeof(uint2)));
+  for (int i = 0; i < n; i++) HIP_TRY(c, dev_alloc(c, c->pipe_dcx[i], npix * sizeof(uint2)));
   c->pipe_npix = npix;
   return MRH_OK;
 }
@@ -2364,12 +1162,6 @@ static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
   return c->frame_fused_mr ? integrate_fused_mr_frame(c, max_num_frames) : integrate_general_frame(c, max_num_frames);
 }
 
-}  // extern "C"
-
-#include "mrh_points.h"
-
-extern "C" {
-
 int mrh_integrate_resume(mrh_ctx* c) {
   int rc = ensure_ready(c, "mrh_integrate_resume");
   if (rc) return rc;
@@ -2566,12 +1358,6 @@ int mrh_get_stats(mrh_ctx* c, mrh_stats* out) {
   return MRH_OK;
 }
 
-}  // extern "C"
-
-#include "mrh_blocks.h"
-
-extern "C" {
-
 int mrh_selftest_division(mrh_ctx* c, uint64_t samples, uint64_t seed, uint64_t* out_mismatches) {
   int rc = ensure_ready(c, "mrh_selftest_division");
   if (rc) return rc;
@@ -2592,7 +1378,6 @@ int mrh_selftest_division(mrh_ctx* c, uint64_t samples, uint64_t seed, uint64_t*
 }  // extern "C"
 
 // ---- raycasting (include/mrhash_raycast.h, mrh_raycast.h) ------------------------------------------------------------------
-extern "C++" {
 namespace {
 float ray_z_host(const float min_depth, const float step, const uint32_t k) { return min_depth + (float) k * step; }  // = ray_z
 
@@ -2640,7 +1425,6 @@ void launch_raycast(mrh_ctx* c, const RayCam& rc, float* depth, float* normals, 
   k_raycast<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, depth, normals, rgb);
 }
 }  // namespace
-}  // extern "C++"
 
 extern "C" {
 
@@ -2689,7 +1473,6 @@ int mrh_raycast_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_ro
 }  // extern "C"
 
 // ---- normal estimation (include/mrhash_normals.h, mrh_normals.h) ------------------------------------------------------------
-extern "C++" {
 namespace {
 
 // the parameter block with its defaults filled in, as the kernels take it
@@ -2714,7 +1497,7 @@ int normals_scratch(mrh_ctx* c, const uint64_t n) {
   auto& N = c->nrm;
   hipStream_t s = c->stream;
   if (!N.d_ctr) {
-    HIP_TRY(c, hipMalloc((void**) &N.d_ctr, 2 * NC_N * sizeof(u64)));
+    HIP_TRY(c, dev_alloc(c, N.d_ctr, 2 * NC_N * sizeof(u64)));
     HIP_TRY(c, hipMemsetAsync(N.d_ctr, 0, 2 * NC_N * sizeof(u64), s));
   }
   if (n > N.cap) {
@@ -2769,7 +1552,6 @@ void normals_fold_info(mrh_ctx* c) {
 }
 
 }  // namespace
-}  // extern "C++"
 
 extern "C" {
 
@@ -2795,7 +1577,7 @@ int mrh_estimate_normals(mrh_ctx* c, const mrh_normals_params* p, mrh_normals_in
   rc = normals_args(c, "mrh_estimate_normals", p, n, &par);
   if (rc) return rc;
   if (!N.h_ctr) {
-    HIP_TRY(c, hipHostMalloc((void**) &N.h_ctr, NC_N * sizeof(u64), hipHostMallocDefault));
+    HIP_TRY(c, pinned_alloc(c, N.h_ctr, NC_N * sizeof(u64)));
     memset(N.h_ctr, 0, NC_N * sizeof(u64));
   }
   L.num_normals = 0;  // none valid from the moment the buffer may change
@@ -2838,5 +1620,3 @@ int mrh_get_normals(mrh_ctx* c, const float** out_nxyz, uint64_t* out_n, mrh_nor
 }
 
 }  // extern "C"
-
-#include "mrh_comm.h"

@@ -1,5 +1,5 @@
-// mrh_comm.h — RCCL behind the C ABI (include/mrhash_comm.h).  Included at the end of mrh_capi.hip: it drives the
-// library's own pack / unpack / drop / extraction steps and needs the context's internals.
+// mrh_comm.h — RCCL behind the C ABI (include/mrhash_comm.h).  Included by mrh_capi.hip behind mrh_blocks.h and
+// mrh_extract.h: it drives the library's own pack / unpack / drop / extraction steps and needs the context's internals.
 //
 // RCCL is opened at run time, from the directory of the HIP runtime this library is itself bound to (dladdr of
 // hipGetDeviceCount): /opt/rocm/lib/librccl.so.1 next to /opt/rocm/lib/libamdhip64.so.7.  That keeps ONE HIP runtime per
@@ -202,7 +202,7 @@ struct PhaseClock {
   int at = 0;
   explicit PhaseClock(mrh_ctx* ctx) : c(ctx) {}
   int mark() {  // events 0 .. 4: start, packed, counted, moved, consumed
-    if (!c->comm_ev[at]) HIP_TRY(c, hipEventCreate(&c->comm_ev[at]));
+    if (!c->comm_ev[at]) HIP_TRY(c, event_new(c, c->comm_ev[at], true));
     HIP_TRY(c, hipEventRecord(c->comm_ev[at], c->stream));
     at++;
     return MRH_OK;
@@ -232,7 +232,7 @@ static void comm_release(mrh_ctx* c) {  // free_all: the context goes away
 static int comm_allreduce_zbuf(mrh_ctx* c, u64* buf, const size_t n) {
   EvPair ev;
   if (!c->comm_ev_pool.empty()) { ev = c->comm_ev_pool.back(); c->comm_ev_pool.pop_back(); }
-  else { HIP_TRY(c, hipEventCreate(&ev.a)); HIP_TRY(c, hipEventCreate(&ev.b)); }
+  else { HIP_TRY(c, event_new(c, ev.a, true)); HIP_TRY(c, event_new(c, ev.b, true)); }
   HIP_TRY(c, hipEventRecord(ev.a, c->stream));
   // every key is < 2^63 ("empty" = INT64_MAX): the unsigned order is the signed one
   CTX_NCCL(c, rccl()->AllReduce(buf, buf, n, ncclInt64, ncclMin, c->comm->nccl, c->stream));

@@ -557,8 +557,8 @@ void ensure_mc_records(mrh_ctx* c, const ExtractOpts& o, McPass* p) {
   p->use_records = o.records;
   if (p->use_records && c->mc_rec_cap == 0) {
     const size_t cap = std::max<size_t>((size_t) p->n * (size_t) o.records_per_block, 16);
-    if (hipMalloc((void**) &c->d_mc_recs, cap * kMcRecWords * sizeof(u32)) == hipSuccess) c->mc_rec_cap = cap;
-    else { (void) hipGetLastError(); c->d_mc_recs = nullptr; p->use_records = false; }  // no room for the records: the two-pass emit needs none
+    if (dev_alloc(c, c->d_mc_recs, cap * kMcRecWords * sizeof(u32)) == hipSuccess) c->mc_rec_cap = cap;
+    else { (void) hipGetLastError(); p->use_records = false; }  // no room for the records: the two-pass emit needs none
   }
   p->R.ctr = p->S.d_rec_ctr; p->R.recs = p->use_records ? c->d_mc_recs : nullptr; p->R.base = p->S.d_rec_base; p->R.count = p->S.d_rec_n;
   p->R.cap = (u32) std::min<size_t>(c->mc_rec_cap, 0xFFFFFFF0u);
@@ -570,10 +570,10 @@ struct GrowRecords {
   ~GrowRecords() {
     if (demand <= c->mc_rec_cap) return;
     (void) hipStreamSynchronize(c->stream);
-    if (c->d_mc_recs) (void) hipFree(c->d_mc_recs);
-    c->d_mc_recs = nullptr; c->mc_rec_cap = 0;
+    (void) dev_free(c, c->d_mc_recs);
+    c->mc_rec_cap = 0;
     const size_t cap = (size_t) (demand + demand / 4);
-    if (hipMalloc((void**) &c->d_mc_recs, cap * kMcRecWords * sizeof(u32)) == hipSuccess) c->mc_rec_cap = cap;
+    if (dev_alloc(c, c->d_mc_recs, cap * kMcRecWords * sizeof(u32)) == hipSuccess) c->mc_rec_cap = cap;
     else (void) hipGetLastError();  // no room: the next extraction starts from the default again
   }
 };
@@ -661,7 +661,7 @@ int extract_soup(mrh_ctx* c, const ExtractOpts& o, const int n, const bool want_
   c->last_mc_blocks = (uint64_t) n;
   if (p.timed)
     for (hipEvent_t& ev : c->mc_ev)
-      if (!ev) HIP_TRY(c, hipEventCreate(&ev));
+      if (!ev) HIP_TRY(c, event_new(c, ev, true));
   GrowRecords grow_records{c};
   ensure_mc_records(c, o, &p);
   if (p.use_records) HIP_TRY(c, hipMemsetAsync(p.S.d_rec_ctr, 0, 2 * sizeof(u32), s));
@@ -676,7 +676,7 @@ int extract_soup(mrh_ctx* c, const ExtractOpts& o, const int n, const bool want_
   const u64 spec_cap = std::min<u64>(c->soup_cap, c->max_triangles);
   // the host waits for the TOTAL, not for the emit pass behind it: it sizes and enqueues the post-process while the emit pass
   // runs (a stream synchronisation here left the GPU idle for the ~20 us of the host's round trip and first launch)
-  if (!c->ev_mc_total) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mc_total, hipEventDisableTiming));
+  if (!c->ev_mc_total) HIP_TRY(c, event_new(c, c->ev_mc_total, false));
   HIP_TRY(c, hipEventRecord(c->ev_mc_total, s));
   if (spec_cap > 0) launch_mc_emit(c, p, spec_cap, 0, p.use_records);
   HIP_TRY(c, hipEventSynchronize(c->ev_mc_total));

@@ -196,14 +196,12 @@ int scan_prepare(mrh_ctx* c, const ScanPlan& p) {
   Scan& sc = L.buckets;
   if (L.buckets_scratch == 0) {
     const size_t nb = (size_t) c->num_blocks;
-    bool ok = hipMalloc((void**) &sc.vcnt, nb * 512 * sizeof(u32)) == hipSuccess;
-    ok = ok && hipMalloc((void**) &sc.bstamp, nb * sizeof(u32)) == hipSuccess;
-    ok = ok && hipMalloc((void**) &L.d_buckets_ctr, 2 * SC_N * sizeof(u32)) == hipSuccess;
+    bool ok = dev_alloc(c, sc.vcnt, nb * 512 * sizeof(u32)) == hipSuccess;
+    ok = ok && dev_alloc(c, sc.bstamp, nb * sizeof(u32)) == hipSuccess;
+    ok = ok && dev_alloc(c, L.d_buckets_ctr, 2 * SC_N * sizeof(u32)) == hipSuccess;
     if (!ok) {  // one counter per voxel slot does not fit next to this map
       (void) hipGetLastError();
-      auto F = [](void* q) { if (q) (void) hipFree(q); };
-      F(sc.vcnt); F(sc.bstamp); F(L.d_buckets_ctr);
-      sc.vcnt = sc.bstamp = L.d_buckets_ctr = nullptr;
+      (void) dev_free(c, sc.vcnt); (void) dev_free(c, sc.bstamp); (void) dev_free(c, L.d_buckets_ctr);
       L.buckets_scratch = -1;
       return 1;
     }
@@ -261,7 +259,7 @@ int scan_buffers(mrh_ctx* c, ScanPlan* p) {
     if (rc) return rc;
   }
   if (!L.h_sorted_report) {
-    HIP_TRY(c, hipHostMalloc((void**) &L.h_sorted_report, 4 * sizeof(u32), hipHostMallocDefault));
+    HIP_TRY(c, pinned_alloc(c, L.h_sorted_report, 4 * sizeof(u32)));
     memset(L.h_sorted_report, 0, 4 * sizeof(u32));
   }
   return MRH_OK;

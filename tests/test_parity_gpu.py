@@ -1070,6 +1070,91 @@ def test_contexts_release_their_device_memory(hip):
     assert free0 - free1 < 32 << 20, f"device memory shrank by {(free0 - free1) >> 20} MiB over 25 create/destroy cycles"
 
 
+def test_failed_create_releases_everything(hip, oracle):
+    """A mrh_create that fails half way — the voxel pool alone is larger than the card, so its hipMalloc answers out-of-memory
+    after about 1 GB of heap and descriptors has been allocated — is an ordinary error return that leaves nothing behind, and
+    the process goes on to fuse correctly."""
+    from mrhash_amd import capi, hipmem
+
+    _, total = hipmem.mem_get_info()
+    too_many = total // 6144 + 1  # blocks of 512 voxels x 12 bytes
+
+    def failing_create():
+        with pytest.raises(capi.MrhError) as ei:
+            pu.make_engine(hip, synth.CFG1, dict(synth.CFG1_PARAMS, sdf_var_threshold=0.0, hash_slots=1024), too_many)
+        assert ei.value.code == capi.MRH_ERR_DEVICE
+        msg = hip.mrh_last_error(None).decode()
+        assert msg.startswith("mrh_create:"), msg
+
+    for _ in range(3):
+        failing_create()
+    hipmem.synchronize()
+    free0, _ = hipmem.mem_get_info()
+    for _ in range(10):
+        failing_create()
+    hipmem.synchronize()
+    free1, _ = hipmem.mem_get_info()
+    print(f"failed creates: free memory {free0 >> 20} -> {free1 >> 20} MiB")
+    assert free0 - free1 < 32 << 20, f"device memory shrank by {(free0 - free1) >> 20} MiB over 10 failed creates"
+    f = synth.cfg1_sphere()
+    a = pu.make_engine(hip, synth.CFG1, synth.CFG1_PARAMS, 4096)
+    b = pu.make_engine(oracle, synth.CFG1, synth.CFG1_PARAMS, 4096)
+    for e in (a, b):
+        pu.feed(e, f)
+    assert pu.compare_maps(a, b)["blocks"] > 0
+    a.close()
+    b.close()
+
+
+def test_contexts_release_their_lazy_buffers(hip):
+    """The lazily allocated buffers test_contexts_release_their_device_memory does not reach — profile events, LiDAR scan and
+    normal-estimation scratch, the raycast images, the pack buffer, the merge accumulator — on a variance-adaptive map: create /
+    use / destroy in a loop leaves the free device memory where it was."""
+    from mrhash_amd import capi, hipmem
+
+    K = synth.CFG1
+    f = synth.cfg1_sphere()
+    # 4 096 points on the camera's side of the sphere the frames show (radius 0.5 around (0, 0, 1.5))
+    u, v = np.meshgrid(np.linspace(-0.9, 0.9, 64, dtype=np.float32), np.linspace(-0.9, 0.9, 64, dtype=np.float32))
+    r2 = u * u + v * v
+    keep = r2 < 0.95
+    pts = np.stack([0.5 * u[keep], 0.5 * v[keep], 1.5 - 0.5 * np.sqrt(1.0 - r2[keep])], axis=-1).astype(np.float32)
+    assert 2000 < len(pts) <= 4096
+
+    def cycle():
+        e = pu.make_engine(hip, K, dict(synth.CFG1_PARAMS, sdf_var_threshold=0.02), 4096)
+        for _ in range(2):
+            pu.feed(e, f)
+        e.set_profile(True)
+        pu.feed(e, f)
+        e.upload_points(pts)
+        e.estimate_normals()
+        e.integrate_points()
+        nrm, _ = e.get_normals()
+        assert nrm.shape == pts.shape
+        depth, _, _ = e.raycast(K.fx, K.fy, K.cx, K.cy, K.rows, K.cols, f.R, f.t, 0.01, 30.0)
+        assert depth.size == K.rows * K.cols
+        _, n, _ = e.pack_blocks(capi.PACK_OWNER, 0)
+        assert n > 0
+        assert e.drop_blocks(capi.DROP_ALL) > 0
+        pu.feed(e, f)  # something to extract again
+        e.mesh_merge_begin()
+        e.extract_triangles()
+        e.mesh_merge_end()
+        e.close()
+
+    for _ in range(3):  # the first uses pay one-off runtime allocations (code objects, queues, scratch)
+        cycle()
+    hipmem.synchronize()
+    free0, _ = hipmem.mem_get_info()
+    for _ in range(10):
+        cycle()
+    hipmem.synchronize()
+    free1, _ = hipmem.mem_get_info()
+    print(f"lazy-buffer cycles: free memory {free0 >> 20} -> {free1 >> 20} MiB")
+    assert free0 - free1 < 32 << 20, f"device memory shrank by {(free0 - free1) >> 20} MiB over 10 create/destroy cycles"
+
+
 _PIPE40 = {}
 
 
