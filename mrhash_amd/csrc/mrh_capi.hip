@@ -1,9 +1,10 @@
 // mrh_capi.hip — implementation of the C ABI (include/mrhash_hip.h) on top of the gfx950 kernels.
 //
 // Host side of the thin HIP layer: enqueues the per-frame kernel chain with no host round trip, and only synchronises in the
-// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the integrate paths, the splat, raycast
-// and normals glue.  The context and its lifetime: mrh_context.h; the copy pool: mrh_hostcopy.h; uploads, frame marks, peeks:
-// mrh_upload.h; extraction, scans, block I/O, RCCL: mrh_extract.h, mrh_points.h, mrh_blocks.h, mrh_comm.h.  One translation unit.
+// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the splat, raycast and normals glue.
+// The context and its lifetime: mrh_context.h; the copy pool: mrh_hostcopy.h; uploads, frame marks, peeks: mrh_upload.h; the
+// host side of a depth frame: mrh_frame.h; extraction, scans, block I/O, RCCL: mrh_extract.h, mrh_points.h, mrh_blocks.h,
+// mrh_comm.h.  One translation unit.
 // There is NO CPU fallback in this file: without a HIP device mrh_create fails with MRH_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -94,24 +95,6 @@ int take_device_flags(mrh_ctx* c, u32* out) {
   return MRH_OK;
 }
 
-// Table upkeep between two frames (mrh_kernels.h): census of the tombstones every `census_period` frames or after a bulk
-// change, rebuild decided on the device.  Four short launches, no host round trip.
-int maintain_table(mrh_ctx* c, bool force_census) {
-  if (c->pending || c->census_period < 0) return MRH_OK;
-  if (!force_census && !c->table_dirty && c->frames_since_census < (uint64_t) c->census_period) return MRH_OK;
-  hipStream_t s = c->stream;
-  const Tab& t = c->tab;
-  const int grid = (int) std::min<uint64_t>(2048, (c->slots + 255) / 256);
-  k_table_census<<<grid, 256, 0, s>>>(t, (size_t) c->slots);
-  k_rehash_decide<<<1, 1, 0, s>>>(t, (u32) (c->slots / 4), c->census_force);
-  k_rehash_clear<<<grid, 256, 0, s>>>(t, (size_t) c->slots);
-  k_rehash_insert<<<1024, 256, 0, s>>>(t);
-  c->frames_since_census = 0;
-  c->table_dirty = false;
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
-
 int ensure_device(mrh_ctx* c, const char* who) {
   if (!c) return MRH_ERR_INVALID_ARG;
   hipError_t e = hipSetDevice(c->device);
@@ -126,8 +109,8 @@ int ensure_ready(mrh_ctx* c, const char* who) {
   if (rc) return rc;
   rc = flush_deferred(c);  // a host-fed frame that mrh_integrate kept back runs before anything else looks at the map
   if (rc < 0) return rc;
-  if (c->stream_front) c->front_needs_sync = true;  // whatever this call does to the map, the front stream must see it before its next launch
-  c->flushed_since_frame = true;
+  main_stream_changed_map(c);  // whatever this call does to the map, the front stream must see it before its next launch
+  c->ps.flushed_since_frame = true;
   return strict_point(c);
 }
 
@@ -140,25 +123,6 @@ int ensure_h_mc(mrh_ctx* c) {
   HIP_TRY(c, pinned_alloc(c, c->h_mc, HMC_SLOTS * sizeof(u64)));
   memset(c->h_mc, 0, HMC_SLOTS * sizeof(u64));
   return MRH_OK;
-}
-
-// What every frame — images or a scan — does to the table before its kernels: the upkeep rebuilds from the descriptors, so the
-// zombies of the pipelined frames leave first
-int frame_upkeep(mrh_ctx* c) {
-  if (c->zombies_possible && c->census_period >= 0 && (c->table_dirty || c->frames_since_census >= (uint64_t) c->census_period)) {
-    const int rc = strict_point(c);
-    if (rc) return rc;
-  }
-  const int rc = maintain_table(c, false);
-  if (rc) return rc;
-  c->frames_since_census++;
-  return MRH_OK;
-}
-
-// coarse free-list refill of a multi-resolution map, decided on the device (vds.cu:885-891, :1048-1054)
-void refill_coarse(mrh_ctx* c) {
-  k_refill_decide<<<1, 64, 0, c->stream>>>(c->tab, c->low_blocks_to_allocate, c->d_flag);
-  k_refill<<<(c->low_blocks_to_allocate + 255) / 256, 256, 0, c->stream>>>(c->tab, c->low_blocks_to_allocate, c->d_flag);
 }
 
 // flatAndReduceHashTable() without a camera: every live block onto the compact list (no frustum filter); enqueue only
@@ -208,128 +172,9 @@ int arena_layout(mrh_ctx* c, const int slot, MeshScratch* m, Layout&& lay) {
   return MRH_OK;
 }
 
-int ensure_zbuf(mrh_ctx* c, size_t npix) { return regrow(c, c->d_zbuf, c->zbuf_n, npix, 2 * npix * sizeof(u64)); }
-
-// A starve frame of a single-resolution, unsharded map on the two-launch path: behind the frame's k_back<FREE = false>, the two
-// min-passes and the tail (pass 2 + summaries + garbage collection + the other z-buffer pair cleared) — three launches on the main
-// stream, nothing of the pipeline flushed.  lz: 2 = a pipelined frame (collected blocks become zombies), 0 = a serial frame.
-int launch_starve_fused(mrh_ctx* c, const Cam& k, const Fast& f, const Lists& L, const int set, const float thr, const u32 stamp, const int lz) {
-  const size_t npix = (size_t) k.rows * k.cols;
-  hipStream_t s = c->stream;
-  if (c->zfused_n < npix) {
-    c->zfused_clean[0] = c->zfused_clean[1] = false;
-    const int rc = regrow(c, c->d_zfused, c->zfused_n, npix, 4 * npix * sizeof(u64));
-    if (rc) return rc;
-  }
-  if (c->zfused_clean_npix != npix) c->zfused_clean[0] = c->zfused_clean[1] = false;  // the camera changed size since the pairs were cleared
-  c->zfused_clean_npix = npix;
-  const int p = c->zfused_next, q = p ^ 1;
-  u64* z0 = c->d_zfused + (size_t) p * 2 * c->zfused_n;
-  u64* z1 = z0 + npix;
-  u64* other = c->d_zfused + (size_t) q * 2 * c->zfused_n;
-  // "empty" = INT64_MAX: above every key (depth bits of a finite positive float < 0x7F800000)
-  if (!c->zfused_clean[p]) k_fill_u64<<<256, 256, 0, s>>>(z0, 2 * npix, 0x7FFFFFFFFFFFFFFFull);
-  c->zfused_clean[p] = false;
-  const int grid = 2048;  // x 4 waves, one block each per round
-  if (k.model) {
-    k_starve_z<0, true><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L.vis, set, z0, z1);
-    k_starve_z<1, true><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L.vis, set, z0, z1);
-    if (lz == 2) k_starve_tail<2, true><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L, set, thr, stamp, z0, z1, other, 2 * npix);
-    else k_starve_tail<0, true><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L, set, thr, stamp, z0, z1, other, 2 * npix);
-  } else {
-    k_starve_z<0, false><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L.vis, set, z0, z1);
-    k_starve_z<1, false><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L.vis, set, z0, z1);
-    if (lz == 2) k_starve_tail<2, false><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L, set, thr, stamp, z0, z1, other, 2 * npix);
-    else k_starve_tail<0, false><<<grid, 256, 0, s>>>(k, c->map, c->tab, f, L, set, thr, stamp, z0, z1, other, 2 * npix);
-  }
-  HIP_TRY(c, hipGetLastError());
-  c->zfused_clean[q] = true;
-  c->zfused_next = q;
-  c->n_starve_fused++;
-  return MRH_OK;
-}
-// may this frame's starve step take the three fused launches?  (tile-sharded maps reduce the z-buffers over the ranks between the
-// passes, multi-resolution and general frames walk lists of another kind: they keep k_starve<0,1,2>)
-bool starve_fused_ok(const mrh_ctx* c) { return c->starve_fused && c->p.shard_count <= 1 && !c->tab.multi_res && !c->frame_general; }
-
-// one of the three starve passes over the current compact (fast path: visible) list
-int launch_starve(mrh_ctx* c, int pass) {
-  const Cam& k = c->cam;
-  const size_t npix = (size_t) k.rows * k.cols;
-  hipStream_t s = c->stream;
-  if (pass == 0) {
-    int rc = ensure_zbuf(c, npix);
-    if (rc) return rc;
-    // "empty" = INT64_MAX: above every key (depth bits of a finite positive float < 0x7F800000) in both the
-    // unsigned and the signed reading, so shards can be min-reduced as int64
-    k_fill_u64<<<256, 256, 0, s>>>(c->d_zbuf, 2 * npix, 0x7FFFFFFFFFFFFFFFull);
-    k_starve<0><<<c->integrate_grid, 512, 0, s>>>(k, c->map, c->tab, c->d_zbuf, c->d_zbuf + npix);
-  } else if (pass == 1) {
-    k_starve<1><<<c->integrate_grid, 512, 0, s>>>(k, c->map, c->tab, c->d_zbuf, c->d_zbuf + npix);
-  } else {
-    k_starve<2><<<c->integrate_grid, 512, 0, s>>>(k, c->map, c->tab, c->d_zbuf, c->d_zbuf + npix);
-  }
-  return MRH_OK;
-}
-
-// everything of a frame that follows the starve step
-int frame_tail(mrh_ctx* c, bool starved, int max_num_frames) {
-  hipStream_t s = c->stream;
-  const Cam& k = c->cam;
-  const Map& m = c->map;
-  const Tab& t = c->tab;
-  const float thr = m.trunc + m.trunc_scale * k.max_depth;  // getTruncation(camera.maxDepth(), ...), vds.cu:1720
-  if (c->frame_general) {  // garbageCollectIdentify + garbageCollectFree over the compact list (vds.cu:1674-1713, :1827-1844)
-    if (max_num_frames > 0) {
-      k_gc_identify<<<c->integrate_grid, 512, 0, s>>>(t, thr, c->d_decision);
-      if (c->profile) k_gc_free<true><<<256, 256, 0, s>>>(t, c->d_decision);
-      else k_gc_free<false><<<256, 256, 0, s>>>(t, c->d_decision);
-    }
-    if (!t.multi_res) c->fast_summaries_stale = true;  // the general kernels do not maintain the fast path's GC summaries
-  } else if (!t.multi_res) {
-    if (starved) k_summarize_visible<<<1024, 256, 0, s>>>(t, c->fast);  // weights changed: the GC summaries follow the payload
-    if (max_num_frames > 0 && !c->frame_gc_inline) {
-      const Lists L = {t.compact, c->fast.bbox, c->d_cfree, c->d_zmin, (u32) c->num_blocks};
-      k_free_lists<<<256, 256, 0, s>>>(t, c->fast, L, c->frame_parity, thr);
-    }
-  }
-  c->frames++;
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
-
-// starve (voxel_data_structures.cpp:139) + the rest of the frame; sharded contexts stop for the host's min-reduction
-int starve_and_tail(mrh_ctx* c, int max_num_frames) {
-  const bool starve = max_num_frames > 0 && c->frames > 0 && c->frames % (uint64_t) max_num_frames == 0;
-  if (starve) {
-    int rc = launch_starve(c, 0);
-    if (rc) return rc;
-    if (c->p.shard_count > 1 && c->comm) {
-      // a communicator is attached: the two min-reductions over the shards run on this stream, between the passes —
-      // ncclAllReduce(int64, MIN) over xGMI, no host synchronisation, the frame stays one enqueue
-      const size_t npix = (size_t) c->cam.rows * c->cam.cols;
-      rc = comm_allreduce_zbuf(c, c->d_zbuf, npix);
-      if (rc) return rc;
-      if ((rc = launch_starve(c, 1))) return rc;
-      rc = comm_allreduce_zbuf(c, c->d_zbuf + npix, npix);
-      if (rc) return rc;
-      if ((rc = launch_starve(c, 2))) return rc;
-      return frame_tail(c, starve, max_num_frames);
-    }
-    if (c->p.shard_count > 1) {
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      c->pending = 1;
-      c->pending_max_frames = max_num_frames;
-      return MRH_PENDING_EXCHANGE;
-    }
-    if ((rc = launch_starve(c, 1))) return rc;
-    if ((rc = launch_starve(c, 2))) return rc;
-  }
-  return frame_tail(c, starve, max_num_frames);
-}
-
 }  // namespace
 
+#include "mrh_frame.h"
 #include "mrh_extract.h"
 #include "mrh_points.h"
 #include "mrh_blocks.h"
@@ -577,609 +422,21 @@ int mrh_set_rgb_device(mrh_ctx* c, const uint8_t* d_rgb, int rows, int cols) {
   return MRH_OK;
 }
 
-// voxel_data_structures.cpp:90-110 VoxelContainer::integrate, as one sync-free kernel chain
-static int integrate_frame(mrh_ctx* c, int n_frames_invalidate);
-
-static int integrate_checks(mrh_ctx* c);
-static void prewarm_maybe(mrh_ctx* c);
+// voxel_data_structures.cpp:90-110 VoxelContainer::integrate, as one sync-free kernel chain (mrh_frame.h)
 int mrh_integrate(mrh_ctx* c, int n_frames_invalidate) {
   int rc = ensure_device(c, "mrh_integrate");
   if (rc) return rc;
   rc = flush_deferred(c);  // the frame of the previous call: its images have landed meanwhile
   if (rc < 0) return rc;
-  // is this a frame of host images whose transfers are still on their way?
-  const bool up_d = c->up_depth.cur >= 0 && c->d_depth == c->up_depth.s[c->up_depth.cur].d && !c->up_depth.waited[0] && !c->up_depth.waited[1];
-  const bool up_c = c->up_rgb.cur >= 0 && c->d_rgb == c->up_rgb.s[c->up_rgb.cur].d && !c->up_rgb.waited[0] && !c->up_rgb.waited[1];
-  if (c->defer_uploads && (up_d || up_c) && c->p.shard_count <= 1 && !c->comm && !c->profile) {
-    rc = integrate_checks(c);  // what can be wrong with the call is reported by the call
-    if (rc) return rc;
-    mrh_ctx::DeferredFrame& d = c->deferred;
-    d.on = true;
-    d.n_inval = n_frames_invalidate;
-    d.cam = c->cam;
-    d.d_depth = c->d_depth; d.d_rgb = c->d_rgb;
-    d.depth_rows = c->depth_rows; d.depth_cols = c->depth_cols; d.rgb_rows = c->rgb_rows; d.rgb_cols = c->rgb_cols;
-    const UpRing* rings[2] = {&c->up_depth, &c->up_rgb};
-    for (int i = 0; i < 2; i++) d.ring[i] = {rings[i]->cur, rings[i]->last_copy, {rings[i]->waited[0], rings[i]->waited[1]}};
-    return MRH_OK;
-  }
-  rc = integrate_frame(c, n_frames_invalidate);
-  if (rc < 0) return rc;
-  const int mrc = mark_frame(c);
-  if (!mrc && rc == MRH_OK) prewarm_maybe(c);
-  return mrc ? mrc : rc;
-}
-
-extern "C++" {
-namespace {
-// runs the frame mrh_integrate kept back, with the inputs it was issued under; the context's current inputs (the next frame's
-// pose and images may have arrived meanwhile) are put back afterwards
-int flush_deferred(mrh_ctx* c) {
-  mrh_ctx::DeferredFrame& d = c->deferred;
-  if (!d.on) return MRH_OK;
-  d.on = false;
-  UpRing* rings[2] = {&c->up_depth, &c->up_rgb};
-  mrh_ctx::DeferredFrame now;
-  now.cam = c->cam;
-  now.d_depth = c->d_depth; now.d_rgb = c->d_rgb;
-  now.depth_rows = c->depth_rows; now.depth_cols = c->depth_cols; now.rgb_rows = c->rgb_rows; now.rgb_cols = c->rgb_cols;
-  for (int i = 0; i < 2; i++) now.ring[i] = {rings[i]->cur, rings[i]->last_copy, {rings[i]->waited[0], rings[i]->waited[1]}};
-  c->cam = d.cam;
-  c->d_depth = d.d_depth; c->d_rgb = d.d_rgb;
-  c->depth_rows = d.depth_rows; c->depth_cols = d.depth_cols; c->rgb_rows = d.rgb_rows; c->rgb_cols = d.rgb_cols;
-  for (int i = 0; i < 2; i++) { rings[i]->cur = d.ring[i].cur; rings[i]->last_copy = d.ring[i].last_copy; rings[i]->waited[0] = d.ring[i].waited[0]; rings[i]->waited[1] = d.ring[i].waited[1]; }
-  int rc = integrate_frame(c, d.n_inval);
-  if (rc >= 0) {
-    const int mrc = mark_frame(c);
-    if (mrc) rc = mrc;
-  }
-  c->cam = now.cam;
-  c->d_depth = now.d_depth; c->d_rgb = now.d_rgb;
-  c->depth_rows = now.depth_rows; c->depth_cols = now.depth_cols; c->rgb_rows = now.rgb_rows; c->rgb_cols = now.rgb_cols;
-  for (int i = 0; i < 2; i++) {
-    rings[i]->cur = now.ring[i].cur;
-    if (now.ring[i].last_copy != d.ring[i].last_copy) {  // a newer image of this kind has arrived: its transfer has not been waited for
-      rings[i]->last_copy = now.ring[i].last_copy;
-      rings[i]->waited[0] = now.ring[i].waited[0]; rings[i]->waited[1] = now.ring[i].waited[1];
-    }  // else: the same transfer, and what the frame has waited for stays waited for
-  }
+  if (frame_is_deferrable(c)) return defer_frame(c, n_frames_invalidate);
+  rc = run_frame(c, n_frames_invalidate);
+  if (rc == MRH_OK) prewarm_maybe(c);
   return rc;
-}
-
-int take_event_pair(mrh_ctx* c, EvPair& e) {
-  if (!c->ev_pool.empty()) { e = c->ev_pool.back(); c->ev_pool.pop_back(); return MRH_OK; }
-  if (c->ev_pending.size() >= 4096) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int r = drain_events(c);
-    if (r) return r;
-    e = c->ev_pool.back(); c->ev_pool.pop_back();
-    return MRH_OK;
-  }
-  HIP_TRY(c, event_new(c, e.a, true)); HIP_TRY(c, event_new(c, e.b, true));
-  return MRH_OK;
-}
-
-// the lists of ring slot i; slot 0's are the context's own (serial frames, the starve passes, frame_tail)
-Lists ring_lists(const mrh_ctx* c, const int i) {
-  if (i == 0) return Lists{c->tab.compact, c->fast.bbox, c->d_cfree, c->d_zmin, (u32) c->num_blocks};
-  return Lists{c->ring_vis[i], c->ring_bbox[i], c->ring_cfree[i], c->ring_zmin[i], (u32) c->num_blocks};
-}
-
-// k_back's and k_front's arguments, in the kernels' parameter order (mrh_fast2.h)
-struct BackArgs {
-  Cam c; Map m; Tab t; Fast f; Lists L;
-  int set, zero_set;
-  float thr;
-  const float* depth_raw; const uint8_t* rgb_raw; u32* deferred;  // the fused multi-resolution frame's re-integration
-  u32 want_stamp; int seq;
-};
-struct FrontArgs {
-  Cam c; Map m; Tab t; Fast f; Lists L;
-  const float* depth; const uint8_t* rgb;
-  int tiles_x, n_tiles; u32 stamp; int set, gc_on; float thr;
-  int n_refill, low_blocks_to_allocate; const int* refill_flag;  // the fused multi-resolution frame's coarse-list refill
-};
-
-// Profile mode (`ev` given): the event pair is attached to the launch itself (hipExtLaunchKernelGGL), so it holds the kernel's own
-// begin / end timestamps — the duration rocprofv3 reports — instead of a hipEventRecord bracket, which adds the dispatch latency of
-// a dependent launch (~3.5 us here) to every sample.
-template <bool FREE, bool PROFILE, bool MULTI, bool SAFEDIV, int LZ, bool SPH>
-void back_as(const int grid, hipStream_t s, const EvPair* ev, const BackArgs& a) {
-  const size_t lds = (size_t) 4 * kTileMaxPx * sizeof(uint2);  // one tile per wave
-  if (ev) hipExtLaunchKernelGGL((k_back<FREE, PROFILE, MULTI, SAFEDIV, LZ, SPH>), dim3(grid), dim3(256), (uint32_t) lds, s, ev->a, ev->b, 0u,
-                                a.c, a.m, a.t, a.f, a.L, a.set, a.zero_set, a.thr, a.depth_raw, a.rgb_raw, a.deferred, a.want_stamp, a.seq);
-  else k_back<FREE, PROFILE, MULTI, SAFEDIV, LZ, SPH><<<grid, 256, lds, s>>>(a.c, a.m, a.t, a.f, a.L, a.set, a.zero_set, a.thr, a.depth_raw, a.rgb_raw,
-                                                                             a.deferred, a.want_stamp, a.seq);
-}
-template <bool FREE, bool PROFILE, int LZ>
-void back_single_res(const bool safe_div, const bool sph, const int grid, hipStream_t s, const EvPair* ev, const BackArgs& a) {
-  if (safe_div && sph) back_as<FREE, PROFILE, false, true, LZ, true>(grid, s, ev, a);
-  else if (safe_div) back_as<FREE, PROFILE, false, true, LZ, false>(grid, s, ev, a);
-  else if (sph) back_as<FREE, PROFILE, false, false, LZ, true>(grid, s, ev, a);
-  else back_as<FREE, PROFILE, false, false, LZ, false>(grid, s, ev, a);
-}
-// The one launch site of k_back.  The runtime flags, in the kernel's template order, pick one of the instantiations the library
-// builds: single-resolution frames FREE x SAFEDIV x LZ (0: serial, 2: pipelined) x SPH, with the roofline counters (PROFILE) on
-// the profile launches of the frames that collect inline — a starve frame's profile launch carries its event pair only —; the
-// fused multi-resolution frame FREE, MULTI x SAFEDIV (never profiled, pipelined or spherical).
-void launch_back(const bool free_, const bool multi, const bool safe_div, const int lz, const bool sph, const int grid, hipStream_t s, const EvPair* ev,
-                 const BackArgs& a) {
-  if (multi) {
-    if (safe_div) back_as<true, false, true, true, 0, false>(grid, s, ev, a);
-    else back_as<true, false, true, false, 0, false>(grid, s, ev, a);
-  } else if (lz == 2) {
-    if (free_ && ev) back_single_res<true, true, 2>(safe_div, sph, grid, s, ev, a);
-    else if (free_) back_single_res<true, false, 2>(safe_div, sph, grid, s, ev, a);
-    else back_single_res<false, false, 2>(safe_div, sph, grid, s, ev, a);
-  } else {
-    if (free_ && ev) back_single_res<true, true, 0>(safe_div, sph, grid, s, ev, a);
-    else if (free_) back_single_res<true, false, 0>(safe_div, sph, grid, s, ev, a);
-    else back_single_res<false, false, 0>(safe_div, sph, grid, s, ev, a);
-  }
-}
-
-template <bool PROFILE, bool MULTI, bool LAZY, bool SPH>
-void front_as(const int grid, hipStream_t s, const EvPair* ev, const FrontArgs& a) {
-  if (ev) hipExtLaunchKernelGGL((k_front<PROFILE, MULTI, LAZY, SPH>), dim3(grid), dim3(256), 0, s, ev->a, ev->b, 0u, a.c, a.m, a.t, a.f, a.L, a.depth, a.rgb,
-                                a.tiles_x, a.n_tiles, a.stamp, a.set, a.gc_on, a.thr, a.n_refill, a.low_blocks_to_allocate, a.refill_flag);
-  else k_front<PROFILE, MULTI, LAZY, SPH><<<grid, 256, 0, s>>>(a.c, a.m, a.t, a.f, a.L, a.depth, a.rgb, a.tiles_x, a.n_tiles, a.stamp, a.set, a.gc_on, a.thr,
-                                                               a.n_refill, a.low_blocks_to_allocate, a.refill_flag);
-}
-template <bool PROFILE>
-void front_single_res(const bool lazy, const bool sph, const int grid, hipStream_t s, const EvPair* ev, const FrontArgs& a) {
-  if (lazy && sph) front_as<PROFILE, false, true, true>(grid, s, ev, a);
-  else if (lazy) front_as<PROFILE, false, true, false>(grid, s, ev, a);
-  else if (sph) front_as<PROFILE, false, false, true>(grid, s, ev, a);
-  else front_as<PROFILE, false, false, false>(grid, s, ev, a);
-}
-// The one launch site of k_front: single-resolution frames PROFILE (= a profile launch, `ev` given) x LAZY x SPH, the fused
-// multi-resolution frame MULTI alone.
-void launch_front(const bool multi, const bool lazy, const bool sph, const int grid, hipStream_t s, const EvPair* ev, const FrontArgs& a) {
-  if (multi) front_as<false, true, false, false>(grid, s, nullptr, a);
-  else if (ev) front_single_res<true>(lazy, sph, grid, s, ev, a);
-  else front_single_res<false>(lazy, sph, grid, s, nullptr, a);
-}
-
-// the integration of the oldest pending pipelined frame, behind its front half
-int launch_pending(mrh_ctx* c, const bool count_skips = false) {
-  if (!c->npend) return MRH_OK;
-  const mrh_ctx::PendingBack pb = c->pendq[0];  // the oldest
-  for (int i = 1; i < c->npend; i++) c->pendq[i - 1] = c->pendq[i];
-  c->npend--;
-  hipStream_t s = c->stream;
-  const hipError_t q = c->pipe_always_wait ? hipErrorNotReady : hipEventQuery(c->ev_front[pb.ring]);
-  if (q == hipErrorNotReady) {
-    (void) hipGetLastError();
-    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_front[pb.ring], 0));
-    c->dbg_waits++;
-  } else if (q != hipSuccess) {
-    return fail(c, MRH_ERR_DEVICE, "mrh_integrate: front half of a pipelined frame: %s", hipGetErrorString(q));
-  }
-  const Map& m = c->map;
-  const Tab& t = c->tab;
-  if (count_skips) HIP_TRY(c, hipMemsetAsync(&c->tab.ctr[CTR_ZSKIP], 0, sizeof(int), s));  // mrh_get_stats: M of the last frame, exactly
-  if (pb.profile)  // U and M of the frame (device-side counters of the roofline numerator): after its front half, before its integration
-    k_count_updates<<<c->fused_grid, 256, 0, s>>>(pb.cam, m, t, pb.f, c->d_cnt_partials, CTR_SET0 + 4 * pb.set, pb.L.vis, pb.L.cfree, pb.stamp, pb.count_zombies ? 1 : 0);
-  launch_back(pb.free_, false, pb.safe_div, 2, pb.sph, c->pipe_grid, s, pb.profile ? &pb.ev : nullptr,
-              {pb.cam, m, t, pb.f, pb.L, pb.set, pb.zero_set, pb.thr, nullptr, nullptr, nullptr, pb.stamp, pb.seq});
-  if (pb.profile) c->ev_pending.push_back(pb.ev);
-  if (pb.free_) c->zombies_possible = true;
-  if (pb.starve) {
-    const int src = launch_starve_fused(c, pb.cam, pb.f, pb.L, pb.set, pb.thr, pb.stamp, 2);
-    if (src) return src;
-    c->zombies_possible = true;
-  }
-  HIP_TRY(c, hipGetLastError());
-  // the frame's pool report (mark_frame left it to this launch): behind its integration
-  return pb.report_seq && c->peek_enabled ? post_report(c, pb.report_seq, s) : MRH_OK;
-}
-
-// Behind the pipelined frames issued so far (their integrations are all on the main stream, each behind its front half), the
-// zombies nobody wanted leave the table: k_reclaim runs alone on the main stream — the front stream is idle once the last
-// integration has started, and nothing is enqueued on it before the host has seen the main stream drain (front_needs_sync).
-int strict_point(mrh_ctx* c) {
-  while (c->npend) {
-    const int rc = launch_pending(c, c->npend == 1);
-    if (rc) return rc;
-  }
-  if (!c->zombies_possible) return MRH_OK;
-  k_reclaim<<<64, 256, 0, c->stream>>>(c->tab, c->fast);
-  k_reclaim_done<<<1, 1, 0, c->stream>>>(c->tab);
-  // the pool report of the newest mark now understates the free list by the zombies that have just left: written again behind the
-  // reclaim, so that a peek after mrh_sync (or after any other flush) reads the level the flush left (with the reclaim period at 64
-  // frames the difference is no longer a handful of blocks)
-  if (c->peek_enabled && c->frame_seq > 1) {
-    const uint64_t seq = c->frame_seq - 1;
-    if (c->peek_seq[seq % 8] == seq && c->peek_done[seq % 8]) {
-      if (const int rc = post_report(c, seq, c->stream)) return rc;
-    }
-  }
-  c->zombies_possible = false;
-  c->lazy_run = 0;
-  c->front_needs_sync = true;
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
-}
-
-// the pipelining state (mrh_ctx::pipe)
-int ensure_pipe_state(mrh_ctx* c) {
-  if (c->stream_front) return MRH_OK;
-  const size_t cap = c->num_blocks;
-  // the stream comes last: it is what says "the state exists", and a step that failed is taken again by the next call
-  // (hipEventDisableSystemFence on these events — they order two streams of one device — was measured in round 5: no difference)
-  for (hipEvent_t& e : c->ev_front) if (!e) HIP_TRY(c, event_new(c, e, false));
-  for (int i = 1; i < kPipeRing; i++) {
-    if (!c->ring_vis[i]) HIP_TRY(c, dev_alloc(c, c->ring_vis[i], cap * sizeof(int4)));
-    if (!c->ring_bbox[i]) HIP_TRY(c, dev_alloc(c, c->ring_bbox[i], cap * sizeof(int4)));
-    if (!c->ring_cfree[i]) HIP_TRY(c, dev_alloc(c, c->ring_cfree[i], cap * sizeof(int4)));
-    if (!c->ring_zmin[i]) HIP_TRY(c, dev_alloc(c, c->ring_zmin[i], cap * sizeof(float)));
-  }
-  if (!c->fast.zlist) HIP_TRY(c, dev_alloc(c, c->fast.zlist, cap * sizeof(int4)));
-  if (!c->want_ring) HIP_TRY(c, dev_alloc(c, c->want_ring, (size_t) kPipeRing * c->slots * sizeof(u32)));
-  HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), c->stream));  // stamps start at 1
-  if (!c->h_levels) HIP_TRY(c, pinned_alloc(c, c->h_levels, 4 * sizeof(int)));
-  // (a high-priority front stream, a ring of eight and integrations deferred by two calls were measured: no difference)
-  HIP_TRY(c, hipStreamCreateWithFlags(&c->stream_front, hipStreamNonBlocking));
-  c->h_levels[0] = (int) c->num_blocks - 1; c->h_levels[1] = 0; c->h_levels[2] = -1;
-  c->tab.h_levels = c->h_levels;
-  c->front_needs_sync = true;  // the memset above
-  return MRH_OK;
-}
-
-// Fast::dcx of the two-launch frames, grow-only: one image per ring slot with the pipelining state, slot 0's alone without it
-int ensure_frame_dcx(mrh_ctx* c, const size_t npix) {
-  if (c->pipe_npix >= npix) return MRH_OK;
-  {
-    const int rc = strict_point(c);  // the pending integrations read the buffers that are about to go
-    if (rc) return rc;
-  }
-  if (c->stream_front) HIP_TRY(c, hipStreamSynchronize(c->stream_front));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (uint2*& d : c->pipe_dcx) HIP_TRY(c, dev_free(c, d));
-  c->pipe_npix = 0;
-  const int n = c->stream_front ? kPipeRing : 1;
-  for (int i = 0; i < n; i++) HIP_TRY(c, dev_alloc(c, c->pipe_dcx[i], npix * sizeof(uint2)));
-  c->pipe_npix = npix;
-  return MRH_OK;
-}
-
-// room in the pool, as the last integration launch reported it (a few frames old: the margins are generous).  Pipelining state only.
-bool pool_roomy(const mrh_ctx* c) {
-  const int64_t free_known = (int64_t) ((volatile int*) c->h_levels)[0] + 1, zombies_known = ((volatile int*) c->h_levels)[1];
-  return free_known >= (int64_t) (c->num_blocks / 4) && zombies_known <= (int64_t) (c->num_blocks / 8);
-}
-
-// One frame of a single-resolution map (pinhole or spherical camera):
-//   pipelined: front stream: k_front<LAZY> (+ event) | main stream: wait for that event, k_back<LZ = 2>.  The front stream never
-//              waits for the main one, so this frame's front half runs next to the integration of the frame(s) before it;
-//              the host only holds back when it is kPipeRing - 1 frames ahead of the integration that has started.
-//   serial:    [k_reclaim] -> k_front -> k_back (-> the starve passes), all on the main stream, no zombies anywhere.
-// A serial frame comes with MRH_PIPE=0, after anything else touched the map, every `pipe_period` frames (the reclaim bounds the
-// zombies), on starve frames that cannot stay in the pipeline, and while the pool is short of room: zombies hold their pool slots
-// until the reclaim, so a pool that is nearly full is fused serially — the reference's accounting, exactly.
-int integrate_single_res_frame(mrh_ctx* c, const int max_num_frames, const bool starve_now) {
-  int rc = MRH_OK;
-  hipStream_t s = c->stream;
-  const Cam& k = c->cam;
-  const Map& m = c->map;
-  const Tab& t = c->tab;
-  const size_t npix = (size_t) k.rows * k.cols;
-  if (c->pipe) {
-    rc = ensure_pipe_state(c);
-    if (rc) return rc;
-  }
-  rc = ensure_frame_dcx(c, npix);
-  if (rc) return rc;
-  if (c->fast_summaries_stale) {  // a LiDAR scan (general kernels) ran since: rebuild the GC summaries once
-    rc = strict_point(c);
-    if (rc) return rc;
-    k_summarize_all<<<2048, 256, 0, s>>>(t, c->fast);
-    c->fast_summaries_stale = false;
-    c->front_needs_sync = true;
-  }
-  const int tiles_x = (k.cols + kRayTile - 1) / kRayTile, tiles_y = (k.rows + kRayTile - 1) / kRayTile;
-  const int n_tiles = tiles_x * tiles_y;
-  // a caller that synchronises (or asks for statistics, a mesh, ...) after EVERY frame gains nothing from the pipeline and would pay
-  // for its flush each time: three frames in a row that found the pipeline flushed switch to serial frames, the first frame that
-  // follows another frame directly switches back
-  c->sync_streak = c->flushed_since_frame ? c->sync_streak + 1 : 0;
-  c->flushed_since_frame = false;
-  // images that come from the host (mrh_upload_*) make the frame loop host- and link-bound (staging copy + 2.15 MB over PCIe: ~60 us
-  // per frame at 640x480 against ~40 us of GPU work): nothing to gain from overlapping kernels, and the second stream's events
-  // only add to the host's bill (measured: 77 us per frame pipelined, 64 serial) — such frames are fused serially unless
-  // MRH_PIPE_UPLOADS=1 says otherwise (the test-suite sets it, so that its upload-fed streams exercise the pipeline)
-  const bool resident_inputs = c->up_depth.cur < 0 && c->up_rgb.cur < 0;
-  // a starve frame stays a frame of the pipeline when its starve step can take the fused launches (round 6; before: every starve
-  // frame flushed the pipeline, ran serially and left a host synchronisation in front of the next pipelined frame)
-  const bool starve_in_pipe = starve_now && starve_fused_ok(c) && !c->starve_serial;
-  const bool lazy = c->pipe && (!starve_now || starve_in_pipe) && pool_roomy(c) && c->lazy_run < c->pipe_period && c->sync_streak < 3 &&
-                    (resident_inputs || c->pipe_uploads);
-  if (!lazy) {
-    rc = strict_point(c);
-    if (rc) return rc;
-  }
-  rc = send_uploads(c, lazy ? c->stream_front : s);  // the raw images are read by the front half
-  if (rc) return rc;
-  const int seq = (int) (c->pipe_seq & 0x3FFFFFFF);
-  const int ring = lazy ? (int) (c->pipe_seq % kPipeRing) : 0;  // a serial frame runs behind everything on the main stream: any slot
-  c->pipe_seq++;                                                // is free for it, and the starve passes walk slot 0's lists
-  const int set = (int) (c->fast_frames % kListSets), zero_set = (set + kListSets - 1) % kListSets;
-  c->frame_parity = set;
-  c->fast_frames++;
-  c->fast.dcx = c->pipe_dcx[ring];
-  c->fast.want = c->want_ring + (size_t) ring * c->slots;  // (no want stamps without the pipelining state: nullptr)
-  const Fast f = c->fast;
-  const u32 stamp = (u32) ((c->frames + 1) & 0x3FFFFFFFu);
-  const float gc_thr = m.trunc + m.trunc_scale * k.max_depth;  // getTruncation(camera.maxDepth(), ...), vds.cu:1720
-  const bool safe_div = m.half_vs_two_steps || m.wsum_two_steps;  // the short divisions failed their check at mrh_create
-  const bool sph = c->spherical;
-  // GC runs inside k_back unless this is a starve frame (the starve step changes weights after the integrate pass)
-  c->frame_gc_inline = max_num_frames > 0 && !starve_now;
-  const Lists L = ring_lists(c, ring);
-  EvPair ev = {nullptr, nullptr}, evf = {nullptr, nullptr};
-  if (c->profile) {
-    rc = take_event_pair(c, evf);
-    if (rc) return rc;
-    rc = take_event_pair(c, ev);
-    if (rc) return rc;
-  }
-  const FrontArgs front = {k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, set, max_num_frames > 0 ? 1 : 0, gc_thr, 0, 0, nullptr};
-  if (lazy) {
-    if (c->front_needs_sync) {  // the main stream erased keys / pushed the free list (reclaim, a serial frame, any other entry
-      HIP_TRY(c, hipStreamSynchronize(s));  // point) after the front stream last looked: the front half must see all of it
-      c->front_needs_sync = false;
-      c->pipe_base = c->pipe_seq - 1;
-    }
-    // ring slot `ring` was last used by frame seq - kPipeRing; its integration is complete once the one after it has started,
-    // and that one has also cleared the list-counter set this frame appends to
-    {
-      const int64_t need = (int64_t) seq - kPipeRing + 2;
-      if (need > (int64_t) c->pipe_base) {
-        const auto t0 = std::chrono::steady_clock::now();
-        while ((int64_t) ((volatile int*) c->h_levels)[2] < need) {
-          MRH_CPU_RELAX();
-          if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(10)) return fail(c, MRH_ERR_DEVICE, "mrh_integrate: the integration of frame %lld never started", (long long) need);
-        }
-        c->dbg_spin_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-      }
-    }
-    c->dbg_lazy_frames++;
-    const auto t_api = std::chrono::steady_clock::now();
-    launch_front(false, true, sph, n_tiles + c->sweep_wgs, c->stream_front, c->profile ? &evf : nullptr, front);
-    HIP_TRY(c, hipEventRecord(c->ev_front[ring], c->stream_front));
-    if (c->profile) c->ev_pending_front.push_back(evf);
-    // the integration of the PREVIOUS pipelined frame goes out now (its front half ran a frame ago: usually no wait), this
-    // frame's is left for the next call
-    const bool zombies_before = c->zombies_possible;
-    while (c->npend >= c->pipe_defer) {
-      rc = launch_pending(c);
-      if (rc) return rc;
-    }
-    mrh_ctx::PendingBack& pb = c->pendq[c->npend++];
-    pb.on = true;
-    pb.cam = k; pb.f = f; pb.L = L;
-    pb.set = set; pb.zero_set = zero_set; pb.ring = ring; pb.seq = seq; pb.stamp = stamp; pb.thr = gc_thr;
-    pb.free_ = c->frame_gc_inline; pb.profile = c->profile != 0; pb.safe_div = safe_div; pb.sph = sph;
-    pb.count_zombies = zombies_before || c->zombies_possible || c->frame_gc_inline;
-    pb.starve = starve_now;
-    pb.ev = ev;
-    pb.report_seq = 0;
-    c->last_frame_lazy = true;
-    c->lazy_run++;
-    c->frames++;  // frame_tail's bookkeeping; nothing else of it applies (GC runs inside the integration)
-    c->dbg_api_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_api).count();
-    HIP_TRY(c, hipGetLastError());
-    return MRH_OK;
-  }
-  // ---- serial frame, all on the main stream (strict_point above has flushed and reclaimed)
-  c->last_frame_lazy = false;
-  launch_front(false, false, sph, n_tiles + c->sweep_wgs, s, c->profile ? &evf : nullptr, front);
-  if (c->profile) {
-    c->ev_pending_front.push_back(evf);
-    k_count_updates<<<c->fused_grid, 256, 0, s>>>(k, m, t, f, c->d_cnt_partials, CTR_SET0 + 4 * set, L.vis, L.cfree, stamp, 0);
-  }
-  launch_back(c->frame_gc_inline, false, safe_div, 0, sph, c->fused_grid, s, c->profile ? &ev : nullptr,
-              {k, m, t, f, L, set, zero_set, gc_thr, nullptr, nullptr, nullptr, stamp, seq});
-  c->front_needs_sync = true;  // direct frees on the main stream
-  if (c->profile) c->ev_pending.push_back(ev);
-  if (starve_now && starve_fused_ok(c)) {
-    rc = launch_starve_fused(c, k, f, L, set, gc_thr, stamp, 0);
-    if (rc) return rc;
-    c->frames++;  // frame_tail's bookkeeping: the summaries and the garbage collection ran inside the tail launch
-    return MRH_OK;
-  }
-  return starve_and_tail(c, max_num_frames);
-}
-
-// One fused frame of a multi-resolution map, on the main stream: k_front<MULTI> (with the coarse-list refill, vds.cu:885-891),
-// k_back<MULTI> (GC inline, the re-integration of what checkVarSDF reallocated), k_mr_tail.
-int integrate_fused_mr_frame(mrh_ctx* c, const int max_num_frames) {
-  hipStream_t s = c->stream;
-  const Cam& k = c->cam;
-  const Map& m = c->map;
-  const Tab& t = c->tab;
-  int rc = ensure_frame_dcx(c, (size_t) k.rows * k.cols);
-  if (rc) return rc;
-  c->fast.dcx = c->pipe_dcx[0];
-  const Fast& f = c->fast;
-  const int parity = (int) (c->fast_frames % kListSets), zero_set = (parity + kListSets - 1) % kListSets;  // the frame's list-counter set, and the one to clear
-  c->frame_parity = parity;
-  c->fast_frames++;
-  const u32 stamp = (u32) ((c->frames + 1) & 0x3FFFFFFFu);
-  const float gc_thr = m.trunc + m.trunc_scale * k.max_depth;  // getTruncation(camera.maxDepth(), ...), vds.cu:1720
-  const Lists L = ring_lists(c, 0);
-  const bool safe_div = m.half_vs_two_steps || m.wsum_two_steps;  // the short divisions failed their check at mrh_create
-  const int tiles_x = (k.cols + kRayTile - 1) / kRayTile, tiles_y = (k.rows + kRayTile - 1) / kRayTile;
-  const int n_tiles = tiles_x * tiles_y;
-  if (!c->mr_summaries_valid) {
-    k_summarize_all<<<2048, 256, 0, s>>>(t, f);
-    c->mr_summaries_valid = true;
-  }
-  c->frame_gc_inline = true;
-  // the coarse-list refill rides in k_front; its test was taken by the previous frame's k_mr_tail unless something else touched
-  // the coarse list since (general frames, import, stream-out, reset)
-  if (!c->refill_flag_valid) k_refill_decide<<<1, 64, 0, s>>>(t, c->low_blocks_to_allocate, c->d_flag);
-  const int n_refill = (c->low_blocks_to_allocate + 255) / 256;
-  launch_front(true, false, false, n_tiles + c->sweep_wgs_mr + n_refill, s, nullptr,
-               {k, m, t, f, L, c->d_depth, c->d_rgb, tiles_x, n_tiles, stamp, parity, 1, gc_thr, n_refill, c->low_blocks_to_allocate, c->d_flag});
-  launch_back(true, true, safe_div, 0, false, c->fused_grid, s, nullptr,
-              {k, m, t, f, L, parity, zero_set, gc_thr, c->d_depth, c->d_rgb, (u32*) c->d_reint, 0u, 0});
-  k_mr_tail<<<1, 256, 0, s>>>(t, (const u32*) c->d_reint, c->low_blocks_to_allocate, c->d_flag);
-  rc = starve_and_tail(c, max_num_frames);
-  c->refill_flag_valid = rc == MRH_OK;
-  return rc;
-}
-
-// One frame of a multi-resolution map through the general kernels (mrh_kernels.h), on the main stream.
-int integrate_general_frame(mrh_ctx* c, const int max_num_frames) {
-  hipStream_t s = c->stream;
-  const Cam& k = c->cam;
-  const Map& m = c->map;
-  const Tab& t = c->tab;
-  refill_coarse(c);
-  // the image every kernel below reads as "depth": the raw image (pinhole: cloud z == depth, cleaned on the fly) or, for
-  // the spherical model, getDepth(cloud) computed once per frame
-  const float* depth_img = c->d_depth;
-  if (c->spherical) {
-    const size_t npix = (size_t) k.rows * k.cols;
-    const int rc = regrow(c, c->d_cloud, c->cloud_n, npix, npix * sizeof(float));
-    if (rc) return rc;
-    k_cloud_depth<<<(int) ((npix + 255) / 256), 256, 0, s>>>(k, c->d_depth, c->d_cloud);
-    depth_img = c->d_cloud;
-  }
-  const dim3 tiles((k.cols + kTile - 1) / kTile, (k.rows + kTile - 1) / kTile);
-  if (c->profile) k_alloc<true><<<tiles, dim3(kTile, kTile), 0, s>>>(k, m, t, depth_img);
-  else k_alloc<false><<<tiles, dim3(kTile, kTile), 0, s>>>(k, m, t, depth_img);
-  k_compact<<<512, 256, 0, s>>>(k, m, t, 1);
-
-  if (c->profile) {
-    EvPair ev;
-    const int rc = take_event_pair(c, ev);
-    if (rc) return rc;
-    HIP_TRY(c, hipEventRecord(ev.a, s));
-    k_integrate<true><<<c->integrate_grid, 512, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_upd_partials);
-    HIP_TRY(c, hipEventRecord(ev.b, s));
-    c->ev_pending.push_back(ev);
-  } else {
-    k_integrate<false><<<c->integrate_grid, 512, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_upd_partials);
-  }
-
-  if (c->frames > 0) {
-    // checkVarSDF -> reallocBlocks -> flatAndReduceHashTable(camera) -> reintegrateDepthMap
-    HIP_TRY(c, hipMemsetAsync(&t.ctr[CTR_NREALLOC], 0, 2 * sizeof(int), s));  // NREALLOC, NREINT
-    k_check_var<<<2048, 64, 0, s>>>(m, t, c->d_realloc);
-    k_realloc<<<64, 256, 0, s>>>(t, c->d_realloc, c->d_reint);
-    k_compact<<<512, 256, 0, s>>>(k, m, t, 1);
-    k_reintegrate<<<1024, 64, 0, s>>>(k, m, t, depth_img, c->d_rgb, c->d_reint);
-  }
-
-  return starve_and_tail(c, max_num_frames);
-}
-
-}  // namespace
-}  // extern "C++"
-
-// what mrh_integrate rejects before it touches the device
-static int integrate_checks(mrh_ctx* c) {
-  if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_integrate: an exchange is pending (call mrh_integrate_resume)");
-  if (c->halo_upper) return fail(c, MRH_ERR_STATE, "mrh_integrate: halo blocks of other shards are present (call mrh_drop_blocks(MRH_DROP_HALO) after the extraction)");
-  if (!c->has_camera) return fail(c, MRH_ERR_STATE, "mrh_integrate: set_camera has not been called");
-  if (c->comm && c->p.shard_count > 1) {  // the starve all-reduce runs over the communicator's ranks: they must be this map's shards
-    int cr = 0, cw = 1;
-    // MRH_COMM_ALLOW_SHARD_MISMATCH=1 is a test hook for one-GPU boxes (a one-rank group reducing the buffer of one of two shards)
-    if (!comm_matches_sharding(c, &cr, &cw) && !getenv("MRH_COMM_ALLOW_SHARD_MISMATCH"))
-      return fail(c, MRH_ERR_STATE, "mrh_integrate: the context is shard %d of %d, the attached communicator rank %d of %d", c->p.shard_rank, c->p.shard_count, cr, cw);
-  }
-  if (!c->d_depth || !c->d_rgb) return fail(c, MRH_ERR_STATE, "mrh_integrate: depth and rgb images are required");
-  const Cam& k = c->cam;
-  if (c->depth_rows != k.rows || c->depth_cols != k.cols || c->rgb_rows != k.rows || c->rgb_cols != k.cols)
-    return fail(c, MRH_ERR_INVALID_ARG, "mrh_integrate: image shape does not match the camera");
-  return MRH_OK;
-}
-
-// see mrh_ctx::prewarm_on
-static void prewarm_maybe(mrh_ctx* c) {
-  if (!c->prewarm_on || c->prewarm_done || c->frames != 3 || c->n_extractions || c->f64_link || c->mesh_on_host || c->pending) return;
-  c->prewarm_done = true;
-  int lev = 0;
-  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&lev, &c->tab.ctr[CTR_HEAP_FINE], sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
-    (void) hipGetLastError();
-    return;
-  }
-  const uint64_t live = (uint64_t) std::max<int64_t>((int64_t) c->num_blocks - ((int64_t) lev + 1), 0);  // fine slots in use (coarse units live in fine slots)
-  const uint64_t nv = live * 64;
-  if (nv < 65536) return;  // a mesh this small costs its first extraction next to nothing
-  try {
-    const size_t nf = (size_t) (nv + nv / 4);  // faces: a little above the vertices (closed surfaces: twice; what is seen of a room: ~1.1 x)
-    size_mesh_staging(c, (size_t) nv, nf);
-    if (c->stage_ctl.data()) memset(c->stage_ctl.data(), 0, c->stage_ctl.cap * sizeof(u32));  // no epoch, no flag of an earlier life
-    c->V.reserve_unpinned((size_t) nv * 3); c->C.reserve_unpinned((size_t) nv * 3);  // never pinned: mapped and faulted in
-    c->V32.clear(); c->C32.clear(); c->F.clear(); c->V.clear(); c->C.clear();  // capacity, not content: the getters still answer "no mesh"
-  } catch (...) {
-    // no memory for it: the first extraction sizes its buffers itself, as it always did
-  }
-  (void) hipGetLastError();
-}
-
-static int integrate_frame(mrh_ctx* c, int n_frames_invalidate) {
-  int rc = integrate_checks(c);
-  if (rc) return rc;
-  const Cam& k = c->cam;
-  const int max_num_frames = n_frames_invalidate < 0 ? c->p.n_frames_invalidate_voxels : n_frames_invalidate;
-  hipStream_t s = c->stream;
-  const Tab& t = c->tab;
-  rc = frame_upkeep(c);
-  if (rc) return rc;
-
-  // Multi-resolution maps take the same two launches when that is exact: the fused kernel checks the variance of a
-  // fine block right after updating it, which covers every block the reference's checkVarSDF can newly decide on —
-  // EXCEPT blocks that changed without being checked (frame 0 is never checked, voxel_data_structures.cpp:99; the starve
-  // step decrements weights after the check; imported blocks) and are then outside the image on the next frame.  Those
-  // frames, and the starve frames themselves, go through the general kernels.
-  const bool starve_now = max_num_frames > 0 && c->frames > 0 && c->frames % (uint64_t) max_num_frames == 0;
-  c->frame_fused_mr = t.multi_res && c->mr_fused && !c->profile && max_num_frames > 0 && !starve_now && !c->mr_next_general &&
-                      c->frames >= 2 && !c->spherical;
-  c->frame_general = t.multi_res && !c->frame_fused_mr;  // (a frame of a single-resolution map always takes the two launches)
-  if (t.multi_res && !c->frame_fused_mr) {
-    c->mr_summaries_valid = false;
-    c->mr_next_general = starve_now || c->frames == 0;
-    c->refill_flag_valid = false;
-  }
-  if (max_num_frames > 0 && starve_fused_ok(c) && c->zfused_n < (size_t) k.rows * k.cols) {
-    // the z-buffers of the starve frames, both pairs empty, while the context is still allocating (not inside its first starve frame)
-    const size_t npix = (size_t) k.rows * k.cols;
-    c->zfused_clean[0] = c->zfused_clean[1] = false;
-    rc = regrow(c, c->d_zfused, c->zfused_n, npix, 4 * npix * sizeof(u64));
-    if (rc) return rc;
-    k_fill_u64<<<512, 256, 0, s>>>(c->d_zfused, 4 * npix, 0x7FFFFFFFFFFFFFFFull);
-    c->zfused_clean[0] = c->zfused_clean[1] = true;
-    c->zfused_clean_npix = npix;
-  }
-  // the frame's kind: the two launches of a single-resolution map (pipelined or serial), a fused or a general multi-resolution frame
-  if (!t.multi_res) return integrate_single_res_frame(c, max_num_frames, starve_now);
-  rc = send_uploads(c, s);  // the frame's kernels read the images on the main stream
-  if (rc) return rc;
-  return c->frame_fused_mr ? integrate_fused_mr_frame(c, max_num_frames) : integrate_general_frame(c, max_num_frames);
 }
 
 int mrh_integrate_resume(mrh_ctx* c) {
-  int rc = ensure_ready(c, "mrh_integrate_resume");
-  if (rc) return rc;
-  if (c->pending == 1) {
-    launch_starve(c, 1);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->pending = 2;
-    return MRH_PENDING_EXCHANGE;
-  }
-  if (c->pending == 2) {
-    launch_starve(c, 2);
-    c->pending = 0;
-    rc = frame_tail(c, true, c->pending_max_frames);
-    if (rc < 0) return rc;
-    const int mrc = mark_frame(c);  // the tail's kernels read the frame's images too
-    return mrc ? mrc : rc;
-  }
-  return fail(c, MRH_ERR_STATE, "mrh_integrate_resume: no exchange is pending");
+  const int rc = ensure_ready(c, "mrh_integrate_resume");
+  return rc ? rc : resume_frame(c);
 }
 
 int mrh_exchange_buffer(mrh_ctx* c, void** out_ptr, uint64_t* out_n, int* out_is_device) {
@@ -1331,7 +588,7 @@ int mrh_get_stats(mrh_ctx* c, mrh_stats* out) {
   out->free_fine = (int64_t) h_ctr[CTR_HEAP_FINE] + 1;
   out->free_coarse = (int64_t) h_ctr[CTR_HEAP_COARSE] + 1;
   out->last_compact_blocks = (uint64_t) h_ctr[CTR_COMPACT] + (fastp ? (uint64_t) h_ctr[CTR_CULLED] + (uint64_t) h_ctr[CTR_FREED_EARLY] : 0);
-  if (fastp && c->h_levels && out->last_compact_blocks >= (uint64_t) h_ctr[CTR_ZSKIP]) out->last_compact_blocks -= (uint64_t) h_ctr[CTR_ZSKIP];  // list entries that were unwanted zombies
+  if (fastp && c->ps.h_levels && out->last_compact_blocks >= (uint64_t) h_ctr[CTR_ZSKIP]) out->last_compact_blocks -= (uint64_t) h_ctr[CTR_ZSKIP];  // list entries that were unwanted zombies
   out->total_updated_voxels = total_upd;
   out->last_updated_voxels = total_upd - c->prev_total_updated;
   out->last_inserted_blocks = h_prof[PROF_INSERTED] - c->prev_inserted;

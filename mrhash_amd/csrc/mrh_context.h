@@ -123,6 +123,106 @@ struct HostVec {
   }
 };
 
+// What a depth frame was issued under: the camera with its pose, the two images, and where each upload ring stood.  One function
+// reads it out of the context and one puts it back (mrh_frame.h: read_inputs, apply_inputs).
+struct FrameInputs {
+  Cam cam;
+  const float* d_depth; const uint8_t* d_rgb;
+  int depth_rows, depth_cols, rgb_rows, rgb_cols;
+  struct Ring { int cur; hipEvent_t last_copy; bool waited[2]; } ring[2];  // up_depth, up_rgb
+};
+// A frame of host images is LAUNCHED one mrh_integrate late (round 5): by then its two transfers have completed and the frame's
+// kernels need no cross-stream wait — a wait that is enqueued while its event is still pending costs the waiting stream ~6 us
+// of idle time, and a host-fed frame had two of them in front of its 41 us of kernels.  mrh_integrate checks what it can,
+// keeps the inputs and returns; the next mrh_integrate — or whichever other entry point needs the map (ensure_ready) — runs the
+// frame first, with those inputs swapped in (mrh_frame.h: flush_deferred).  MRH_DEFER_UPLOADS=0 launches at once.
+struct DeferredFrame {
+  bool on = false;
+  int n_inval = 0;
+  FrameInputs in;
+};
+
+// Every decision about one frame, each computed once (mrh_frame.h: plan_begin, plan_frame, the pipelined-or-serial choice in
+// integrate_single_res_frame, take_slots) and read by whatever launches for the frame; the context keeps the last one.
+enum FrameKind {
+  FRAME_SERIAL,     // the two launches of a single-resolution map on the main stream
+  FRAME_PIPELINED,  // ... its front half on the front stream, its integration held back (PendingBack)
+  FRAME_FUSED_MR,   // the two launches of a multi-resolution map
+  FRAME_GENERAL,    // the general kernels (mrh_kernels.h): multi-resolution frames that cannot be fused, LiDAR scans; GC by k_gc_identify / k_gc_free
+};
+struct FramePlan {
+  FrameKind kind = FRAME_SERIAL;
+  int max_num_frames = 0;       // n_frames_invalidate_voxels of this frame; > 0: garbage collection on
+  bool starve_now = false;      // the frame ends with the starve step
+  bool starve_fused = false;    // a starve step of this frame takes k_starve_z / k_starve_tail (else k_starve<0,1,2>) ...
+  bool starve_in_pipe = false;  // ... and this frame's does, without leaving the pipeline
+  bool gc_inline = false;       // k_back collects (FREE); else frame_tail or the starve tail does
+  bool safe_div = false, sph = false;
+  float gc_thr = 0.f;           // the GC threshold
+  int set = 0, zero_set = 0;    // the frame's list-counter set, and the one its integration clears
+  int ring = 0, seq = 0;        // ring slot (0: a serial frame) and sequence number among the single-resolution frames
+  u32 stamp = 0;
+  int tiles_x = 0, n_tiles = 0; // ray tiles of k_front
+};
+// the integration of the newest pipelined frame is enqueued by the NEXT mrh_integrate (or by whichever other entry point comes
+// first): by then its front half has usually finished, the host sees that (hipEventQuery) and the main stream needs no
+// cross-stream wait in front of the launch — such a wait costs ~6 us of idle main stream per frame on this runtime.
+// The plan, and what only a held-back integration needs: what its front half was launched with, a profile launch's event pair
+// (null: none), the frame mark whose pool report was left to this launch (0: none), k_count_updates' zombie flag.
+struct PendingBack {
+  FramePlan plan;
+  Cam cam; Fast f; Lists L;
+  EvPair ev;
+  uint64_t report_seq;
+  bool count_zombies;
+};
+
+// ---- pipelined frames (mrh_frame.h; MRH_PIPE=0: every frame serial, the two launches on the main stream) ----
+// The front half of a frame (k_front<..., LAZY>) is launched on `stream_front`, its integration (k_back<..., LZ = 2>) on the
+// main stream behind one event; the front stream never waits for the main one, so the front half of frame g + 1 runs next to
+// the integration of frame g.  Up to kPipeRing - 1 frames are in flight, each with its own {depth, colour} image, lists,
+// list-counter set and want stamps.  Two invariants order the streams, each enforced in one place (mrh_frame.h):
+//   (a) after the main stream has changed keys or the free list (a reclaim, a serial frame, a table rebuild, any other entry point),
+//       the next front half is launched only after the host has seen the main stream drain: main_stream_changed_map raises
+//       front_needs_sync, resync_front — in front of k_front<LAZY> — synchronises and lowers it;
+//   (b) anything that is not a pipelined frame meets the map only behind strict_point: the pending integrations launched, the zombies
+//       reclaimed.  In particular the table is rebuilt only with no frame in flight (frame_upkeep).
+struct PipeState {
+  // created by ensure_pipe_state (a context with `pipe` set, at its first single-resolution frame) and kept for the context's life:
+  // the front stream, its events, ring slots 1 .. kPipeRing - 1, the want stamps, h_levels (and Fast::zlist)
+  hipStream_t stream_front = nullptr;
+  hipEvent_t ev_front[kPipeRing] = {};
+  int4* ring_vis[kPipeRing] = {}; int4* ring_bbox[kPipeRing] = {}; int4* ring_cfree[kPipeRing] = {}; float* ring_zmin[kPipeRing] = {};  // [0]: unused (ring_lists)
+  u32* want_ring = nullptr;        // kPipeRing x slots stamps
+  int* h_levels = nullptr;         // pinned {fine free-list level, zombies, sequence number of the last integration that started}
+  uint2* dcx[kPipeRing] = {};      // {cleaned depth, packed colour} of a frame (written by k_front), per ring slot; without the pipelining
+  size_t npix = 0;                 // state [0] alone, which every serial frame uses (ensure_frame_dcx)
+  // what describes the MAP's frames: cleared by reset_pipe_counters (mrh_reset: an empty map has no frame in flight, no zombies, and
+  // its list-counter sets and sequence numbers start over)
+  uint64_t fast_frames = 0;        // two-launch frames issued: selects the list-counter set
+  uint64_t seq = 0;                // single-resolution frames issued (pipelined or not)
+  uint64_t base = 0;               // every frame below this sequence number is known complete (host synchronised)
+  int lazy_run = 0;                // pipelined frames since the last reclaim
+  bool zombies_possible = false;
+  bool front_needs_sync = false;   // invariant (a)
+  static constexpr int kPendMax = 3;
+  PendingBack pendq[kPendMax];     // oldest first
+  int npend = 0;
+  // what describes the CALLER's pattern and the scratch: survives a reset.  A caller that synchronised after each of the last frames
+  // still does (flushed_since_frame is raised by the reset's own ensure_ready anyway), last_frame_lazy is written by every frame
+  // before mark_frame reads it, and the z-buffer pairs are scratch that is as clean or dirty as before.
+  bool last_frame_lazy = false;
+  bool flushed_since_frame = false;  // an entry point other than the per-frame ones ran since the last frame
+  int sync_streak = 0;               // frames in a row that found the pipeline flushed
+  // starve frames on the two-launch path (mrh_fast2.h: k_starve_z / k_starve_tail): two PAIRS of z-buffers, the tail launch of
+  // one starve frame puts the other pair back to "empty" for the next
+  u64* d_zfused = nullptr;  // 2 pairs x 2 x npix
+  size_t zfused_n = 0;
+  bool zfused_clean[2] = {false, false};
+  size_t zfused_clean_npix = 0;  // the image size the clean pairs were cleared for (a pair holds zbuf0 | zbuf1 at THAT size)
+  int zfused_next = 0;
+};
+
 }  // namespace
 
 struct mrh_ctx {
@@ -140,19 +240,7 @@ struct mrh_ctx {
   // device buffer — on a second stream, so the copy of frame N+1 overlaps the kernels of frame N; the frame's kernels
   // wait for the newest copy event, a slot is rewritten only after the last frame that read it (frame_done event).
   UpRing up_depth, up_rgb;
-  // A frame of host images is LAUNCHED one mrh_integrate late (round 5): by then its two transfers have completed and the frame's
-  // kernels need no cross-stream wait — a wait that is enqueued while its event is still pending costs the waiting stream ~6 us
-  // of idle time, and a host-fed frame had two of them in front of its 41 us of kernels.  mrh_integrate checks what it can,
-  // keeps {pose, image pointers, ring state} and returns; the next mrh_integrate — or whichever other entry point needs the map
-  // (ensure_ready) — runs the frame first, with those inputs swapped in.  MRH_DEFER_UPLOADS=0 launches at once.
-  struct DeferredFrame {
-    bool on = false;
-    int n_inval = 0;
-    Cam cam;
-    const float* d_depth = nullptr; const uint8_t* d_rgb = nullptr;
-    int depth_rows = 0, depth_cols = 0, rgb_rows = 0, rgb_cols = 0;
-    struct Ring { int cur; hipEvent_t last_copy; bool waited[2]; } ring[2];
-  } deferred;
+  DeferredFrame deferred;
   int defer_uploads = 1;            // MRH_DEFER_UPLOADS=0: a host-fed frame is launched by the mrh_integrate that issues it
   hipEvent_t frame_done[8] = {};       // recorded behind the kernels that READ a frame's ring slots (front stream for a pipelined frame): slot reuse
   hipEvent_t peek_done[8] = {};        // recorded on the main stream behind the k_report of a mark: what the non-blocking peeks query
@@ -172,13 +260,6 @@ struct mrh_ctx {
   u32* d_decision = nullptr;
   u64* d_zbuf = nullptr;  // 2 * npix
   size_t zbuf_n = 0;
-  // starve frames on the two-launch path (mrh_fast2.h: k_starve_z / k_starve_tail): two PAIRS of z-buffers, the tail launch of
-  // one starve frame puts the other pair back to "empty" for the next
-  u64* d_zfused = nullptr;  // 2 pairs x 2 x npix
-  size_t zfused_n = 0;
-  bool zfused_clean[2] = {false, false};
-  size_t zfused_clean_npix = 0;  // the image size the clean pairs were cleared for (a pair holds zbuf0 | zbuf1 at THAT size)
-  int zfused_next = 0;
   bool starve_fused = true;  // MRH_STARVE_FUSED=0: the eight launches of rounds 1-5 (k_starve<0,1,2>, k_summarize_visible, k_free_lists)
   bool starve_serial = false;  // MRH_STARVE_SERIAL=1: starve frames leave the pipeline (and keep the three fused launches)
   uint64_t n_starve_fused = 0;
@@ -189,11 +270,7 @@ struct mrh_ctx {
   u32* d_misc = nullptr;  // 4 words for k_get_voxel
   float* d_rcp_w = nullptr;  // Fast::rcp_w
   Fast fast;              // fast path buffers
-  // ---- pipelined frames (integrate_single_res_frame; MRH_PIPE=0: every frame serial, the two launches on the main stream) ----
-  // The front half of a frame (k_front<..., LAZY>) is launched on `stream_front`, its integration (k_back<..., LZ = 2>) on the
-  // main stream behind one event; the front stream never waits for the main one, so the front half of frame g + 1 runs next to
-  // the integration of frame g.  Up to kPipeRing - 1 frames are in flight, each with its own {depth, colour} image, lists,
-  // list-counter set and want stamps.  Everything that is not a pipelined frame meets the map only after k_reclaim.
+  // the pipeline's switches; its state is `ps`
   int pipe = 1;
   int pipe_grid = 1024;                     // workgroups of a pipelined integration: ONE resident generation (4 per CU x 256 CUs).  With 2048 the
                                             // second generation competes with the front half's workgroups for the slots the first one frees: 37.3 against
@@ -203,48 +280,13 @@ struct mrh_ctx {
                                             // round 6: a period boundary costs the pipeline ~60 us, the zombies it bounds are also bounded by the
                                             // pool test below (zombies <= pool / 8); 64 — the census period — gave +4 % at 100 steps, 128 no more)
   bool pipe_always_wait = false;            // MRH_PIPE_ALWAYS_WAIT=1: a pipelined integration always carries its wait packet (A/B)
-  // the pipelining state (ensure_pipe_state: a context with `pipe` set, at its first single-resolution frame) — the front stream,
-  // its events, ring slots 1 .. kPipeRing - 1, the want stamps, h_levels and Fast::zlist
-  hipStream_t stream_front = nullptr;
-  hipEvent_t ev_front[kPipeRing] = {};
-  uint2* pipe_dcx[kPipeRing] = {};          // {cleaned depth, packed colour} of a frame (written by k_front), per ring slot; without the pipelining
-  size_t pipe_npix = 0;                     // state [0] alone, which every serial frame uses (ensure_frame_dcx)
-  int4* ring_vis[kPipeRing] = {}; int4* ring_bbox[kPipeRing] = {}; int4* ring_cfree[kPipeRing] = {}; float* ring_zmin[kPipeRing] = {};  // [0]: unused (ring_lists)
-  u32* want_ring = nullptr;                 // kPipeRing x slots stamps
-  int* h_levels = nullptr;                  // pinned {fine free-list level, zombies, sequence number of the last integration that started}
-  uint64_t pipe_seq = 0;                    // single-resolution frames issued (pipelined or not)
-  uint64_t pipe_base = 0;                   // every frame below this sequence number is known complete (host synchronised)
-  int lazy_run = 0;                         // pipelined frames since the last reclaim
-  bool zombies_possible = false;
-  bool last_frame_lazy = false;
-  bool flushed_since_frame = false;          // an entry point other than the per-frame ones ran since the last frame
-  int sync_streak = 0;
-  bool front_needs_sync = false;            // the main stream changed the table / free list behind the front stream's back
-  // the integration of the newest pipelined frame is enqueued by the NEXT mrh_integrate (or by whichever other entry point comes
-  // first): by then its front half has usually finished, the host sees that (hipEventQuery) and the main stream needs no
-  // cross-stream wait in front of the launch — such a wait costs ~6 us of idle main stream per frame on this runtime
-  struct PendingBack {
-    bool on = false;
-    Cam cam;
-    Fast f;
-    Lists L;
-    int set = 0, zero_set = 0, ring = 0, seq = 0;
-    u32 stamp = 0;
-    float thr = 0.f;
-    bool free_ = false, profile = false, safe_div = false, count_zombies = false, sph = false;
-    bool starve = false;  // a starve frame: behind the integration (which collects nothing) the three fused starve launches
-    EvPair ev = {nullptr, nullptr};
-    uint64_t report_seq = 0;  // frame mark whose pool report was written before this integration ran (refreshed behind it)
-  };
-  static constexpr int kPendMax = 3;
-  PendingBack pendq[kPendMax];            // oldest first
-  int npend = 0;
-  int pipe_defer = 1;                     // integrations kept back (MRH_PIPE_DEFER, 1 .. kPendMax - 1): the older a front half, the surer it has finished
+  int pipe_defer = 1;                     // integrations kept back (MRH_PIPE_DEFER, 1 .. PipeState::kPendMax - 1): the older a front half, the surer it has finished
+  PipeState ps;
+  FramePlan plan;  // the last frame's (a sharded starve frame's until mrh_integrate_resume has run its tail)
   uint64_t dbg_waits = 0;
   double dbg_spin_us = 0, dbg_api_us = 0; uint64_t dbg_lazy_frames = 0;  // MRH_DEBUG: where the host's time in a pipelined frame goes
   int4* d_cfree = nullptr;
   float* d_cloud = nullptr; size_t cloud_n = 0;  // spherical camera: getDepth(cloud) image of the current frame (k_cloud_depth)
-  bool frame_general = false;       // this frame ran through the general kernels (mrh_kernels.h): GC by k_gc_identify / k_gc_free
   bool fast_summaries_stale = false;  // single-resolution map: a general frame left Fast::summary behind
   // LiDAR scans (mrh_points.h).  Nothing here is touched by mrh_reset: the counters are zero between scans, buckets_dirty covers a failed one
   struct Lidar {
@@ -293,24 +335,19 @@ struct mrh_ctx {
   int mr_fused = 1;          // MRH_MR_FUSED=0: multi-resolution maps always through the general kernels (mrh_kernels.h)
   bool mr_next_general = true;    // the next multi-resolution frame must take the general path (frame 0 / after a starve frame / after an import)
   bool mr_summaries_valid = false;  // fast.summary / summary_c describe every live block (the general kernels do not maintain them)
-  bool frame_fused_mr = false;
   bool refill_flag_valid = false;  // d_flag holds the refill test for the next fused frame (taken by k_mr_tail)
   int mesh_on_host = 0;      // MRH_MESH_HOST=1: mesh post-process with the host restatement instead of mrh_mesh.h
   float* d_zmin = nullptr;   // per visible-list entry (Lists::zmin)
-  uint64_t fast_frames = 0;  // fast-path frames issued: parity selects the list-counter set
-  int frame_parity = 0;
   u64* d_cnt_partials = nullptr;
   int fused_grid = 2048;  // x 4 waves
   int sweep_wgs_mr = 1024; // the same for multi-resolution maps (9x the descriptors); MRH_SWEEP_WGS_MR
   int sweep_wgs = 128;    // descriptor-sweep workgroups appended to the allocation launch (k_front)
-  bool frame_gc_inline = false;
   int integrate_grid = 1024;
   int low_blocks_to_allocate = 0;
   uint64_t num_blocks = 0, slots = 0, max_triangles = 0;
   uint64_t frames = 0;
   int heap_descending = 0;   // MRH_DEBUG_HEAP_DESCENDING: the fine free list starts in descending order (tests)
   int pending = 0;           // sharded starve frames: 1 after pass 0, 2 after pass 1
-  int pending_max_frames = 0;
   // mesh (host)
   HostVec<mrh_triangle> tris;   // host copy of the soup: only when the caller of mrh_extract_triangles asks for it
   std::vector<mrh_block_desc> tri_blocks;
@@ -402,12 +439,17 @@ struct mrh_ctx {
   std::string err;
 };
 
-// the calls that close a cycle between this header, mrh_upload.h, mrh_comm.h (the next two) and mrh_capi.hip, declared once
+// the calls that close a cycle between this header, mrh_upload.h, mrh_frame.h, mrh_comm.h (the next three: integrate_checks, in
+// mrh_frame.h, sits above mrh_comm.h) and mrh_capi.hip, declared once
 static int comm_allreduce_zbuf(mrh_ctx* c, mrh::u64* buf, size_t n);
 static void comm_release(mrh_ctx* c);
+static bool comm_matches_sharding(const mrh_ctx* c, int* comm_rank, int* comm_world);
 namespace {
-int strict_point(mrh_ctx* c);  // mrh_capi.hip
+int strict_point(mrh_ctx* c);  // mrh_frame.h
 int flush_deferred(mrh_ctx* c);
+// PipeState's invariant (a): the main stream has changed keys or the free list, or is about to (every caller sits in front of the
+// launches it speaks for), while the front stream is not looking.  Without a front stream the flag is raised for nobody.
+void main_stream_changed_map(mrh_ctx* c) { c->ps.front_needs_sync = true; }
 
 int fail(mrh_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -523,7 +565,7 @@ uint64_t next_pow2(uint64_t v) {
 void free_all(mrh_ctx* c) {
   if (!c) return;
   (void) hipSetDevice(c->device);
-  hipStream_t* streams[4] = {&c->up_depth.stream, &c->up_rgb.stream, &c->stream_front, &c->stream};
+  hipStream_t* streams[4] = {&c->up_depth.stream, &c->up_rgb.stream, &c->ps.stream_front, &c->stream};
   for (hipStream_t* s : streams) if (*s) (void) hipStreamSynchronize(*s);
   comm_release(c);
   for (hipEvent_t e : c->owned.events) (void) hipEventDestroy(e);
@@ -533,23 +575,28 @@ void free_all(mrh_ctx* c) {
   for (hipStream_t* s : streams) if (*s) { (void) hipStreamDestroy(*s); *s = nullptr; }
 }
 
+// what of PipeState describes the map's frames (see there): a reset map has nothing left to integrate
+void reset_pipe_counters(mrh_ctx* c) {
+  PipeState& ps = c->ps;
+  for (int i = 0; i < ps.npend; i++) if (ps.pendq[i].ev.a) c->ev_pool.push_back(ps.pendq[i].ev);
+  ps.npend = 0;
+  ps.fast_frames = 0;
+  ps.seq = ps.base = 0;
+  ps.lazy_run = 0;
+  ps.zombies_possible = false;
+  ps.front_needs_sync = false;
+}
+
 // (re)initialises every device structure to the empty map (voxel_data_structures.cpp:58-87 + ctor counters)
 int init_buffers(mrh_ctx* c) {
   hipStream_t s = c->stream;
   c->mr_next_general = true;
   c->refill_flag_valid = false;
   c->mr_summaries_valid = false;
-  c->fast_frames = 0;
-  if (c->stream_front) HIP_TRY(c, hipStreamSynchronize(c->stream_front));
-  for (int i = 0; i < c->npend; i++) if (c->pendq[i].profile) c->ev_pool.push_back(c->pendq[i].ev);
-  c->npend = 0;  // a reset map has nothing left to integrate
-  c->pipe_seq = 0;
-  c->pipe_base = 0;
-  c->lazy_run = 0;
-  c->zombies_possible = false;
-  c->front_needs_sync = false;
-  if (c->h_levels) { c->h_levels[0] = (int) c->num_blocks - 1; c->h_levels[1] = 0; c->h_levels[2] = -1; }
-  if (c->want_ring) HIP_TRY(c, hipMemsetAsync(c->want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), s));
+  if (c->ps.stream_front) HIP_TRY(c, hipStreamSynchronize(c->ps.stream_front));
+  reset_pipe_counters(c);
+  if (c->ps.h_levels) { c->ps.h_levels[0] = (int) c->num_blocks - 1; c->ps.h_levels[1] = 0; c->ps.h_levels[2] = -1; }
+  if (c->ps.want_ring) HIP_TRY(c, hipMemsetAsync(c->ps.want_ring, 0, (size_t) kPipeRing * c->slots * sizeof(u32), s));
   const Tab& t = c->tab;
   k_init_table<<<1024, 256, 0, s>>>(t.keys, c->slots);
   k_init_heap<<<1024, 256, 0, s>>>(t.heap_fine, (u32) c->num_blocks, c->heap_descending);
@@ -721,7 +768,7 @@ void read_switches(mrh_ctx* c) {
   c->starve_serial = env_present("MRH_STARVE_SERIAL");
   c->pipe_always_wait = env_present("MRH_PIPE_ALWAYS_WAIT");
   env_int("MRH_PIPE_GRID", 1, 32768, c->pipe_grid);
-  env_int("MRH_PIPE_DEFER", 1, mrh_ctx::kPendMax - 1, c->pipe_defer);
+  env_int("MRH_PIPE_DEFER", 1, PipeState::kPendMax - 1, c->pipe_defer);
   env_onoff("MRH_PIPE_UPLOADS", c->pipe_uploads);
   env_int("MRH_PIPE_PERIOD", 1, kIntMax, c->pipe_period);
   env_int("MRH_SWEEP_WGS", 1, 4096, c->sweep_wgs);

@@ -195,6 +195,30 @@ void size_mesh_staging(mrh_ctx* c, const size_t nv, const size_t nf) {
   c->stage_ctl.resize_discard(kStageHdrWords + 2 * ((std::min(c->V32.cap, c->C32.cap) * 4 + kStageChunk - 1) / kStageChunk + 2));
 }
 
+// see mrh_ctx::prewarm_on
+void prewarm_maybe(mrh_ctx* c) {
+  if (!c->prewarm_on || c->prewarm_done || c->frames != 3 || c->n_extractions || c->f64_link || c->mesh_on_host || c->pending) return;
+  c->prewarm_done = true;
+  int lev = 0;
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&lev, &c->tab.ctr[CTR_HEAP_FINE], sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+    (void) hipGetLastError();
+    return;
+  }
+  const uint64_t live = (uint64_t) std::max<int64_t>((int64_t) c->num_blocks - ((int64_t) lev + 1), 0);  // fine slots in use (coarse units live in fine slots)
+  const uint64_t nv = live * 64;
+  if (nv < 65536) return;  // a mesh this small costs its first extraction next to nothing
+  try {
+    const size_t nf = (size_t) (nv + nv / 4);  // faces: a little above the vertices (closed surfaces: twice; what is seen of a room: ~1.1 x)
+    size_mesh_staging(c, (size_t) nv, nf);
+    if (c->stage_ctl.data()) memset(c->stage_ctl.data(), 0, c->stage_ctl.cap * sizeof(u32));  // no epoch, no flag of an earlier life
+    c->V.reserve_unpinned((size_t) nv * 3); c->C.reserve_unpinned((size_t) nv * 3);  // never pinned: mapped and faulted in
+    c->V32.clear(); c->C32.clear(); c->F.clear(); c->V.clear(); c->C.clear();  // capacity, not content: the getters still answer "no mesh"
+  } catch (...) {
+    // no memory for it: the first extraction sizes its buffers itself, as it always did
+  }
+  (void) hipGetLastError();
+}
+
 // the switches of the post-process, read once per call
 struct MeshOpts {
   bool dbg;         // MRH_DEBUG: the phase line on stderr

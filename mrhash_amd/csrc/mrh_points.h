@@ -3,8 +3,8 @@
 // takes a scan through one of two record paths — the voxel buckets (kernels in mrh_scan.h) or, where their scratch does not fit,
 // the voxel ids need 64-bit keys, a beam is too long or MRH_LIDAR_BUCKETS=0 says so, the sorted records (kernels in mrh_lidar.h,
 // the sort in mrh_sort.h).  The state is mrh_ctx::lidar.  Included by mrh_capi.hip, same translation unit: it needs the context's
-// internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all, ensure_ready, frame_upkeep, refill_coarse, launch_compact_all,
-// starve_and_tail, mark_frame).
+// internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all, ensure_ready, launch_compact_all, mark_frame and, from
+// mrh_frame.h, frame_upkeep, refill_coarse, plan_begin, starve_and_tail).
 #pragma once
 
 namespace {
@@ -390,11 +390,10 @@ int mrh_integrate_points(mrh_ctx* c, int n_frames_invalidate) {
   if (rc) return rc;
   rc = points_checks(c);
   if (rc) return rc;
-  const int max_num_frames = n_frames_invalidate < 0 ? c->p.n_frames_invalidate_voxels : n_frames_invalidate;
   rc = frame_upkeep(c);
   if (rc) return rc;
-  c->frame_general = true;  // GC (and the starve step) of a scan run through the general kernels on the list of ALL live blocks
-  c->frame_fused_mr = false;
+  FramePlan& plan = c->plan;
+  plan_begin(c, plan, FRAME_GENERAL, n_frames_invalidate);  // GC (and the starve step) of a scan run through the general kernels on the list of ALL live blocks
   if (c->tab.multi_res) { c->mr_summaries_valid = false; c->mr_next_general = true; c->refill_flag_valid = false; }
   if (c->lidar.num_points > 0) {
     if (c->tab.multi_res) refill_coarse(c);
@@ -418,11 +417,11 @@ int mrh_integrate_points(mrh_ctx* c, int n_frames_invalidate) {
       if (rc) return rc;
     }
   }
-  if (max_num_frames > 0) {  // flatAndReduceHashTable() without a camera: every live block (voxel_data_structures.cpp:121, :126)
+  if (plan.max_num_frames > 0) {  // flatAndReduceHashTable() without a camera: every live block (voxel_data_structures.cpp:121, :126)
     rc = launch_compact_all(c);
     if (rc) return rc;
   }
-  rc = starve_and_tail(c, max_num_frames);  // garbageCollect(camera, max_num_frames); counts the frame
+  rc = starve_and_tail(c, plan);  // garbageCollect(camera, max_num_frames); counts the frame
   if (rc < 0) return rc;
   HIP_TRY(c, hipGetLastError());
   if (c->peek_enabled) {

@@ -15,7 +15,7 @@ int upload_image(mrh_ctx* c, UpRing& ring, const void* src, const size_t bytes, 
   if (!ring.stream) HIP_TRY(c, hipStreamCreateWithFlags(&ring.stream, hipStreamNonBlocking));
   const int next = (ring.cur + 1) % 3;
   // a frame that mrh_integrate kept back (flush_deferred) has not marked its slots yet: before the ring comes round to one of them, it runs
-  if (c->deferred.on && next == c->deferred.ring[&ring == &c->up_rgb ? 1 : 0].cur) {
+  if (c->deferred.on && next == c->deferred.in.ring[&ring == &c->up_rgb ? 1 : 0].cur) {
     const int frc = flush_deferred(c);
     if (frc < 0) return frc;
   }
@@ -108,7 +108,7 @@ int mark_frame(mrh_ctx* c) {
   const uint64_t seq = c->frame_seq++;
   if (!c->frame_done[7])  // created in order: the last one says that all exist
     for (hipEvent_t& e : c->frame_done) if (!e) HIP_TRY(c, event_new(c, e, false));
-  const bool lazy = c->last_frame_lazy && c->npend;  // the frame's integration is not enqueued yet (launch_pending)
+  const bool lazy = c->ps.last_frame_lazy && c->ps.npend;  // the frame's integration is not enqueued yet (launch_pending)
   if (c->peek_enabled) {
     if (!c->peek_done[7])
       for (hipEvent_t& e : c->peek_done) if (!e) HIP_TRY(c, event_new(c, e, false));
@@ -117,14 +117,14 @@ int mark_frame(mrh_ctx* c) {
       // exist for the peeks (they fall back to an older one and say how many frames behind it is).  A report launched here would
       // sit behind the integration of an EARLIER frame only, and an event on the front stream says nothing about it at all.
       c->peek_seq[seq % 8] = 0;
-      c->pendq[c->npend - 1].report_seq = seq;
+      c->ps.pendq[c->ps.npend - 1].report_seq = seq;
     } else if (const int rc = post_report(c, seq, c->stream)) {
       return rc;
     }
   }
   if (used[0] || used[1]) {
     // the raw images of a pipelined frame are read by its front half, on the front stream (its integration reads the cleaned copy)
-    HIP_TRY(c, hipEventRecord(c->frame_done[seq % 8], lazy ? c->stream_front : c->stream));
+    HIP_TRY(c, hipEventRecord(c->frame_done[seq % 8], lazy ? c->ps.stream_front : c->stream));
     for (UpSlot* u : used) if (u) u->last_seq = seq;
   }
   return MRH_OK;

@@ -1179,7 +1179,7 @@ def _pipe40_reference(hip, oracle, monkeypatch):
 
 @pytest.mark.parametrize("period", ["2", "5", "1000"])
 def test_pipelined_frames_build_the_serial_map(hip, oracle, monkeypatch, period):
-    """Pipelined frames (mrh_capi.hip integrate_lazy: front half on a second stream next to the integrations before it, lazy
+    """Pipelined frames (mrh_frame.h integrate_single_res_frame: front half on a second stream next to the integrations before it, lazy
     garbage collection through zombies and per-frame want stamps, k_reclaim every `period` frames) against the oracle AND against
     the same library fusing serially (MRH_PIPE=0): 40 frames of the 640x480 orbit without a synchronisation in between, GC on
     every frame — the blocks of the truncation band's near edge are collected and wanted again every single frame, blocks that
@@ -1234,6 +1234,89 @@ def test_starve_frames_stay_in_the_pipeline(hip, oracle, monkeypatch, mode):
         assert getattr(sa, k) == getattr(sb, k), (k, getattr(sa, k), getattr(sb, k))
     r = pu.compare_maps(a, b)
     assert r["blocks"] > 500 and r["sdf_bit_exact"] and r["sumsq_bit_exact"]
+    pu.compare_meshes(a, b)
+    a.close()
+    b.close()
+
+
+def _every_kind_script(engines, lib_engine=None):
+    """The frames of test_every_kind_of_frame_on_one_context into `engines` alike; `lib_engine` (the library's, when it takes part)
+    gets the calls in between (None: the oracle alone, which is how the block counts in that test's docstring were taken).  Yields
+    "end" after frame 23 and again after the reset and eight more frames."""
+    K = synth.Intrinsics(160.0, 160.0, 79.5, 59.5, 120, 160)
+    K2 = synth.Intrinsics(200.0, 200.0, 79.5 * 1.25, 59.5 * 1.25, 150, 200)
+    scene = synth.scannet_room()
+    poses = synth.walk_poses(24, seed=11)
+    f = None
+    for i, (t, q) in enumerate(poses):
+        if i == 14:  # the dcx images regrow with frames in flight, the z-buffer pairs change size
+            for e in engines:
+                e.set_camera(K2.fx, K2.fy, K2.cx, K2.cy, K2.rows, K2.cols, e.params.min_depth, e.params.max_depth)
+        f = synth.render(scene, K if i < 14 else K2, t, q, depth_scaling=5000.0)
+        for e in engines:
+            pu.feed(e, f)
+        if lib_engine is not None and i in (6, 7, 8):  # the sync streak reaches three: frame 9 is serial, frame 10 pipelined again
+            lib_engine.sync()
+        if lib_engine is not None and i == 12:  # an entry point with an integration held back
+            lib_engine.stats()
+    yield "end"
+    for e in engines:  # one more frame, so that the library holds one back when the reset comes
+        pu.feed(e, f)
+    for e in engines:
+        e.reset()
+    for t, q in poses[:8]:
+        f = synth.render(scene, K2, t, q, depth_scaling=5000.0)
+        for e in engines:
+            pu.feed(e, f)
+    yield "end"
+
+
+def _every_kind_params():
+    return dict(synth.REPLICA_PARAMS, virtual_voxel_size=0.02, sdf_truncation=0.08, n_frames_invalidate_voxels=3)
+
+
+@pytest.mark.parametrize("defer", ["1", "0"])
+@pytest.mark.parametrize("pipe", ["1", "0"])
+def test_every_kind_of_frame_on_one_context(hip, oracle, monkeypatch, pipe, defer):
+    """One context through every transition of the frame paths (mrh_frame.h) at 160x120, starve period 3, reclaim period 4: six
+    frames back to back (the ring of six wraps, frames 3 and 6 starve inside the pipeline), a synchronisation after each of frames
+    6, 7 and 8 (frame 9 must be serial, frame 10 is pipelined again), statistics with an integration held back, a larger camera
+    from frame 14 on (the per-slot images regrow with frames in flight, the z-buffer pairs of the starve launches change size), a
+    reset with a frame held back and eight more frames.  Pipelined and serial, host-fed frames deferred and not; against the
+    oracle bit for bit, twice (the oracle leaves 694 blocks after frame 23 and 651 after the reset and eight more frames)."""
+    monkeypatch.setenv("MRH_PIPE", pipe)
+    monkeypatch.setenv("MRH_DEFER_UPLOADS", defer)
+    monkeypatch.setenv("MRH_PIPE_PERIOD", "4")
+    K = synth.Intrinsics(160.0, 160.0, 79.5, 59.5, 120, 160)
+    a, b = _pair(hip, oracle, K, _every_kind_params(), 65536)
+    for _ in _every_kind_script([a, b], lib_engine=a):
+        sa, sb = a.stats(), b.stats()
+        for k in ("occupied_fine", "free_fine", "frames_integrated", "error_flags"):
+            assert getattr(sa, k) == getattr(sb, k), (k, getattr(sa, k), getattr(sb, k))
+        r = pu.compare_maps(a, b)
+        assert r["blocks"] > 500 and r["sdf_bit_exact"] and r["sumsq_bit_exact"]
+        pu.compare_meshes(a, b)
+    a.close()
+    b.close()
+
+
+def test_table_rebuild_with_frames_in_flight(hip, oracle, monkeypatch):
+    """The table is rebuilt only with no frame in flight (mrh_frame.h frame_upkeep), garbage collection on or off: with GC off a
+    pipelined frame leaves no zombies behind, so nothing used to flush the pending integration in front of the census, and the front
+    stream was never told that the rebuild had moved keys.  A rebuild in front of every frame (MRH_REHASH_PERIOD=1,
+    MRH_REHASH_FORCE=1), twelve frames with no call between them."""
+    monkeypatch.setenv("MRH_REHASH_PERIOD", "1")
+    monkeypatch.setenv("MRH_REHASH_FORCE", "1")
+    assert synth.CFG1_PARAMS["n_frames_invalidate_voxels"] == 0
+    a, b = _pair(hip, oracle, synth.CFG1, synth.CFG1_PARAMS, 4096)
+    for i in range(12):
+        f = synth.cfg1_sphere(zc=1.3 + 0.02 * i)
+        pu.feed(a, f)
+        pu.feed(b, f)
+    st = a.stats()
+    assert st.rehash_count >= 11 and st.error_flags == 0, (st.rehash_count, st.error_flags)
+    r = pu.compare_maps(a, b)
+    assert r["sdf_bit_exact"] and r["sumsq_bit_exact"]
     pu.compare_meshes(a, b)
     a.close()
     b.close()
