@@ -28,6 +28,7 @@
 #define MRH_SM_PI 3.14159265358979323846f
 #define MRH_SM_PIO2 1.57079632679489661923f
 #define MRH_SM_PIO4 0.78539816339744830962f
+#define MRH_SM_SINCOS_MAX 8192.0f /* mrh_sincosf is specified for |x| <= this (its octant count stays exact in the reduction) */
 
 /* sin / cos of x for |x| <= 8192 (the camera uses |x| <= pi): octant reduction with a three-part pi / 4 (Cody-Waite),
  * degree-7 / degree-8 polynomials on [0, pi / 4]. */

@@ -130,8 +130,8 @@ COMM_ID_BYTES = 128
 COMM_SUM, COMM_MAX, COMM_MIN = 0, 1, 2
 
 # every symbol include/mrhash_raycast.h declares (the HIP library only: the oracle does not render)
-RAYCAST_SYMBOLS = ("mrh_raycast mrh_raycast_device").split()
-RAYCAST_NORMALS, RAYCAST_COLORS = 1, 2
+RAYCAST_SYMBOLS = ("mrh_raycast mrh_raycast_device mrh_raycast_spherical mrh_raycast_spherical_device").split()
+RAYCAST_NORMALS, RAYCAST_COLORS, RAYCAST_POINTS = 1, 2, 4
 
 
 class MrhRaycastParams(C.Structure):
@@ -249,6 +249,8 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "mrh_raycast"):  # include/mrhash_raycast.h
         lib.mrh_raycast.argtypes = [C.c_void_p, P(MrhRaycastParams), P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
         lib.mrh_raycast_device.argtypes = [C.c_void_p, P(MrhRaycastParams), P(C.c_float), P(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mrh_raycast_spherical.argtypes = lib.mrh_raycast.argtypes + [P(C.c_void_p)]
+        lib.mrh_raycast_spherical_device.argtypes = lib.mrh_raycast_device.argtypes + [C.c_void_p]
         for name in RAYCAST_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_estimate_normals"):  # include/mrhash_normals.h
@@ -695,9 +697,9 @@ class Engine:
 
     # -- rendering (include/mrhash_raycast.h) ------------------------------------------------------
     @staticmethod
-    def _raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, normals, colors):
+    def _raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, normals, colors, points=False):
         p = MrhRaycastParams(fx, fy, cx, cy, int(rows), int(cols), min_depth, max_depth, step,
-                             (RAYCAST_NORMALS if normals else 0) | (RAYCAST_COLORS if colors else 0))
+                             (RAYCAST_NORMALS if normals else 0) | (RAYCAST_COLORS if colors else 0) | (RAYCAST_POINTS if points else 0))
         R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
         t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
         return p, R, t
@@ -728,6 +730,38 @@ class Engine:
         F = C.POINTER(C.c_float)
         self._check(self.lib.mrh_raycast_device(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), d_depth or None,
                                                 d_normals or None, d_rgb or None))
+
+    def raycast_spherical(self, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, normals=True, colors=True, points=False):
+        """Renders the map from the sensor-to-world pose (R, t) with a spherical camera (mrh_raycast_spherical):
+        fx / fy in pixels per radian, cx / cy as set_camera(..., model=1) means them, min_depth / max_depth / step ranges along
+        the ray.  Returns numpy copies (range f32 [rows, cols], normals f32 [rows, cols, 3] or None, rgb u8 [rows, cols, 3] or
+        None, points f32 [rows * cols, 3] or None); the points are the crossings in the SENSOR frame, an organised scan of `cols`
+        points per row that upload_points takes as it is.  A pixel without a hit is 0 in all four."""
+        p, R, t = self._raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, normals, colors, points)
+        pd, pn, pc, pp = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        F = C.POINTER(C.c_float)
+        self._check(self.lib.mrh_raycast_spherical(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), C.byref(pd),
+                                                   C.byref(pn) if normals else None, C.byref(pc) if colors else None,
+                                                   C.byref(pp) if points else None))
+        n = int(rows) * int(cols)
+
+        def arr(ptr, count, dt, shape):
+            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).reshape(shape).copy()
+
+        rng = arr(pd, n, np.float32, (rows, cols))
+        nrm = arr(pn, 3 * n, np.float32, (rows, cols, 3)) if normals else None
+        rgb = arr(pc, 3 * n, np.uint8, (rows, cols, 3)) if colors else None
+        pts = arr(pp, 3 * n, np.float32, (n, 3)) if points else None
+        return rng, nrm, rgb, pts
+
+    def raycast_spherical_device(self, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, d_range=0, d_normals=0, d_rgb=0,
+                                 d_points=0):
+        """mrh_raycast_spherical_device: as raycast_device; d_points ([rows * cols, 3] float32) can go to set_points_device of
+        another context after sync()."""
+        p, R, t = self._raycast_args(fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, bool(d_normals), bool(d_rgb), bool(d_points))
+        F = C.POINTER(C.c_float)
+        self._check(self.lib.mrh_raycast_spherical_device(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), d_range or None,
+                                                          d_normals or None, d_rgb or None, d_points or None))
 
     # -- scan normals (include/mrhash_normals.h) ----------------------------------------------------
     def estimate_normals(self, radius=0.0, min_points=0, min_spread=0.0, max_flatness=0.0, info=False):

@@ -539,16 +539,21 @@ GeoWrapper::RaycastImages GeoWrapper::raycast() { return raycastPose(pose_); }
 
 GeoWrapper::RaycastImages GeoWrapper::raycast(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastPose(pose_from(t, q)); }
 
-GeoWrapper::RaycastImages GeoWrapper::raycastPose(const std::array<float, 16>& pose) {
-  if (!has_camera_) throw std::runtime_error("GeoWrapper::raycast | setCamera has not been called");
-  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::raycast | pinhole cameras only (the camera is spherical)");
+mrh_raycast_params GeoWrapper::raycastParams(const uint32_t outputs) const {
   mrh_raycast_params p;
   std::memset(&p, 0, sizeof p);
   p.fx = camera_fx_; p.fy = camera_fy_; p.cx = camera_cx_; p.cy = camera_cy_;
   p.rows = camera_rows_; p.cols = camera_cols_;
   p.min_depth = camera_min_depth_; p.max_depth = max_depth_;
   p.step = 0.f;  // half the truncation
-  p.outputs = MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS;
+  p.outputs = outputs;
+  return p;
+}
+
+GeoWrapper::RaycastImages GeoWrapper::raycastPose(const std::array<float, 16>& pose) {
+  if (!has_camera_) throw std::runtime_error("GeoWrapper::raycast | setCamera has not been called");
+  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::raycast | pinhole cameras only (the camera is spherical)");
+  const mrh_raycast_params p = raycastParams(MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS);
   const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
   const float t[3] = {pose[3], pose[7], pose[11]};
   const float *depth = nullptr, *normals = nullptr;
@@ -560,6 +565,29 @@ GeoWrapper::RaycastImages GeoWrapper::raycastPose(const std::array<float, 16>& p
   out.depth.assign(depth, depth + n);
   out.normals.assign(normals, normals + 3 * n);
   out.colors.assign(rgb, rgb + 3 * n);
+  return out;
+}
+
+GeoWrapper::RaycastScan GeoWrapper::raycastScan() { return raycastScanPose(pose_); }
+
+GeoWrapper::RaycastScan GeoWrapper::raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastScanPose(pose_from(t, q)); }
+
+GeoWrapper::RaycastScan GeoWrapper::raycastScanPose(const std::array<float, 16>& pose) {
+  if (!has_camera_) throw std::runtime_error("GeoWrapper::raycastScan | setCamera has not been called");
+  if (camera_model_ != MRH_CAMERA_SPHERICAL) throw std::runtime_error("GeoWrapper::raycastScan | spherical cameras only (the camera is pinhole)");
+  const mrh_raycast_params p = raycastParams(MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS | MRH_RAYCAST_POINTS);
+  const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
+  const float t[3] = {pose[3], pose[7], pose[11]};
+  const float *range = nullptr, *normals = nullptr, *points = nullptr;
+  const uint8_t* rgb = nullptr;
+  check(mrh_raycast_spherical(ctx_, &p, R, t, &range, &normals, &rgb, &points), "raycastScan");
+  RaycastScan out;
+  out.rows = p.rows; out.cols = p.cols;
+  const size_t n = (size_t) p.rows * (size_t) p.cols;
+  out.range.assign(range, range + n);
+  out.normals.assign(normals, normals + 3 * n);
+  out.colors.assign(rgb, rgb + 3 * n);
+  out.points.assign(points, points + 3 * n);
   return out;
 }
 

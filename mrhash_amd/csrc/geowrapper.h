@@ -97,7 +97,7 @@ public:
   // ---- rendering (include/mrhash_raycast.h; no reference counterpart): the map seen by the camera of the last setCamera
   // (intrinsics, rows, cols, min and max depth), from the current pose (getCurrPose) or from (t, q) converted as setCurrPose
   // does.  depth [rows * cols] (camera z, metres), normals [rows * cols * 3] (world frame), colors [rows * cols * 3], row-major;
-  // a pixel without a hit is 0 in all three.  A spherical camera throws std::runtime_error.  Blocks paged out to the host
+  // a pixel without a hit is 0 in all three.  A spherical camera throws std::runtime_error (raycastScan renders it).  Blocks paged out to the host
   // grid (stream(), streamAllOut()) are not on the device and are not rendered.
   struct RaycastImages {
     int rows = 0, cols = 0;
@@ -106,6 +106,16 @@ public:
   };
   RaycastImages raycast();
   RaycastImages raycast(const std::array<float, 3>& t, const std::array<float, 4>& q);
+  // The same for the spherical camera of the last setCamera (LiDAR scans, range images): range [rows * cols] (metres along the
+  // ray) instead of depth, and the crossings as sensor-frame points [rows * cols * 3] — an organised scan of `cols` points per
+  // row with (0, 0, 0) for a ray without a hit, which setPointCloud takes as it is.  A pinhole camera throws std::runtime_error.
+  struct RaycastScan {
+    int rows = 0, cols = 0;
+    std::vector<float> range, normals, points;
+    std::vector<uint8_t> colors;
+  };
+  RaycastScan raycastScan();
+  RaycastScan raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q);
 
   // ---- multi-GPU (include/mrhash_comm.h; no reference counterpart): one GeoWrapper per process / GPU.
   // commUniqueId() on one rank, the 128 bytes handed to the others by the launcher, then commInit on every rank.
@@ -144,6 +154,8 @@ private:
   uint32_t flags_announced_ = 0, last_compute_flags_ = 0;
   float max_depth_ = 0.f;
   RaycastImages raycastPose(const std::array<float, 16>& pose);
+  RaycastScan raycastScanPose(const std::array<float, 16>& pose);
+  mrh_raycast_params raycastParams(uint32_t outputs) const;  // the camera of the last setCamera, step = half the truncation
   bool has_camera_ = false;  // the camera of the last setCamera, for raycast()
   int camera_model_ = MRH_CAMERA_PINHOLE, camera_rows_ = 0, camera_cols_ = 0;
   float camera_fx_ = 0.f, camera_fy_ = 0.f, camera_cx_ = 0.f, camera_cy_ = 0.f, camera_min_depth_ = 0.f;

@@ -638,8 +638,8 @@ int mrh_selftest_division(mrh_ctx* c, uint64_t samples, uint64_t seed, uint64_t*
 namespace {
 float ray_z_host(const float min_depth, const float step, const uint32_t k) { return min_depth + (float) k * step; }  // = ray_z
 
-// the arguments both entry points share, checked before the map is touched; fills the kernel's camera
-int raycast_args(mrh_ctx* c, const char* who, const mrh_raycast_params* p, const float* R, const float* t, RayCam* rc) {
+// the arguments every entry point shares, checked before the map is touched; fills the kernel's camera.  model: MRH_CAMERA_*
+int raycast_args(mrh_ctx* c, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, RayCam* rc) {
   if (!p || !R || !t) return fail(c, MRH_ERR_INVALID_ARG, "%s: null argument", who);
   if (c->pending) return fail(c, MRH_ERR_STATE, "%s: an exchange is pending (call mrh_integrate_resume)", who);
   if (c->map.shard_count > 1) return fail(c, MRH_ERR_UNSUPPORTED, "%s: sharded maps are not rendered (shard_count %d)", who, c->map.shard_count);
@@ -649,7 +649,8 @@ int raycast_args(mrh_ctx* c, const char* who, const mrh_raycast_params* p, const
     return fail(c, MRH_ERR_INVALID_ARG, "%s: bad intrinsics", who);
   if (!(p->min_depth > 0.f) || !(p->max_depth > p->min_depth) || !std::isfinite(p->max_depth))
     return fail(c, MRH_ERR_INVALID_ARG, "%s: need 0 < min_depth < max_depth (got %g, %g)", who, (double) p->min_depth, (double) p->max_depth);
-  if (p->outputs & ~(MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS)) return fail(c, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  const uint32_t known = MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS | (model == MRH_CAMERA_SPHERICAL ? MRH_RAYCAST_POINTS : 0u);
+  if (p->outputs & ~known) return fail(c, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
   const float step = p->step == 0.f ? 0.5f * c->p.sdf_truncation : p->step;
   if (!(step > 0.f) || !std::isfinite(step)) return fail(c, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
   for (int i = 0; i < 9; i++)
@@ -670,6 +671,16 @@ int raycast_args(mrh_ctx* c, const char* who, const mrh_raycast_params* p, const
   rc->ify = 1.0f / p->fy;
   rc->cx = p->cx; rc->cy = p->cy;
   rc->rows = p->rows; rc->cols = p->cols;
+  if (model == MRH_CAMERA_SPHERICAL) {
+    // every pixel's azimuth and elevation within the range mrh_sincosf is specified on: the kernel's expressions (ray_dir_sensor)
+    // at the corner pixels — they are monotone in the column and in the row, so the corners bound every pixel
+    const float az0 = rc->ifx * (((float) 0 - rc->cx) - 0.5f), az1 = rc->ifx * (((float) (rc->cols - 1) - rc->cx) - 0.5f);
+    const float el0 = rc->ify * (((float) 0 - rc->cy) - 0.5f), el1 = rc->ify * (((float) (rc->rows - 1) - rc->cy) - 0.5f);
+    const float worst = std::fmax(std::fmax(std::fabs(az0), std::fabs(az1)), std::fmax(std::fabs(el0), std::fabs(el1)));
+    if (!(worst <= MRH_SM_SINCOS_MAX))
+      return fail(c, MRH_ERR_INVALID_ARG, "%s: a pixel's azimuth or elevation reaches %g rad (sine and cosine are specified up to %g)", who,
+                  (double) worst, (double) MRH_SM_SINCOS_MAX);
+  }
   rc->min_depth = p->min_depth; rc->max_depth = p->max_depth; rc->step = step;
   rc->n_samples = hi;
   for (int i = 0; i < 9; i++) rc->R[i] = R[i];
@@ -677,9 +688,67 @@ int raycast_args(mrh_ctx* c, const char* who, const mrh_raycast_params* p, const
   return MRH_OK;
 }
 
-void launch_raycast(mrh_ctx* c, const RayCam& rc, float* depth, float* normals, uint8_t* rgb) {
+// the four images, device pointers (nullptr = not wanted); `points` exists for the spherical model only
+struct RayOut {
+  float* depth; float* normals; uint8_t* rgb; float* points;
+};
+
+void launch_raycast(mrh_ctx* c, const int model, const RayCam& rc, const RayOut& o) {
   const dim3 grid((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
-  k_raycast<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, depth, normals, rgb);
+  if (model == MRH_CAMERA_SPHERICAL) k_raycast<true><<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, o.depth, o.normals, o.rgb, o.points);
+  else k_raycast<false><<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, o.depth, o.normals, o.rgb, nullptr);
+}
+
+// c->d_ray / c->h_ray per pixel: [depth f32 | normals 3 x f32 | points 3 x f32 | rgb 3 x u8], each image contiguous
+constexpr size_t kRayPixelBytes = sizeof(float) * 7 + 3;
+constexpr size_t ray_off_normals(const size_t npix) { return npix * sizeof(float); }
+constexpr size_t ray_off_points(const size_t npix) { return npix * sizeof(float) * 4; }
+constexpr size_t ray_off_rgb(const size_t npix) { return npix * sizeof(float) * 7; }
+
+// mrh_raycast / mrh_raycast_spherical: the render into the context's own images and their pinned copy (blocks)
+int raycast_host(mrh_ctx* c, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, const float** out_depth,
+                 const float** out_normals, const uint8_t** out_rgb, const float** out_points) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  RayCam rc;
+  int rc_ = raycast_args(c, who, model, p, R, t, &rc);
+  if (rc_) return rc_;
+  rc_ = ensure_ready(c, who);
+  if (rc_) return rc_;
+  const size_t npix = (size_t) rc.rows * (size_t) rc.cols;
+  const size_t bytes = npix * kRayPixelBytes;
+  rc_ = regrow(c, c->d_ray, c->ray_cap, npix, bytes, false);  // the previous raycast has finished (it blocked): nothing reads the old buffers
+  if (rc_) return rc_;
+  if ((rc_ = regrow_pinned(c, c->h_ray, c->h_ray_cap, npix, bytes))) return rc_;
+  const bool want_n = out_normals && (p->outputs & MRH_RAYCAST_NORMALS), want_c = out_rgb && (p->outputs & MRH_RAYCAST_COLORS);
+  const bool want_p = out_points && (p->outputs & MRH_RAYCAST_POINTS);
+  const RayOut d = {(float*) c->d_ray, (float*) (c->d_ray + ray_off_normals(npix)), (uint8_t*) (c->d_ray + ray_off_rgb(npix)),
+                    (float*) (c->d_ray + ray_off_points(npix))};
+  launch_raycast(c, model, rc, RayOut{out_depth ? d.depth : nullptr, want_n ? d.normals : nullptr, want_c ? d.rgb : nullptr, want_p ? d.points : nullptr});
+  HIP_TRY(c, hipGetLastError());
+  if (out_depth) HIP_TRY(c, hipMemcpyAsync(c->h_ray, d.depth, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (want_n) HIP_TRY(c, hipMemcpyAsync(c->h_ray + ray_off_normals(npix), d.normals, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (want_c) HIP_TRY(c, hipMemcpyAsync(c->h_ray + ray_off_rgb(npix), d.rgb, npix * 3, hipMemcpyDeviceToHost, c->stream));
+  if (want_p) HIP_TRY(c, hipMemcpyAsync(c->h_ray + ray_off_points(npix), d.points, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (out_depth) *out_depth = (const float*) c->h_ray;
+  if (out_normals) *out_normals = want_n ? (const float*) (c->h_ray + ray_off_normals(npix)) : nullptr;
+  if (out_rgb) *out_rgb = want_c ? (const uint8_t*) (c->h_ray + ray_off_rgb(npix)) : nullptr;
+  if (out_points) *out_points = want_p ? (const float*) (c->h_ray + ray_off_points(npix)) : nullptr;
+  return MRH_OK;
+}
+
+// mrh_raycast_device / mrh_raycast_spherical_device: the render into the caller's device buffers (enqueues)
+int raycast_device(mrh_ctx* c, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, const RayOut& o) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  RayCam rc;
+  int rc_ = raycast_args(c, who, model, p, R, t, &rc);
+  if (rc_) return rc_;
+  rc_ = ensure_ready(c, who);
+  if (rc_) return rc_;
+  launch_raycast(c, model, rc, RayOut{o.depth, (p->outputs & MRH_RAYCAST_NORMALS) ? o.normals : nullptr, (p->outputs & MRH_RAYCAST_COLORS) ? o.rgb : nullptr,
+                                      (p->outputs & MRH_RAYCAST_POINTS) ? o.points : nullptr});
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
 }
 }  // namespace
 
@@ -687,44 +756,22 @@ extern "C" {
 
 int mrh_raycast(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], const float** out_depth,
                 const float** out_normals, const uint8_t** out_rgb) {
-  if (!c) return MRH_ERR_INVALID_ARG;
-  RayCam rc;
-  int rc_ = raycast_args(c, "mrh_raycast", p, R_row_major, t, &rc);
-  if (rc_) return rc_;
-  rc_ = ensure_ready(c, "mrh_raycast");
-  if (rc_) return rc_;
-  const size_t npix = (size_t) rc.rows * (size_t) rc.cols;
-  const size_t bytes = npix * (sizeof(float) * 4 + 3);
-  rc_ = regrow(c, c->d_ray, c->ray_cap, npix, bytes, false);  // the previous raycast has finished (it blocked): nothing reads the old buffers
-  if (rc_) return rc_;
-  if ((rc_ = regrow_pinned(c, c->h_ray, c->h_ray_cap, npix, bytes))) return rc_;
-  const bool want_n = out_normals && (p->outputs & MRH_RAYCAST_NORMALS), want_c = out_rgb && (p->outputs & MRH_RAYCAST_COLORS);
-  float* d_depth = (float*) c->d_ray;
-  float* d_normals = (float*) (c->d_ray + npix * sizeof(float));
-  uint8_t* d_rgb = (uint8_t*) (c->d_ray + npix * sizeof(float) * 4);
-  launch_raycast(c, rc, out_depth ? d_depth : nullptr, want_n ? d_normals : nullptr, want_c ? d_rgb : nullptr);
-  HIP_TRY(c, hipGetLastError());
-  if (out_depth) HIP_TRY(c, hipMemcpyAsync(c->h_ray, d_depth, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (want_n) HIP_TRY(c, hipMemcpyAsync(c->h_ray + npix * sizeof(float), d_normals, npix * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (want_c) HIP_TRY(c, hipMemcpyAsync(c->h_ray + npix * sizeof(float) * 4, d_rgb, npix * 3, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (out_depth) *out_depth = (const float*) c->h_ray;
-  if (out_normals) *out_normals = want_n ? (const float*) (c->h_ray + npix * sizeof(float)) : nullptr;
-  if (out_rgb) *out_rgb = want_c ? (const uint8_t*) (c->h_ray + npix * sizeof(float) * 4) : nullptr;
-  return MRH_OK;
+  return raycast_host(c, "mrh_raycast", MRH_CAMERA_PINHOLE, p, R_row_major, t, out_depth, out_normals, out_rgb, nullptr);
 }
 
 int mrh_raycast_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_depth, float* d_normals,
                        uint8_t* d_rgb) {
-  if (!c) return MRH_ERR_INVALID_ARG;
-  RayCam rc;
-  int rc_ = raycast_args(c, "mrh_raycast_device", p, R_row_major, t, &rc);
-  if (rc_) return rc_;
-  rc_ = ensure_ready(c, "mrh_raycast_device");
-  if (rc_) return rc_;
-  launch_raycast(c, rc, d_depth, (p->outputs & MRH_RAYCAST_NORMALS) ? d_normals : nullptr, (p->outputs & MRH_RAYCAST_COLORS) ? d_rgb : nullptr);
-  HIP_TRY(c, hipGetLastError());
-  return MRH_OK;
+  return raycast_device(c, "mrh_raycast_device", MRH_CAMERA_PINHOLE, p, R_row_major, t, RayOut{d_depth, d_normals, d_rgb, nullptr});
+}
+
+int mrh_raycast_spherical(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], const float** out_range,
+                          const float** out_normals, const uint8_t** out_rgb, const float** out_points) {
+  return raycast_host(c, "mrh_raycast_spherical", MRH_CAMERA_SPHERICAL, p, R_row_major, t, out_range, out_normals, out_rgb, out_points);
+}
+
+int mrh_raycast_spherical_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_range,
+                                 float* d_normals, uint8_t* d_rgb, float* d_points) {
+  return raycast_device(c, "mrh_raycast_spherical_device", MRH_CAMERA_SPHERICAL, p, R_row_major, t, RayOut{d_range, d_normals, d_rgb, d_points});
 }
 
 }  // extern "C"

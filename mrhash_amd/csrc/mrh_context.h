@@ -418,8 +418,8 @@ struct mrh_ctx {
   hipEvent_t comm_ev[5] = {};
   mrh_comm_phases comm_phases = {};
   std::vector<EvPair> comm_ev_pool, comm_ev_pending;
-  // raycasting (mrh_raycast.h): the images of mrh_raycast, grow-only — device [depth f32 | normals 3 x f32 | rgb 3 x u8] per
-  // pixel and the pinned host copy the caller reads
+  // raycasting (mrh_raycast.h): the images of mrh_raycast and mrh_raycast_spherical, grow-only — device [depth f32 | normals
+  // 3 x f32 | points 3 x f32 | rgb 3 x u8] per pixel and the pinned host copy the caller reads
   char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
   char* h_ray = nullptr; size_t h_ray_cap = 0;
   // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of

@@ -1,5 +1,6 @@
-// mrh_raycast.h — rendering the map from a pinhole camera: depth, world-frame normal and colour of the first zero crossing
-// of the TSDF along every pixel ray (include/mrhash_raycast.h).
+// mrh_raycast.h — rendering the map from a pinhole or a spherical camera: depth (pinhole) or range (spherical), world-frame
+// normal and colour of the first zero crossing of the TSDF along every pixel ray, and for the spherical camera the crossing as a
+// sensor-frame point: an organised scan (include/mrhash_raycast.h).
 //
 // Reference: findIntersectionBisection (vds.cu:348-383) with n_iteration_bisection = 3 (params.h:26), trilinearInterpolation
 // (vds.cu:260-338, restated by mrh_mc.h:trilinear, which is used here as it is), getVoxelSize (vds.cu:236-240), getVoxel
@@ -7,7 +8,8 @@
 // that marches a ray; the march, the hit rule and the outputs are this project's definition D11.
 //
 // Layout: one lane per pixel, a wave64 renders an 8 x 8 tile (its rays share blocks and table slots), a workgroup of four
-// waves a 16 x 16 tile.  Read-only on the map: no atomics, plain stores of the three images.
+// waves a 16 x 16 tile.  Read-only on the map: no atomics, plain stores of the images.  k_raycast<false> is the pinhole
+// render, k_raycast<true> the spherical one: they differ in the ray's direction and in the points image, nothing else.
 #pragma once
 
 #include "mrh_mc.h"
@@ -98,17 +100,36 @@ __device__ __forceinline__ bool ray_refine(const Map& m, const Tab& t, const Nei
   return true;
 }
 
+// The sensor-frame direction of pixel (r, c).  Pinhole: camera.cuh:88 with d = 1.  Spherical: camera.cuh:91-99 with d = 1, the
+// expressions of inverse_projection_m (mrh_device.h) — azimuth from the column, elevation from the row, sine and cosine through
+// mrh_sincosf (the host has checked that every pixel's angle is in its domain).
+template <bool SPH>
+__device__ __forceinline__ f3 ray_dir_sensor(const RayCam& rc, const int r, const int c) {
+  const float u = rc.ifx * (((float) c - rc.cx) - 0.5f);
+  const float v = rc.ify * (((float) r - rc.cy) - 0.5f);
+  if (!SPH) return mk3(u, v, 1.f);
+  float s0, c0, s1, c1;
+  mrh_sincosf(u, &s0, &c0);
+  mrh_sincosf(v, &s1, &c1);
+  return mk3(c0 * c1, s0 * c1, s1);
+}
+
+// out_depth: camera z of the crossing (pinhole) or the range along the ray (spherical).  out_points (spherical only): the
+// crossing in the sensor frame, range * d_c = inverse_projection_m(r, c, range); a miss is (0, 0, 0), a missing return.
+template <bool SPH>
 __global__ __launch_bounds__(256) void k_raycast(const Map m, const Tab t, const RayCam rc, float* __restrict__ out_depth,
-                                                 float* __restrict__ out_normals, uint8_t* __restrict__ out_rgb) {
+                                                 float* __restrict__ out_normals, uint8_t* __restrict__ out_rgb, float* __restrict__ out_points) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
   const int r = blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
   if (r >= rc.rows || c >= rc.cols) return;
-  // camera.cuh:88 with d = 1, then R d_c with every row summed left to right (cuda_algebra.cuh:71-75)
-  const float dcx = rc.ifx * (((float) c - rc.cx) - 0.5f);
-  const float dcy = rc.ify * (((float) r - rc.cy) - 0.5f);
-  const f3 d = mk3(rc.R[0] * dcx + rc.R[1] * dcy + rc.R[2] * 1.f, rc.R[3] * dcx + rc.R[4] * dcy + rc.R[5] * 1.f,
-                   rc.R[6] * dcx + rc.R[7] * dcy + rc.R[8] * 1.f);
+  // d_w = R d_c with every row summed left to right (cuda_algebra.cuh:71-75)
+  f3 d;
+  {
+    const f3 dc = ray_dir_sensor<SPH>(rc, r, c);
+    d = mk3(rc.R[0] * dc.x + rc.R[1] * dc.y + rc.R[2] * dc.z, rc.R[3] * dc.x + rc.R[4] * dc.y + rc.R[5] * dc.z,
+            rc.R[6] * dc.x + rc.R[7] * dc.y + rc.R[8] * dc.z);
+  }
   Neigh nb = neigh_none();  // no workgroup neighbourhood: every block through the table
   nb.shift_limit = m.block_shift_limit;
   // empty-space skipping is allowed when every position of this ray stays within kRaySkipReachVoxels of the origin
@@ -196,6 +217,12 @@ __global__ __launch_bounds__(256) void k_raycast(const Map m, const Tab t, const
     out_rgb[3 * pix + 0] = (uint8_t) (rgbw & 0xFF);
     out_rgb[3 * pix + 1] = (uint8_t) ((rgbw >> 8) & 0xFF);
     out_rgb[3 * pix + 2] = (uint8_t) ((rgbw >> 16) & 0xFF);
+  }
+  if (SPH && out_points) {  // d_c again rather than three registers held across the march: the same operations, the same bits
+    const f3 dc = ray_dir_sensor<SPH>(rc, r, c);
+    out_points[3 * pix + 0] = hit ? depth * dc.x : 0.f;  // a miss is +0 in every component, whatever the sign of d_c
+    out_points[3 * pix + 1] = hit ? depth * dc.y : 0.f;
+    out_points[3 * pix + 2] = hit ? depth * dc.z : 0.f;
   }
 }
 

@@ -172,6 +172,29 @@ PYBIND11_MODULE(pygeowrapper, m) {
       std::memcpy(colors.mutable_data(), im.colors.data(), im.colors.size());
       return py::make_tuple(depth, normals, colors);
     }, py::arg("t") = py::none(), py::arg("q") = py::none())
+    // ... and with the spherical camera of the last setCamera: (range [H, W] f32, normals [H, W, 3] f32 world frame, colors
+    // [H, W, 3] u8, points [H * W, 3] f32 sensor frame — an organised scan, (0, 0, 0) where nothing was hit)
+    .def("raycastScan", [](GeoWrapper& g, std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                           std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> q) {
+      if (t.has_value() != q.has_value()) throw std::runtime_error("GeoWrapper::raycastScan|give both t and q, or neither");
+      GeoWrapper::RaycastScan im;
+      if (t) {
+        if (t->size() != 3 || q->size() != 4) throw std::runtime_error("GeoWrapper::raycastScan|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+        im = g.raycastScan({t->data()[0], t->data()[1], t->data()[2]}, {q->data()[0], q->data()[1], q->data()[2], q->data()[3]});
+      } else {
+        im = g.raycastScan();
+      }
+      const size_t H = (size_t) im.rows, W = (size_t) im.cols;
+      py::array_t<float> range({H, W});
+      py::array_t<float> normals({H, W, (size_t) 3});
+      py::array_t<uint8_t> colors({H, W, (size_t) 3});
+      py::array_t<float> points({H * W, (size_t) 3});
+      std::memcpy(range.mutable_data(), im.range.data(), im.range.size() * sizeof(float));
+      std::memcpy(normals.mutable_data(), im.normals.data(), im.normals.size() * sizeof(float));
+      std::memcpy(colors.mutable_data(), im.colors.data(), im.colors.size());
+      std::memcpy(points.mutable_data(), im.points.data(), im.points.size() * sizeof(float));
+      return py::make_tuple(range, normals, colors, points);
+    }, py::arg("t") = py::none(), py::arg("q") = py::none())
     .def("clearBuffers", &GeoWrapper::clearBuffers)
     .def("serializeData", &GeoWrapper::serializeData, py::arg("filename_hash") = "./data/hash_points.ply",
          py::arg("filename_voxel") = "./data/voxel_points.ply")
