@@ -311,16 +311,30 @@ __device__ __forceinline__ i3 world_to_block_r(const GridRcp& g, f3 pt) {
 // float detour (vhu.cuh:75-103: voxel -> world -> +-1e-5 -> / (8 * vs) -> floor / ceil): mrh_create evaluates the
 // float form for every voxel coordinate and records the first |v| at which it leaves floor(v / 8)
 // (k_block_shift_limit); beyond that bound (hundreds of metres from the origin) the float form is used.
-__device__ __forceinline__ i3 world_to_block_fast(const GridRcp& g, f3 pt, const int limit) {
+//
+// The world -> voxel half (world_to_voxel above) without its sign selects.  For the quotient p the literal form is
+//   a = p + float(sign(p)) * 0.5;   v = int(a >= 0 ? floor(a + eps) : ceil(a - eps))
+// and voxel_round_arg(p) returns an x with int(x) == v (int(.) = v_cvt_i32_f32: toward zero, saturating, NaN -> 0):
+//   p != 0, not NaN: float(sign(p)) * 0.5 == copysign(0.5, p) exactly, so a is the same float; |a| >= 0.5 and a has p's sign
+//                    (adding 0.5 of the same sign cannot cancel), so `a >= 0` == `p > 0` and the literal form picks
+//                    a + copysign(eps, p) == x.  x has a's sign (eps of the same sign is added), and for x >= 0 floor(x),
+//                    for x <= 0 ceil(x) are the integer the conversion truncates x to (+-inf saturate either way).
+//   p == +-0:        literal a = +0, v = int(floor(1e-5)) = 0; here a = +-0.5, x = +-(0.5 + 1e-5 rounded), int(x) = 0.
+//   p NaN:           a and x are NaN in both forms, int(NaN) = 0.
+// tests/test_kfront_rewrites.py sweeps the float range against the literal form.
+__device__ __forceinline__ float voxel_round_arg(const float p) {
   const float epsilon = 1e-5;
-  const f3 p = mk3(div_rr(pt.x, g.vs, g.r_vs), div_rr(pt.y, g.vs, g.r_vs), div_rr(pt.z, g.vs, g.r_vs));
-  f3 a = mk3(p.x + (float) signi(p.x) * 0.5f, p.y + (float) signi(p.y) * 0.5f, p.z + (float) signi(p.z) * 0.5f);
-  a.x = (a.x >= 0) ? floorf(a.x + epsilon) : ceilf(a.x - epsilon);
-  a.y = (a.y >= 0) ? floorf(a.y + epsilon) : ceilf(a.y - epsilon);
-  a.z = (a.z >= 0) ? floorf(a.z + epsilon) : ceilf(a.z - epsilon);
-  const i3 v = mki3(f2i_hw(a.x), f2i_hw(a.y), f2i_hw(a.z));
-  const int ax = v.x < 0 ? -v.x : v.x, ay = v.y < 0 ? -v.y : v.y, az = v.z < 0 ? -v.z : v.z;
-  if ((u32) (ax | ay | az) < (u32) limit) return mki3(v.x >> 3, v.y >> 3, v.z >> 3);  // (a | b | c) < 2^k bound, limit is a power of two
+  return (p + __builtin_copysignf(0.5f, p)) + __builtin_copysignf(epsilon, p);
+}
+// The shift-limit test on the floats: with v = int(x), (|v.x| | |v.y| | |v.z|) < limit for a power of two `limit` (or 0) says
+// |v| < limit on every axis, and |int(x)| < L  <=>  |x| < L for an integer L >= 0 (truncation toward zero; a saturated
+// conversion has |x| >= 2^31 > L).  fmaxf ignores a NaN operand, as the OR ignores its v = 0; if all three are NaN the test
+// fails and voxel_to_block((0, 0, 0)) runs, which is the shift's (0, 0, 0) whenever limit > 0 (k_block_shift_limit
+// checked v = 0) and is what the literal test chose for limit == 0.
+__device__ __forceinline__ i3 world_to_block_fast(const GridRcp& g, f3 pt, const int limit) {
+  const f3 x = mk3(voxel_round_arg(div_rr(pt.x, g.vs, g.r_vs)), voxel_round_arg(div_rr(pt.y, g.vs, g.r_vs)), voxel_round_arg(div_rr(pt.z, g.vs, g.r_vs)));
+  const i3 v = mki3(f2i_hw(x.x), f2i_hw(x.y), f2i_hw(x.z));
+  if (fmaxf(fmaxf(fabsf(x.x), fabsf(x.y)), fabsf(x.z)) < (float) limit) return mki3(v.x >> 3, v.y >> 3, v.z >> 3);  // limit <= 2^22: exact as a float
   return voxel_to_block(v, g.vs);
 }
 

@@ -96,7 +96,7 @@ __device__ __forceinline__ bool tile_rays(const Cam& c, const Map& m, uint2* __r
       if (!ray_keys_in_range(ray)) {
         slow = true;
       } else {
-        slow = !walk_ray_lean(m, ray, [&](const i3 cur, const u64 key) {
+        slow = !walk_ray_lean(m, ray, [&](const i3 cur, const u64 key) __attribute__((always_inline)) {
           u32 s = (u32) __mul24(cur.z, 5851) + (u32) __mul24(cur.y, 73) + (u32) cur.x;
           s = (s ^ (s >> 7)) & (kRayCap - 1);
 #pragma unroll 1

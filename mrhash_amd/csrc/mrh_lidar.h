@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_alloc3d(const Cam c, const Map m, const
       const RayState ray = ray_from_segment(m, pw_min, pw_max);
       bool slow = !ray_keys_in_range(ray);
       if (!slow) {
-        slow = !walk_ray_lean(m, ray, [&](const i3 cur, const u64 key) {
+        slow = !walk_ray_lean(m, ray, [&](const i3 cur, const u64 key) __attribute__((always_inline)) {
           u32 s = (u32) __mul24(cur.z, 5851) + (u32) __mul24(cur.y, 73) + (u32) cur.x;
           s = (s ^ (s >> 7)) & (kRayCap - 1);
 #pragma unroll 1
@@ -96,6 +96,7 @@ __global__ __launch_bounds__(256) void k_alloc3d(const Cam c, const Map m, const
       }
       if (slow) {  // LDS set saturated or keys out of range: the literal walk with direct inserts
         RayState r = ray;
+        r.bound = ray_bound_literal(ray);
 #pragma unroll 1
         for (u32 iter = 0; iter < kMaxDdaIter; iter++) {
           u64 key;
