@@ -178,6 +178,7 @@ int arena_layout(mrh_ctx* c, const int slot, MeshScratch* m, Layout&& lay) {
 #include "mrh_extract.h"
 #include "mrh_points.h"
 #include "mrh_blocks.h"
+#include "mrh_xplan.h"
 #include "mrh_comm.h"
 
 extern "C" {

@@ -145,31 +145,42 @@ int exchange_room(mrh_ctx* c, char*& p, size_t& cap, const size_t bytes) {
   return need <= cap ? MRH_OK : regrow_keep(c, p, cap, need + need / 4, need + need / 4, 0);
 }
 
+// A small host-to-host collective through d_small on stream `s`: H2D, collective(d_send, d_recv, s), D2H, synchronise.  The result
+// lies `recv_off` bytes behind what was sent (0: in place).  The communicator's helpers pass the communicator's stream,
+// ctx_allgather_u64 the context's.
+template <class Collective>
+int comm_staged(mrh_comm* m, hipStream_t s, const void* send, const size_t send_bytes, void* recv, const size_t recv_bytes, const size_t recv_off,
+                const char* what, Collective collective) {
+  const int rc = comm_small(m, recv_off + recv_bytes);
+  if (rc) return rc;
+  COMM_HIP(m, hipMemcpyAsync(m->d_small, send, send_bytes, hipMemcpyHostToDevice, s));
+  const ncclResult_t r = collective(m->d_small, m->d_small + recv_off, s);
+  if (r != ncclSuccess) return comm_fail(m, MRH_ERR_DEVICE, "%s failed: %s", what, rccl()->GetErrorString(r));
+  COMM_HIP(m, hipMemcpyAsync(recv, m->d_small + recv_off, recv_bytes, hipMemcpyDeviceToHost, s));
+  COMM_HIP(m, hipStreamSynchronize(s));
+  return MRH_OK;
+}
+
 // every rank's `n_words` 64-bit words -> all[world * n_words] on the host (device staging in the communicator, the
 // collective on the CONTEXT's stream so that it is ordered with the pack that produced the numbers)
 int ctx_allgather_u64(mrh_ctx* c, const uint64_t* mine, const size_t n_words, uint64_t* all) {
   mrh_comm* m = c->comm;
   const size_t bytes = n_words * sizeof(uint64_t);
-  if (comm_small(m, bytes * ((size_t) m->world + 1))) return fail(c, MRH_ERR_DEVICE, "%s", m->err.c_str());
-  char* d_send = m->d_small;
-  char* d_recv = m->d_small + bytes;
-  HIP_TRY(c, hipMemcpyAsync(d_send, mine, bytes, hipMemcpyHostToDevice, c->stream));
-  CTX_NCCL(c, rccl()->AllGather(d_send, d_recv, n_words, ncclUint64, m->nccl, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(all, d_recv, bytes * (size_t) m->world, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MRH_OK;
+  const int rc = comm_staged(m, c->stream, mine, bytes, all, bytes * (size_t) m->world, bytes, "ncclAllGather", [&](const void* d_send, void* d_recv, hipStream_t s) {
+    return rccl()->AllGather(d_send, d_recv, n_words, ncclUint64, m->nccl, s);
+  });
+  return rc ? fail(c, rc, "%s", m->err.c_str()) : MRH_OK;
 }
 
 // Every rank contributes the status of its local steps as word 0 of a small all-gather (plus `n_words` payload words); the
 // call fails on EVERY rank if it failed on any, so that no rank walks into a data collective its peers will never join (a
 // pack error, an out-of-memory in exchange_room, a broken owner partition on one rank used to leave the others hanging inside
-// ncclSend / ncclRecv, which have no time limit).  all: world * (1 + n_words) words, rank r's at r * (1 + n_words).
-int ctx_agree(mrh_ctx* c, const int local_rc, const char* who, const uint64_t* mine, const size_t n_words, std::vector<uint64_t>& all) {
+// ncclSend / ncclRecv, which have no time limit).  counts: the payload alone, world * n_words words, rank r's at r * n_words.
+int ctx_agree(mrh_ctx* c, const int local_rc, const char* who, const uint64_t* mine = nullptr, const size_t n_words = 0, std::vector<uint64_t>* counts = nullptr) {
   mrh_comm* m = c->comm;
-  std::vector<uint64_t> send(1 + n_words, 0);
+  std::vector<uint64_t> send(1 + n_words, 0), all((size_t) m->world * (1 + n_words), 0);
   send[0] = (uint64_t) (uint32_t) local_rc;
-  for (size_t i = 0; i < n_words; i++) send[1 + i] = mine ? mine[i] : 0;
-  all.assign((size_t) m->world * (1 + n_words), 0);
+  for (size_t i = 0; i < n_words; i++) send[1 + i] = mine[i];
   const std::string local_err = local_rc ? c->err : std::string();
   const int rc = ctx_allgather_u64(c, send.data(), 1 + n_words, all.data());
   if (rc) return rc;  // the collective itself failed: nothing more can be agreed on
@@ -177,6 +188,11 @@ int ctx_agree(mrh_ctx* c, const int local_rc, const char* who, const uint64_t* m
   for (int r = 0; r < m->world; r++) {
     const int prc = (int) (uint32_t) all[(size_t) r * (1 + n_words)];
     if (prc) return fail(c, MRH_ERR_STATE, "%s: rank %d reported error %d before the exchange; nothing was moved", who, r, prc);
+  }
+  if (counts) {
+    counts->clear();
+    for (size_t i = 0; i < all.size(); i++)
+      if (i % (1 + n_words)) counts->push_back(all[i]);  // every word but the status
   }
   return MRH_OK;
 }
@@ -217,6 +233,95 @@ struct PhaseClock {
   }
 };
 
+// The only place that calls ncclSend / ncclRecv: a plan's parts (mrh_xplan.h) as one group on the CONTEXT's stream, behind the pack
+// that filled the send sides.  send_base / recv_base: where each stream's two sides begin.  Only after both ctx_agree rounds of an
+// exchange: every rank comes here or none does.
+int issue_plan(mrh_ctx* c, const XPlan& p, const char* const send_base[2], char* const recv_base[2]) {
+  if (p.parts.empty()) return MRH_OK;
+  CTX_NCCL(c, rccl()->GroupStart());
+  for (const XPart& x : p.parts) {
+    if (x.send) CTX_NCCL(c, rccl()->Send(send_base[x.stream] + x.off, x.bytes, ncclUint8, x.peer, c->comm->nccl, c->stream));
+    else CTX_NCCL(c, rccl()->Recv(recv_base[x.stream] + x.off, x.bytes, ncclUint8, x.peer, c->comm->nccl, c->stream));
+  }
+  CTX_NCCL(c, rccl()->GroupEnd());
+  return MRH_OK;
+}
+
+// the starve all-reduces whose events have completed (the caller has synchronised the stream) go into comm_phases, their events back to the pool
+int comm_fold_pending(mrh_ctx* c) {
+  for (auto& e : c->comm_ev_pending) {
+    float ms = 0.f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
+    c->comm_phases.allreduce_ms_sum += ms; c->comm_phases.allreduce_count++;
+    c->comm_ev_pool.push_back(e);
+  }
+  c->comm_ev_pending.clear();
+  return MRH_OK;
+}
+
+// ---- the larger stages of the exchanges below ---------------------------------------------------------------------------------------
+
+// merge, local pack: the new sharding, then ONE send buffer with the parts in destination order, row[dest] records each (every live
+// block has exactly one owner: n_all records in total) — the layout xplan_merge reads the send offsets from.  Marks start and packed.
+int merge_pack(mrh_ctx* c, PhaseClock& clk, const int chunk_log2, uint64_t* row) {
+  const size_t rec = sizeof(mrh_block_record);
+  int rc = mrh_set_sharding(c, c->comm->rank, c->comm->world, chunk_log2);
+  if (rc) return rc;
+  if ((rc = clk.mark())) return rc;
+  int n_all = 0;
+  if ((rc = select_blocks(c, kSelAll, 0, &n_all))) return rc;
+  if ((rc = exchange_room(c, c->d_xsend, c->xsend_cap, (size_t) n_all * rec))) return rc;
+  uint64_t packed = 0;
+  for (int dest = 0; dest < c->comm->world; dest++) {
+    int n = 0;
+    if ((rc = select_blocks(c, kSelOwner, dest, &n))) return rc;
+    row[dest] = (uint64_t) n;
+    if (packed + (uint64_t) n > (uint64_t) n_all) return fail(c, MRH_ERR_STATE, "mrh_comm_merge_submaps: the owner partition does not add up");
+    pack_selected(c, n, c->d_xsend + packed * rec);
+    packed += (uint64_t) n;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return clk.mark();
+}
+
+// gather: a rank's block metadata travels as [nb descriptors | nb counts], kMetaBlock bytes a block
+constexpr size_t kMetaDesc = sizeof(mrh_block_desc), kMetaCount = sizeof(uint32_t), kMetaBlock = kMetaDesc + kMetaCount;
+
+// gather, local pack: the extraction (the soup stays in c->d_soup, *nt triangles) and the metadata of the non-empty blocks
+int gather_pack(mrh_ctx* c, std::vector<mrh_block_desc>& my_d, std::vector<uint32_t>& my_c, uint64_t* nt) {
+  const mrh_block_desc* descs = nullptr;
+  const uint32_t* cnts = nullptr;
+  uint64_t nblk = 0;
+  int rc = mrh_extract_triangles(c, nullptr, nt);
+  if (!rc) rc = mrh_get_triangle_blocks(c, &descs, &cnts, &nblk);
+  if (rc) return rc;
+  for (uint64_t i = 0; i < nblk; i++)
+    if (cnts[i]) { my_d.push_back(descs[i]); my_c.push_back(cnts[i]); }
+  return MRH_OK;
+}
+
+// gather, consume on the root: every rank's metadata from its segment of area[0] into two arrays in rank order, then the run merge
+// over the triangles in area[1]
+int gather_consume(mrh_ctx* c, const XPlan& plan, char* const area[2], uint64_t* out_triangles) {
+  const uint64_t meta_all = plan.area_bytes[0], tot_b = meta_all / kMetaBlock, tot_t = plan.area_bytes[1] / sizeof(mrh_triangle);
+  std::vector<char> h_meta(meta_all ? meta_all : 1);
+  if (meta_all) HIP_TRY(c, hipMemcpyAsync(h_meta.data(), area[0], meta_all, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::vector<mrh_block_desc> all_d((size_t) tot_b);
+  std::vector<uint32_t> all_c((size_t) tot_b);
+  for (const XSeg& g : plan.seg[0]) {
+    const uint64_t b = g.bytes / kMetaBlock, at = g.off / kMetaBlock;
+    if (!b) continue;
+    memcpy(&all_d[at], h_meta.data() + g.off, b * kMetaDesc);
+    memcpy(&all_c[at], h_meta.data() + g.off + b * kMetaDesc, b * kMetaCount);
+  }
+  // area[1] is not c->d_soup: the run merge writes the soup buffer while it reads this one
+  const int rc = mrh_process_triangle_runs(c, all_d.data(), all_c.data(), tot_b, (const mrh_triangle*) area[1], tot_t, 1);
+  if (rc) return rc;
+  if (out_triangles) *out_triangles = tot_t;
+  return MRH_OK;
+}
+
 }  // namespace
 
 static bool comm_matches_sharding(const mrh_ctx* c, int* comm_rank, int* comm_world) {
@@ -238,17 +343,9 @@ static int comm_allreduce_zbuf(mrh_ctx* c, u64* buf, const size_t n) {
   CTX_NCCL(c, rccl()->AllReduce(buf, buf, n, ncclInt64, ncclMin, c->comm->nccl, c->stream));
   HIP_TRY(c, hipEventRecord(ev.b, c->stream));
   c->comm_ev_pending.push_back(ev);
-  if (c->comm_ev_pending.size() >= 1024) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (auto& e : c->comm_ev_pending) {
-      float ms = 0.f;
-      HIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
-      c->comm_phases.allreduce_ms_sum += ms; c->comm_phases.allreduce_count++;
-      c->comm_ev_pool.push_back(e);
-    }
-    c->comm_ev_pending.clear();
-  }
-  return MRH_OK;
+  if (c->comm_ev_pending.size() < 1024) return MRH_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return comm_fold_pending(c);
 }
 
 extern "C" {
@@ -375,14 +472,10 @@ int mrh_comm_allreduce_f64(mrh_comm* m, double* inout, uint64_t n, int op) {
   if (op != MRH_COMM_SUM && op != MRH_COMM_MAX && op != MRH_COMM_MIN) return comm_fail(m, MRH_ERR_INVALID_ARG, "mrh_comm_allreduce_f64: bad op %d", op);
   if (n == 0) return MRH_OK;
   COMM_HIP(m, hipSetDevice(m->device));
-  int rc = comm_small(m, n * sizeof(double));
-  if (rc) return rc;
-  COMM_HIP(m, hipMemcpyAsync(m->d_small, inout, n * sizeof(double), hipMemcpyHostToDevice, m->stream));
   const ncclRedOp_t o = op == MRH_COMM_SUM ? ncclSum : op == MRH_COMM_MAX ? ncclMax : ncclMin;
-  COMM_NCCL(m, rccl()->AllReduce(m->d_small, m->d_small, n, ncclFloat64, o, m->nccl, m->stream));
-  COMM_HIP(m, hipMemcpyAsync(inout, m->d_small, n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-  COMM_HIP(m, hipStreamSynchronize(m->stream));
-  return MRH_OK;
+  return comm_staged(m, m->stream, inout, n * sizeof(double), inout, n * sizeof(double), 0, "ncclAllReduce", [&](const void* d_send, void* d_recv, hipStream_t s) {
+    return rccl()->AllReduce(d_send, d_recv, n, ncclFloat64, o, m->nccl, s);
+  });
 }
 
 int mrh_comm_barrier(mrh_comm* m) {
@@ -394,13 +487,9 @@ int mrh_comm_allgather_bytes(mrh_comm* m, const void* send, uint64_t bytes, void
   if (!m || (bytes && (!send || !recv))) return MRH_ERR_INVALID_ARG;
   if (bytes == 0) return MRH_OK;
   COMM_HIP(m, hipSetDevice(m->device));
-  int rc = comm_small(m, bytes * ((size_t) m->world + 1));
-  if (rc) return rc;
-  COMM_HIP(m, hipMemcpyAsync(m->d_small, send, bytes, hipMemcpyHostToDevice, m->stream));
-  COMM_NCCL(m, rccl()->AllGather(m->d_small, m->d_small + bytes, bytes, ncclUint8, m->nccl, m->stream));
-  COMM_HIP(m, hipMemcpyAsync(recv, m->d_small + bytes, bytes * (size_t) m->world, hipMemcpyDeviceToHost, m->stream));
-  COMM_HIP(m, hipStreamSynchronize(m->stream));
-  return MRH_OK;
+  return comm_staged(m, m->stream, send, bytes, recv, bytes * (size_t) m->world, bytes, "ncclAllGather", [&](const void* d_send, void* d_recv, hipStream_t s) {
+    return rccl()->AllGather(d_send, d_recv, bytes, ncclUint8, m->nccl, s);
+  });
 }
 
 int mrh_comm_attach(mrh_ctx* c, mrh_comm* m) {
@@ -424,243 +513,139 @@ int mrh_comm_phase_times(mrh_ctx* c, mrh_comm_phases* out) {
   if (rc) return rc;
   if (!out) return MRH_ERR_INVALID_ARG;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (auto& e : c->comm_ev_pending) {
-    float ms = 0.f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, e.a, e.b));
-    c->comm_phases.allreduce_ms_sum += ms; c->comm_phases.allreduce_count++;
-    c->comm_ev_pool.push_back(e);
-  }
-  c->comm_ev_pending.clear();
+  if ((rc = comm_fold_pending(c))) return rc;
   *out = c->comm_phases;
   return MRH_OK;
 }
 
+// The three exchanges run the same stages: checks, local pack, agree on the counts, plan and receive room, agree, issue, consume,
+// phases.  Either every rank enters the data exchange or none does: the status of a rank's local steps travels as word 0 of both
+// ctx_agree rounds, the first behind the pack, the second behind the receive room.  The plan (mrh_xplan.h) decides every offset and
+// size and which zero-size parts both sides skip; the data moves on the context's stream.  Events: start, packed, counted, moved, consumed.
+
 int mrh_comm_exchange_halo(mrh_ctx* c, uint64_t* out_taken) {
-  int rc = need_comm(c, "mrh_comm_exchange_halo");
+  const char* who = "mrh_comm_exchange_halo";
+  int rc = need_comm(c, who);  // checks
   if (rc) return rc;
   if (out_taken) *out_taken = 0;
-  mrh_comm* m = c->comm;
-  const int world = m->world, rank = m->rank;
-  if (c->p.shard_count != world || c->p.shard_rank != rank)
+  int rank = 0, world = 1;
+  if (!comm_matches_sharding(c, &rank, &world))
     return fail(c, MRH_ERR_STATE, "mrh_comm_exchange_halo: the context is shard %d of %d, the communicator rank %d of %d", c->p.shard_rank, c->p.shard_count, rank, world);
+  const size_t rec = sizeof(mrh_block_record);
   PhaseClock clk(c);
   const mrh_block_record* mine = nullptr;
-  uint64_t n = 0;
-  const size_t rec = sizeof(mrh_block_record);
-  // local steps first, their status travels with the counts: either every rank enters the data exchange or none does
-  rc = clk.mark();
+  uint64_t n = 0, taken = 0;
+  rc = clk.mark();  // local pack
   if (!rc) rc = mrh_pack_blocks(c, MRH_PACK_HALO, 0, &mine, &n, nullptr);
   if (!rc) rc = clk.mark();
-  std::vector<uint64_t> agreed;
-  rc = ctx_agree(c, rc, "mrh_comm_exchange_halo", &n, 1, agreed);
+  std::vector<uint64_t> counts;
+  rc = ctx_agree(c, rc, who, &n, 1, &counts);  // agree on the counts
   if (rc) return rc;
-  std::vector<uint64_t> counts((size_t) world);
-  for (int r = 0; r < world; r++) counts[r] = agreed[2 * (size_t) r + 1];
   if ((rc = clk.mark())) return rc;
-  uint64_t total_in = 0;
-  std::vector<uint64_t> off((size_t) world, 0);
-  const bool self = comm_self_loop();
-  for (int r = 0; r < world; r++) { off[r] = total_in; if (r != rank || self) total_in += counts[r]; }
-  rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, total_in * rec);
-  rc = ctx_agree(c, rc, "mrh_comm_exchange_halo", nullptr, 0, agreed);  // the receive buffer exists on every rank
+  const XPlan plan = xplan_halo(world, rank, comm_self_loop(), counts.data(), rec);  // plan and receive room
+  rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, plan.recv_bytes);
+  rc = ctx_agree(c, rc, who);  // agree: the receive buffer exists on every rank
   if (rc) return rc;
-  if (world > 1 || self) {
-    CTX_NCCL(c, rccl()->GroupStart());
-    for (int r = 0; r < world; r++) {
-      if (r == rank && !self) continue;
-      if (n) CTX_NCCL(c, rccl()->Send(mine, (size_t) n * rec, ncclUint8, r, m->nccl, c->stream));
-      if (counts[r]) CTX_NCCL(c, rccl()->Recv(c->d_xrecv + off[r] * rec, (size_t) counts[r] * rec, ncclUint8, r, m->nccl, c->stream));
-    }
-    CTX_NCCL(c, rccl()->GroupEnd());
-  }
+  const char* const from[2] = {(const char*) mine, nullptr};
+  char* const to[2] = {c->d_xrecv, nullptr};
+  if ((rc = issue_plan(c, plan, from, to))) return rc;  // issue
   if ((rc = clk.mark())) return rc;
-  uint64_t taken = 0;
-  if (total_in) {  // one call over every peer's records: a position has exactly one owner, so the keys are unique
-    rc = mrh_unpack_blocks(c, MRH_UNPACK_HALO, (const mrh_block_record*) c->d_xrecv, total_in, 1, &taken);
+  if (plan.recv_bytes) {  // consume, in one call over every peer's records: a position has exactly one owner, so the keys are unique
+    rc = mrh_unpack_blocks(c, MRH_UNPACK_HALO, (const mrh_block_record*) c->d_xrecv, plan.recv_bytes / rec, 1, &taken);
     if (rc) return rc;
   }
   if ((rc = clk.mark())) return rc;
   if (out_taken) *out_taken = taken;
-  return clk.finish((uint64_t) (world - 1) * n * rec, total_in * rec);
+  return clk.finish(plan.bytes_out, plan.bytes_in);  // phases
 }
 
 int mrh_comm_merge_submaps(mrh_ctx* c, int chunk_log2, mrh_comm_merge_info* out) {
-  int rc = need_comm(c, "mrh_comm_merge_submaps");
+  const char* who = "mrh_comm_merge_submaps";
+  int rc = need_comm(c, who);  // checks
   if (rc) return rc;
   if (out) memset(out, 0, sizeof *out);
   if (c->halo_upper) return fail(c, MRH_ERR_STATE, "mrh_comm_merge_submaps: halo blocks are present (mrh_drop_blocks(MRH_DROP_HALO) first)");
-  mrh_comm* m = c->comm;
-  const int world = m->world, rank = m->rank;
+  const int world = c->comm->world, rank = c->comm->rank;
   const int old_rank = c->p.shard_rank, old_count = c->p.shard_count, old_log2 = c->p.shard_chunk_log2;
   const size_t rec = sizeof(mrh_block_record);
   PhaseClock clk(c);
-  // one send buffer, the parts in destination order (every live block has exactly one owner: n_all records in total).
-  // Local steps first; their status travels with the count matrix, so a rank that failed keeps the others out of the exchange.
-  std::vector<uint64_t> out_counts((size_t) world, 0), out_off((size_t) world, 0);
-  auto pack_all = [&]() -> int {
-    int r2 = mrh_set_sharding(c, rank, world, chunk_log2);
-    if (r2) return r2;
-    if ((r2 = clk.mark())) return r2;
-    int n_all = 0;
-    if ((r2 = select_blocks(c, kSelAll, 0, &n_all))) return r2;
-    if ((r2 = exchange_room(c, c->d_xsend, c->xsend_cap, (size_t) n_all * rec))) return r2;
-    uint64_t packed = 0;
-    for (int dest = 0; dest < world; dest++) {
-      int n = 0;
-      if ((r2 = select_blocks(c, kSelOwner, dest, &n))) return r2;
-      out_off[dest] = packed;
-      out_counts[dest] = (uint64_t) n;
-      if (packed + (uint64_t) n > (uint64_t) n_all) return fail(c, MRH_ERR_STATE, "mrh_comm_merge_submaps: the owner partition does not add up");
-      pack_selected(c, n, c->d_xsend + packed * rec);
-      packed += (uint64_t) n;
-    }
-    HIP_TRY(c, hipGetLastError());
-    return clk.mark();
-  };
-  auto restore_sharding = [&](const int code) {  // nothing has been moved or dropped yet: the context goes back to what it was
+  // any failure before the exchange puts the old sharding back: nothing has been moved or dropped yet, the context is what it was
+  auto restore_sharding = [&](const int code) {
     const std::string keep = c->err;
     (void) mrh_set_sharding(c, old_rank, old_count, old_log2);
     c->err = keep;
     return code;
   };
-  rc = pack_all();
-  std::vector<uint64_t> agreed;
-  rc = ctx_agree(c, rc, "mrh_comm_merge_submaps", out_counts.data(), (size_t) world, agreed);
+  std::vector<uint64_t> row((size_t) world, 0), matrix;
+  rc = merge_pack(c, clk, chunk_log2, row.data());        // local pack
+  rc = ctx_agree(c, rc, who, row.data(), world, &matrix);  // agree on the counts: matrix[src * world + dest]
   if (rc) return restore_sharding(rc);
-  std::vector<uint64_t> in_counts((size_t) world), in_off((size_t) world, 0);
-  uint64_t total_in = 0;
-  const bool self = comm_self_loop();
-  for (int src = 0; src < world; src++) {
-    in_counts[src] = agreed[(size_t) src * (world + 1) + 1 + rank];  // matrix[src][dest = this rank]
-    in_off[src] = total_in;
-    if (src != rank || self) total_in += in_counts[src];
-  }
-  rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, total_in * rec);
-  rc = ctx_agree(c, rc, "mrh_comm_merge_submaps", nullptr, 0, agreed);
+  const XPlan plan = xplan_merge(world, rank, comm_self_loop(), matrix.data(), rec);  // plan and receive room
+  rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, plan.recv_bytes);
+  rc = ctx_agree(c, rc, who);  // agree
   if (rc) return restore_sharding(rc);
   if ((rc = clk.mark())) return rc;
-  uint64_t sent = 0;
-  if (world > 1 || self) {
-    CTX_NCCL(c, rccl()->GroupStart());
-    for (int r = 0; r < world; r++) {
-      if (r == rank && !self) continue;
-      if (out_counts[r]) CTX_NCCL(c, rccl()->Send(c->d_xsend + out_off[r] * rec, (size_t) out_counts[r] * rec, ncclUint8, r, m->nccl, c->stream));
-      if (in_counts[r]) CTX_NCCL(c, rccl()->Recv(c->d_xrecv + in_off[r] * rec, (size_t) in_counts[r] * rec, ncclUint8, r, m->nccl, c->stream));
-      if (r != rank) sent += out_counts[r];
-    }
-    CTX_NCCL(c, rccl()->GroupEnd());
-  }
+  const char* const from[2] = {c->d_xsend, nullptr};
+  char* const to[2] = {c->d_xrecv, nullptr};
+  if ((rc = issue_plan(c, plan, from, to))) return rc;  // issue
   if ((rc = clk.mark())) return rc;
-  // the owned blocks come back through the fold, at this rank's position in the order: deterministic for a given world size
+  // consume: every block comes back through the fold, the sub-maps in rank order 0 .. world-1 with the rank's own part at its own
+  // position (read in place from the send buffer without the self-loop): deterministic for a given world size
   rc = mrh_drop_blocks(c, MRH_DROP_ALL, nullptr);
   if (rc) return rc;
   for (int src = 0; src < world; src++) {
-    const char* seg = (src == rank && !self) ? c->d_xsend + out_off[rank] * rec : c->d_xrecv + in_off[src] * rec;
-    if (in_counts[src] == 0) continue;
-    rc = mrh_unpack_blocks(c, MRH_UNPACK_MERGE, (const mrh_block_record*) seg, in_counts[src], 1, nullptr);
+    const XSeg& g = plan.seg[0][src];
+    if (!g.bytes) continue;
+    const char* seg = src == rank && plan.own == kOwnInPlace ? c->d_xsend + plan.own_sent[0].off : c->d_xrecv + g.off;
+    rc = mrh_unpack_blocks(c, MRH_UNPACK_MERGE, (const mrh_block_record*) seg, g.bytes / rec, 1, nullptr);
     if (rc) return rc;
   }
   if ((rc = clk.mark())) return rc;
-  if (out) {
-    out->blocks_sent = sent; out->blocks_received = total_in - (self ? in_counts[rank] : 0); out->bytes_sent = sent * rec; out->blocks_kept = out_counts[rank];
-  }
-  return clk.finish(sent * rec, (total_in - (self ? in_counts[rank] : 0)) * rec);
+  if (out) { out->blocks_sent = plan.sent; out->blocks_received = plan.received; out->bytes_sent = plan.bytes_out; out->blocks_kept = plan.kept; }
+  return clk.finish(plan.bytes_out, plan.bytes_in);  // phases
 }
 
 int mrh_comm_gather_mesh(mrh_ctx* c, int root, uint64_t* out_triangles) {
-  int rc = need_comm(c, "mrh_comm_gather_mesh");
+  const char* who = "mrh_comm_gather_mesh";
+  int rc = need_comm(c, who);  // checks
   if (rc) return rc;
   if (out_triangles) *out_triangles = 0;
-  mrh_comm* m = c->comm;
-  const int world = m->world, rank = m->rank;
+  const int world = c->comm->world, rank = c->comm->rank;
   if (root < 0 || root >= world) return fail(c, MRH_ERR_INVALID_ARG, "mrh_comm_gather_mesh: root %d of %d ranks", root, world);
   PhaseClock clk(c);
-  uint64_t nt = 0;
-  const mrh_block_desc* descs = nullptr;
-  const uint32_t* cnts = nullptr;
-  uint64_t nblk = 0;
-  rc = clk.mark();
-  if (!rc) rc = mrh_extract_triangles(c, nullptr, &nt);  // the soup stays in c->d_soup
-  if (!rc) rc = mrh_get_triangle_blocks(c, &descs, &cnts, &nblk);
-  // per-block metadata of the non-empty blocks: 16-byte descriptor + 4-byte count
   std::vector<mrh_block_desc> my_d;
   std::vector<uint32_t> my_c;
-  if (!rc)
-    for (uint64_t i = 0; i < nblk; i++)
-      if (cnts[i]) { my_d.push_back(descs[i]); my_c.push_back(cnts[i]); }
-  const uint64_t nb = my_d.size();
+  uint64_t nt = 0;
+  rc = clk.mark();  // local pack
+  if (!rc) rc = gather_pack(c, my_d, my_c, &nt);
   if (!rc) rc = clk.mark();
-  const uint64_t mine[2] = {nb, rc ? 0 : nt};
-  std::vector<uint64_t> agreed;
-  rc = ctx_agree(c, rc, "mrh_comm_gather_mesh", mine, 2, agreed);
+  const uint64_t nb = my_d.size(), mine[2] = {nb, rc ? 0 : nt};
+  std::vector<uint64_t> counts;
+  rc = ctx_agree(c, rc, who, mine, 2, &counts);  // agree on the counts: rank r's blocks and triangles at 2 * r
   if (rc) return rc;
-  std::vector<uint64_t> sizes((size_t) world * 2);
-  for (int r = 0; r < world; r++) { sizes[2 * r] = agreed[3 * (size_t) r + 1]; sizes[2 * r + 1] = agreed[3 * (size_t) r + 2]; }
   if ((rc = clk.mark())) return rc;
-  uint64_t tot_b = 0, tot_t = 0;
-  std::vector<uint64_t> boff((size_t) world), toff((size_t) world);
-  for (int r = 0; r < world; r++) { boff[r] = tot_b; toff[r] = tot_t; tot_b += sizes[2 * r]; tot_t += sizes[2 * r + 1]; }
-  // metadata travels through device staging (20 bytes a block), the triangles from soup to soup.  The triangle area starts on a
-  // 256-byte boundary: the run merge reads it with 16-byte loads (k_permute_runs), and 20 * tot_b is only 4-byte aligned.
-  const size_t meta_mine = (size_t) nb * 20, meta_all = (size_t) tot_b * 20, meta_span = (meta_all + 255) & ~(size_t) 255;
-  rc = exchange_room(c, c->d_xsend, c->xsend_cap, meta_mine);
+  // plan and receive room: the metadata travels through device staging, the triangles from the soup to the root's triangle area,
+  // which the plan starts on a 256-byte boundary
+  const uint64_t unit[2] = {kMetaBlock, sizeof(mrh_triangle)};
+  const XPlan plan = xplan_gather(world, rank, comm_self_loop(), root, counts.data(), unit);
+  rc = exchange_room(c, c->d_xsend, c->xsend_cap, nb * kMetaBlock);
   if (!rc && nb) {
-    hipError_t e = hipMemcpyAsync(c->d_xsend, my_d.data(), nb * 16, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->d_xsend + nb * 16, my_c.data(), nb * 4, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(c->d_xsend, my_d.data(), nb * kMetaDesc, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->d_xsend + nb * kMetaDesc, my_c.data(), nb * kMetaCount, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) rc = fail(c, MRH_ERR_DEVICE, "mrh_comm_gather_mesh: staging the block metadata failed: %s", hipGetErrorString(e));
   }
-  const size_t tri = sizeof(mrh_triangle);
-  if (!rc && rank == root) rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, meta_span + tot_t * tri);
-  rc = ctx_agree(c, rc, "mrh_comm_gather_mesh", nullptr, 0, agreed);  // buffers exist everywhere before anybody sends
+  if (!rc && rank == root) rc = exchange_room(c, c->d_xrecv, c->xrecv_cap, plan.recv_bytes);
+  rc = ctx_agree(c, rc, who);  // agree: the buffers exist everywhere before anybody sends
   if (rc) return rc;
-  char* d_meta = c->d_xrecv;             // root: [rank r's descs | counts] at boff[r] * 20
-  char* d_tris = c->d_xrecv + meta_span;  // root: rank r's triangles at toff[r]
-  const mrh_triangle* soup = c->soup_n ? c->d_soup : nullptr;
-  const bool self = comm_self_loop();
-  if (world > 1 || self) {
-    CTX_NCCL(c, rccl()->GroupStart());
-    if (rank == root && self) {
-      if (nb) CTX_NCCL(c, rccl()->Send(c->d_xsend, meta_mine, ncclUint8, root, m->nccl, c->stream));
-      if (nt) CTX_NCCL(c, rccl()->Send(soup, (size_t) nt * tri, ncclUint8, root, m->nccl, c->stream));
-    }
-    if (rank == root) {
-      for (int r = 0; r < world; r++) {
-        if (r == root && !self) continue;
-        if (sizes[2 * r]) CTX_NCCL(c, rccl()->Recv(d_meta + boff[r] * 20, (size_t) sizes[2 * r] * 20, ncclUint8, r, m->nccl, c->stream));
-        if (sizes[2 * r + 1]) CTX_NCCL(c, rccl()->Recv(d_tris + toff[r] * tri, (size_t) sizes[2 * r + 1] * tri, ncclUint8, r, m->nccl, c->stream));
-      }
-    } else {
-      if (nb) CTX_NCCL(c, rccl()->Send(c->d_xsend, meta_mine, ncclUint8, root, m->nccl, c->stream));
-      if (nt) CTX_NCCL(c, rccl()->Send(soup, (size_t) nt * tri, ncclUint8, root, m->nccl, c->stream));
-    }
-    CTX_NCCL(c, rccl()->GroupEnd());
-  }
-  uint64_t bytes_in = 0;
-  if (rank == root) {
-    if (nb && !self) HIP_TRY(c, hipMemcpyAsync(d_meta + boff[root] * 20, c->d_xsend, meta_mine, hipMemcpyDeviceToDevice, c->stream));
-    if (nt && !self) HIP_TRY(c, hipMemcpyAsync(d_tris + toff[root] * tri, soup, (size_t) nt * tri, hipMemcpyDeviceToDevice, c->stream));
-    bytes_in = (tot_b - nb) * 20 + (tot_t - nt) * tri;
-  }
+  const char* const from[2] = {c->d_xsend, (const char*) (c->soup_n ? c->d_soup : nullptr)};
+  char* const to[2] = {c->d_xrecv + plan.area[0], c->d_xrecv + plan.area[1]};  // root: rank r's metadata and triangles at seg[s][r]
+  if ((rc = issue_plan(c, plan, from, to))) return rc;  // issue
+  for (int s = 0; s < 2 && plan.own == kOwnCopied; s++)  // the root's own part without the self-loop
+    if (plan.own_sent[s].bytes) HIP_TRY(c, hipMemcpyAsync(to[s] + plan.seg[s][rank].off, from[s], plan.own_sent[s].bytes, hipMemcpyDeviceToDevice, c->stream));
   if ((rc = clk.mark())) return rc;
-  if (rank == root) {
-    std::vector<char> h_meta(meta_all ? meta_all : 1);
-    if (meta_all) HIP_TRY(c, hipMemcpyAsync(h_meta.data(), d_meta, meta_all, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::vector<mrh_block_desc> all_d((size_t) tot_b);
-    std::vector<uint32_t> all_c((size_t) tot_b);
-    for (int r = 0; r < world; r++) {
-      const uint64_t b = sizes[2 * r];
-      if (!b) continue;
-      memcpy(&all_d[boff[r]], h_meta.data() + boff[r] * 20, b * 16);
-      memcpy(&all_c[boff[r]], h_meta.data() + boff[r] * 20 + b * 16, b * 4);
-    }
-    // d_tris is not c->d_soup: the run merge writes the soup buffer while it reads this one
-    rc = mrh_process_triangle_runs(c, all_d.data(), all_c.data(), tot_b, (const mrh_triangle*) d_tris, tot_t, 1);
-    if (rc) return rc;
-    if (out_triangles) *out_triangles = tot_t;
-  }
+  if (rank == root && (rc = gather_consume(c, plan, to, out_triangles))) return rc;  // consume
   if ((rc = clk.mark())) return rc;
-  return clk.finish(rank == root ? 0 : meta_mine + nt * tri, bytes_in);
+  return clk.finish(plan.bytes_out, plan.bytes_in);  // phases
 }
 
 }  // extern "C"
