@@ -139,6 +139,25 @@ class MrhRaycastParams(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float), ("outputs", C.c_uint32)]
 
 
+# every symbol include/mrhash_track.h declares (the HIP library only: the oracle does not track)
+TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device").split()
+TRACK_OK, TRACK_LOST = 0, 1
+
+
+class MrhTrackParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float), ("dist_max", C.c_float),
+                ("iterations", C.c_int32), ("min_pixels", C.c_uint32)]
+
+
+class MrhTrackInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations_done", C.c_int32), ("pixels", C.c_uint64), ("rms", C.c_double), ("sums", C.c_int64 * 32)]
+
+    def as_dict(self) -> dict:
+        return dict(status=int(self.status), iterations_done=int(self.iterations_done), pixels=int(self.pixels), rms=float(self.rms),
+                    sums=np.array(self.sums[:], dtype=np.int64))
+
+
 # every symbol include/mrhash_normals.h declares (the HIP library only: the oracle is given its normals)
 NORMALS_SYMBOLS = ("mrh_estimate_normals_device mrh_estimate_normals mrh_get_normals").split()
 
@@ -252,6 +271,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_raycast_spherical.argtypes = lib.mrh_raycast.argtypes + [P(C.c_void_p)]
         lib.mrh_raycast_spherical_device.argtypes = lib.mrh_raycast_device.argtypes + [C.c_void_p]
         for name in RAYCAST_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_track_depth"):  # include/mrhash_track.h
+        lib.mrh_track_depth.argtypes = [C.c_void_p, P(MrhTrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                        P(MrhTrackInfo)]
+        lib.mrh_track_depth_device.argtypes = lib.mrh_track_depth.argtypes
+        for name in TRACK_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_estimate_normals"):  # include/mrhash_normals.h
         lib.mrh_estimate_normals_device.argtypes = [C.c_void_p, P(MrhNormalsParams), C.c_void_p, C.c_uint64, C.c_void_p]
@@ -762,6 +787,36 @@ class Engine:
         F = C.POINTER(C.c_float)
         self._check(self.lib.mrh_raycast_spherical_device(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), d_range or None,
                                                           d_normals or None, d_rgb or None, d_points or None))
+
+    # -- tracking (include/mrhash_track.h) ------------------------------------------------------------
+    def _track(self, fn, depth_ptr, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):
+        p = MrhTrackParams(fx, fy, cx, cy, int(rows), int(cols), min_depth, max_depth, step, dist_max, int(iterations), int(min_pixels))
+        R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        out_R, out_t, info = np.zeros(9, np.float32), np.zeros(3, np.float32), MrhTrackInfo()
+        F = C.POINTER(C.c_float)
+        self._check(fn(self._ctx, C.byref(p), depth_ptr, R.ctypes.data_as(F), t.ctypes.data_as(F), out_R.ctypes.data_as(F),
+                       out_t.ctypes.data_as(F), C.byref(info)))
+        return out_R.reshape(3, 3), out_t, info.as_dict()
+
+    def track_depth(self, depth, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, dist_max=0.0, iterations=0, min_pixels=0):
+        """Estimates the camera-to-world pose of the depth image (float32 [rows, cols], metres) by point-to-plane ICP against
+        one render of the map from the initial pose (R, t) (mrh_track_depth).  Blocks.  0 = the default of
+        step, dist_max, iterations (10) and min_pixels (64).  Returns (R float32 [3, 3], t float32 [3], info) with info =
+        {status (TRACK_OK / TRACK_LOST), iterations_done, pixels, rms, sums int64 [32]}; a lost track returns the pose from
+        before the step that failed."""
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if d.size != int(rows) * int(cols):
+            raise ValueError(f"track_depth: depth has {d.size} pixels, rows * cols = {int(rows) * int(cols)}")
+        return self._track(self.lib.mrh_track_depth, d.ctypes.data, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max,
+                           iterations, min_pixels)
+
+    def track_depth_device(self, ptr_depth: int, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, dist_max=0.0, iterations=0,
+                           min_pixels=0):
+        """mrh_track_depth_device: as track_depth with the image already on the device (integer pointer, e.g.
+        hipmem.DeviceBuffer.ptr, [rows * cols] float32).  Blocks too: the solve is on the host."""
+        return self._track(self.lib.mrh_track_depth_device, ptr_depth or None, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step,
+                           dist_max, iterations, min_pixels)
 
     # -- scan normals (include/mrhash_normals.h) ----------------------------------------------------
     def estimate_normals(self, radius=0.0, min_points=0, min_spread=0.0, max_flatness=0.0, info=False):

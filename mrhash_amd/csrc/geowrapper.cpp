@@ -591,6 +591,57 @@ GeoWrapper::RaycastScan GeoWrapper::raycastScanPose(const std::array<float, 16>&
   return out;
 }
 
+GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols) { return trackDepthPose(depth, rows, cols, pose_); }
+
+GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) {
+  return trackDepthPose(depth, rows, cols, pose_from(t, q));
+}
+
+namespace {
+// unit quaternion (qx, qy, qz, qw) of a rotation matrix (row-major), by the branch with the largest divisor, normalised; w >= 0.
+// The wrapper's own conversion: D14 ends at the matrix.
+std::array<float, 4> quat_from(const float R[9]) {
+  const double m00 = R[0], m01 = R[1], m02 = R[2], m10 = R[3], m11 = R[4], m12 = R[5], m20 = R[6], m21 = R[7], m22 = R[8];
+  double x, y, z, w;
+  const double tr = m00 + m11 + m22;
+  if (tr > 0.0) {
+    const double s = 2.0 * std::sqrt(tr + 1.0);
+    w = 0.25 * s; x = (m21 - m12) / s; y = (m02 - m20) / s; z = (m10 - m01) / s;
+  } else if (m00 > m11 && m00 > m22) {
+    const double s = 2.0 * std::sqrt(1.0 + m00 - m11 - m22);
+    w = (m21 - m12) / s; x = 0.25 * s; y = (m01 + m10) / s; z = (m02 + m20) / s;
+  } else if (m11 > m22) {
+    const double s = 2.0 * std::sqrt(1.0 + m11 - m00 - m22);
+    w = (m02 - m20) / s; x = (m01 + m10) / s; y = 0.25 * s; z = (m12 + m21) / s;
+  } else {
+    const double s = 2.0 * std::sqrt(1.0 + m22 - m00 - m11);
+    w = (m10 - m01) / s; x = (m02 + m20) / s; y = (m12 + m21) / s; z = 0.25 * s;
+  }
+  const double n = std::sqrt(x * x + y * y + z * z + w * w) * (w < 0.0 ? -1.0 : 1.0);
+  return {(float) (x / n), (float) (y / n), (float) (z / n), (float) (w / n)};
+}
+}  // namespace
+
+GeoWrapper::TrackResult GeoWrapper::trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose) {
+  if (!has_camera_) throw std::runtime_error("GeoWrapper::trackDepthImage | setCamera has not been called");
+  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::trackDepthImage | pinhole cameras only (the camera is spherical)");
+  if (!depth || rows != (size_t) camera_rows_ || cols != (size_t) camera_cols_)
+    throw std::runtime_error("GeoWrapper::trackDepthImage | the depth image must have the camera's rows x cols");
+  mrh_track_params p;
+  std::memset(&p, 0, sizeof p);  // step, dist_max, iterations, min_pixels: the defaults
+  p.fx = camera_fx_; p.fy = camera_fy_; p.cx = camera_cx_; p.cy = camera_cy_;
+  p.rows = camera_rows_; p.cols = camera_cols_;
+  p.min_depth = camera_min_depth_; p.max_depth = max_depth_;
+  const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
+  const float t[3] = {pose[3], pose[7], pose[11]};
+  float out_R[9], out_t[3];
+  TrackResult out;
+  check(mrh_track_depth(ctx_, &p, depth, R, t, out_R, out_t, &out.info), "trackDepthImage");
+  out.t = {out_t[0], out_t[1], out_t[2]};
+  out.q = quat_from(out_R);
+  return out;
+}
+
 void GeoWrapper::clearBuffers() {
   std::cout << "clearing buffers..." << std::endl;
   cacheMesh();  // the mesh of the last extractMesh outlives the map, as the reference's host matrices do

@@ -13,6 +13,7 @@
 #include "mrhash_hip.h"
 #include "mrhash_comm.h"
 #include "mrhash_raycast.h"
+#include "mrhash_track.h"
 #include "mrhash_normals.h"
 
 namespace pygeowrapper {
@@ -117,6 +118,19 @@ public:
   RaycastScan raycastScan();
   RaycastScan raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q);
 
+  // ---- tracking (include/mrhash_track.h; no reference counterpart): the pose of a depth image (rows x cols as
+  // the camera of the last setCamera, metres) by point-to-plane ICP against the map, started from the current pose (setCurrPose)
+  // or from (t, q).  Every parameter of mrh_track_params at its default.  Returns the pose as setCurrPose takes it; pose_ is left
+  // alone — the SLAM loop is trackDepthImage -> setCurrPose -> setDepthImage -> compute.  info.status == MRH_TRACK_LOST: (t, q) is
+  // the pose from before the step that failed.  A spherical camera throws std::runtime_error.
+  struct TrackResult {
+    std::array<float, 3> t;
+    std::array<float, 4> q;  // qx, qy, qz, qw
+    mrh_track_info info;
+  };
+  TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols);
+  TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q);
+
   // ---- multi-GPU (include/mrhash_comm.h; no reference counterpart): one GeoWrapper per process / GPU.
   // commUniqueId() on one rank, the 128 bytes handed to the others by the launcher, then commInit on every rank.
   //   tile_sharded = true : the result-identical mode — every rank is given every frame, compute() fuses the tiles this rank
@@ -155,6 +169,7 @@ private:
   float max_depth_ = 0.f;
   RaycastImages raycastPose(const std::array<float, 16>& pose);
   RaycastScan raycastScanPose(const std::array<float, 16>& pose);
+  TrackResult trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose);
   mrh_raycast_params raycastParams(uint32_t outputs) const;  // the camera of the last setCamera, step = half the truncation
   bool has_camera_ = false;  // the camera of the last setCamera, for raycast()
   int camera_model_ = MRH_CAMERA_PINHOLE, camera_rows_ = 0, camera_cols_ = 0;

@@ -1,7 +1,7 @@
 // mrh_capi.hip — implementation of the C ABI (include/mrhash_hip.h) on top of the gfx950 kernels.
 //
 // Host side of the thin HIP layer: enqueues the per-frame kernel chain with no host round trip, and only synchronises in the
-// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the splat, raycast and normals glue.
+// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the splat, raycast, tracking and normals glue.
 // The context and its lifetime: mrh_context.h; the copy pool: mrh_hostcopy.h; uploads, frame marks, peeks: mrh_upload.h; the
 // host side of a depth frame: mrh_frame.h; extraction, scans, block I/O, RCCL: mrh_extract.h, mrh_points.h, mrh_blocks.h,
 // mrh_comm.h.  One translation unit.
@@ -26,10 +26,12 @@
 #include "../../include/mrhash_hip.h"
 #include "../../include/mrhash_comm.h"
 #include "../../include/mrhash_raycast.h"
+#include "../../include/mrhash_track.h"
 #include "../../include/mrhash_normals.h"
 #include "mrh_kernels.h"
 #include "mrh_mc.h"
 #include "mrh_raycast.h"
+#include "mrh_track.h"
 #include "mrh_normals.h"
 #include "mrh_fast.h"
 #include "mrh_pipe.h"
@@ -773,6 +775,101 @@ int mrh_raycast_spherical(mrh_ctx* c, const mrh_raycast_params* p, const float R
 int mrh_raycast_spherical_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_range,
                                  float* d_normals, uint8_t* d_rgb, float* d_points) {
   return raycast_device(c, "mrh_raycast_spherical_device", MRH_CAMERA_SPHERICAL, p, R_row_major, t, RayOut{d_range, d_normals, d_rgb, d_points});
+}
+
+}  // extern "C"
+
+// ---- depth-frame tracking (include/mrhash_track.h, mrh_track.h, mrh_tracksolve.h) ---------------------------------------------
+namespace {
+
+// mrh_track_depth / mrh_track_depth_device: one render of the model through the raycast's own argument check and launch, then per
+// iteration k_track_linearise, k_track_finish, the 256-byte read-back from pinned memory, and solve + update on the host (blocks)
+int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const float* depth_host, const float* depth_dev, const float* R0, const float* t0,
+              float* out_R, float* out_t, mrh_track_info* out_info) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  if (!p || !(depth_host || depth_dev) || !out_R || !out_t) return fail(c, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  const mrh_raycast_params rp = {p->fx, p->fy, p->cx, p->cy, p->rows, p->cols, p->min_depth, p->max_depth, p->step, MRH_RAYCAST_NORMALS};
+  RayCam rc;
+  int rc_ = raycast_args(c, who, MRH_CAMERA_PINHOLE, &rp, R0, t0, &rc);
+  if (rc_) return rc_;
+  const float dist_max = p->dist_max == 0.f ? std::fmin(2.f * c->p.sdf_truncation, 1.f) : p->dist_max;
+  if (!(dist_max > 0.f && dist_max <= 1.f)) return fail(c, MRH_ERR_INVALID_ARG, "%s: the gate must lie in (0, 1] m (dist_max %g)", who, (double) dist_max);
+  if (p->iterations < 0 || p->iterations > MRH_TRACK_MAX_ITERATIONS)
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: %d iterations (1 .. %d, 0 = 10)", who, p->iterations, MRH_TRACK_MAX_ITERATIONS);
+  const int iterations = p->iterations ? p->iterations : 10;
+  const uint32_t min_pixels = p->min_pixels ? p->min_pixels : 64u;
+  rc_ = ensure_ready(c, who);
+  if (rc_) return rc_;
+  // the previous call blocked: nothing reads the old buffers
+  const size_t npix = (size_t) rc.rows * (size_t) rc.cols;
+  const dim3 grid((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
+  const size_t n_rows = (size_t) grid.x * grid.y;
+  if ((rc_ = regrow(c, c->trk.d_img, c->trk.cap, npix, npix * 5 * sizeof(float), false))) return rc_;
+  if ((rc_ = regrow(c, c->trk.d_slab, c->trk.slab_cap, n_rows, n_rows * mrh_track::kSumWords * sizeof(i64), false))) return rc_;
+  if (!c->trk.h_sums) HIP_TRY(c, pinned_alloc(c, c->trk.h_sums, mrh_track::kSumWords * sizeof(i64)));
+  float* d_md = (float*) c->trk.d_img;
+  float* d_mn = d_md + npix;
+  const float* d_depth = depth_dev;
+  if (!d_depth) {
+    if ((rc_ = regrow_pinned(c, c->trk.h_depth, c->trk.h_cap, npix, npix * sizeof(float)))) return rc_;
+    memcpy(c->trk.h_depth, depth_host, npix * sizeof(float));
+    HIP_TRY(c, hipMemcpyAsync(d_md + 4 * npix, c->trk.h_depth, npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    d_depth = d_md + 4 * npix;
+  }
+  launch_raycast(c, MRH_CAMERA_PINHOLE, rc, RayOut{d_md, d_mn, nullptr, nullptr});
+  HIP_TRY(c, hipGetLastError());
+
+  TrackLin k;
+  k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.ifx = rc.ifx; k.ify = rc.ify;
+  k.rows = rc.rows; k.cols = rc.cols;
+  k.min_depth = rc.min_depth; k.max_depth = rc.max_depth;
+  k.dmax2 = dist_max * dist_max;
+  k.s_a = mrh_track::angle_scale(rc.max_depth);
+  double R[9], t[3];
+  for (int i = 0; i < 9; i++) { k.Rr[i] = R0[i]; R[i] = (double) R0[i]; }
+  for (int i = 0; i < 3; i++) { k.tr[i] = t0[i]; t[i] = (double) t0[i]; }
+  int64_t sums[mrh_track::kSumWords] = {};
+  int status = MRH_TRACK_OK, done = 0;
+  for (int it = 0; it < iterations; it++) {
+    for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
+    for (int i = 0; i < 3; i++) k.t[i] = (float) t[i];
+    k_track_linearise<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(k, d_depth, d_md, d_mn, c->trk.d_slab);
+    k_track_finish<<<1, 1024, 0, c->stream>>>(c->trk.d_slab, (int) n_rows, c->trk.h_sums);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
+    for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) c->trk.h_sums)[i];
+    double xi[6];
+    if (!mrh_track::solve(sums, k.s_a, min_pixels, xi)) {
+      status = MRH_TRACK_LOST;
+      break;
+    }
+    mrh_track::update(R, t, xi);
+    done++;
+  }
+  for (int i = 0; i < 9; i++) out_R[i] = (float) R[i];
+  for (int i = 0; i < 3; i++) out_t[i] = (float) t[i];
+  if (out_info) {
+    out_info->status = status;
+    out_info->iterations_done = done;
+    out_info->pixels = (uint64_t) sums[mrh_track::kSumN];
+    out_info->rms = mrh_track::rms(sums);
+    for (int i = 0; i < mrh_track::kSumWords; i++) out_info->sums[i] = sums[i];
+  }
+  return MRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrh_track_depth(mrh_ctx* c, const mrh_track_params* p, const float* depth_host, const float R_init[9], const float t_init[3], float out_R[9],
+                    float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_depth", p, depth_host, nullptr, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_depth_device(mrh_ctx* c, const mrh_track_params* p, const float* d_depth, const float R_init[9], const float t_init[3], float out_R[9],
+                           float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_depth_device", p, nullptr, d_depth, R_init, t_init, out_R, out_t, out_info);
 }
 
 }  // extern "C"

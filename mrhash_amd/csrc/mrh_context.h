@@ -422,6 +422,14 @@ struct mrh_ctx {
   // 3 x f32 | points 3 x f32 | rgb 3 x u8] per pixel and the pinned host copy the caller reads
   char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
   char* h_ray = nullptr; size_t h_ray_cap = 0;
+  // depth-frame tracking (mrh_track.h), grow-only — device [model depth f32 | model normals 3 x f32 | the caller's depth f32] per
+  // pixel and the partial slab (one row of 32 words per workgroup); pinned: the staged depth image and the 32 sums the host reads
+  struct Track {
+    char* d_img = nullptr; size_t cap = 0;           // pixels
+    long long* d_slab = nullptr; size_t slab_cap = 0;  // rows
+    float* h_depth = nullptr; size_t h_cap = 0;      // pixels
+    long long* h_sums = nullptr;
+  } trk;
   // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of
   // every point, grow-only; two sets of counters, a scan's last launch zeroes the next one's
   struct Normals {

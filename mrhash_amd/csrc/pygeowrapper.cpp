@@ -195,6 +195,35 @@ PYBIND11_MODULE(pygeowrapper, m) {
       std::memcpy(points.mutable_data(), im.points.data(), im.points.size() * sizeof(float));
       return py::make_tuple(range, normals, colors, points);
     }, py::arg("t") = py::none(), py::arg("q") = py::none())
+    // not part of the reference binding: the pose of a depth image (2-D, the camera's rows x cols, metres) by ICP against the map,
+    // started from the current pose or from (t, q); returns (t [3], q [4] = qx,qy,qz,qw, info dict) and leaves the current pose
+    // alone — call setCurrPose(t, q) with the result before setDepthImage / compute
+    .def("trackDepthImage", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> depth,
+                               std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                               std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> q) {
+      if (depth.ndim() != 2) throw std::runtime_error("GeoWrapper::trackDepthImage|input should be a 2D numpy array");
+      if (t.has_value() != q.has_value()) throw std::runtime_error("GeoWrapper::trackDepthImage|give both t and q, or neither");
+      GeoWrapper::TrackResult r;
+      if (t) {
+        if (t->size() != 3 || q->size() != 4) throw std::runtime_error("GeoWrapper::trackDepthImage|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+        r = g.trackDepthImage(depth.data(), (size_t) depth.shape(0), (size_t) depth.shape(1), {t->data()[0], t->data()[1], t->data()[2]},
+                              {q->data()[0], q->data()[1], q->data()[2], q->data()[3]});
+      } else {
+        r = g.trackDepthImage(depth.data(), (size_t) depth.shape(0), (size_t) depth.shape(1));
+      }
+      py::array_t<float> ot(3), oq(4);
+      std::memcpy(ot.mutable_data(), r.t.data(), 3 * sizeof(float));
+      std::memcpy(oq.mutable_data(), r.q.data(), 4 * sizeof(float));
+      py::array_t<int64_t> sums(32);
+      std::memcpy(sums.mutable_data(), r.info.sums, sizeof r.info.sums);
+      py::dict info;
+      info["status"] = r.info.status;
+      info["iterations_done"] = r.info.iterations_done;
+      info["pixels"] = r.info.pixels;
+      info["rms"] = r.info.rms;
+      info["sums"] = sums;
+      return py::make_tuple(ot, oq, info);
+    }, py::arg("depth"), py::arg("t") = py::none(), py::arg("q") = py::none())
     .def("clearBuffers", &GeoWrapper::clearBuffers)
     .def("serializeData", &GeoWrapper::serializeData, py::arg("filename_hash") = "./data/hash_points.ply",
          py::arg("filename_voxel") = "./data/voxel_points.ply")
