@@ -1,6 +1,6 @@
 /*
- * mrhash_track.h — the pose of a pinhole depth frame from the fused map: point-to-plane ICP against one raycast of the map
- * (libmrhash_hip.so; kernels in mrhash_amd/csrc/mrh_track.h, solve in mrhash_amd/csrc/mrh_tracksolve.h).  The reference has no
+ * mrhash_track.h — the pose of a pinhole depth frame or of a LiDAR scan from the fused map: point-to-plane ICP against one raycast
+ * of the map (libmrhash_hip.so; kernels in mrhash_amd/csrc/mrh_track.h, solve in mrhash_amd/csrc/mrh_tracksolve.h).  The reference has no
  * tracker; DESIGN.md D14 is the normative statement and tests/track_ref.py restates it in numpy.  Every sum is an exact
  * integer and the solve is a fixed sequence of IEEE operations, so the result is reproducible bit for bit.
  *
@@ -30,13 +30,27 @@
  * Loop     `iterations` times linearise, solve, update; no early exit on a small step.  A lost step ends the loop with the pose
  *          from before that step: status MRH_TRACK_LOST, and the call still returns MRH_OK.
  *
+ * Scans    (mrh_track_scan; DESIGN.md D15 is normative, tests/track_scan_ref.py restates it) n sensor-frame points p_s against one
+ *          mrh_raycast_spherical render (D13) from (R_r, t_r): range M_rho, world-frame normals M_n, sensor-frame points M_p.
+ *          Everything above holds except steps 1-5, which read per point:
+ *   1  rho_p = sqrtf((x^2 + y^2) + z^2); accept only rho_p > min_depth && rho_p <= max_depth ((0, 0, 0), a NaN, an infinity fail)
+ *   2  a = R32 p_s; p_w = a + t32
+ *   3  q = R_r^T (p_w - t_r); rho_q = sqrtf((q.x^2 + q.y^2) + q.z^2); accept only rho_q > min_depth && rho_q <= max_depth
+ *   4  az = mrh_atan2f(q.y, q.x), el = mrh_asinf(q.z / rho_q) (mrh_softmath.h); u = (fx * az + cx) + 1, v = (fy * el + cy) + 1;
+ *      the same bounds test and floor; no azimuth wrap
+ *   5  reject if M_rho[r', c'] == 0 or if N = M_n[r', c'] is the zero vector (a hit without a gradient gives no row and does not
+ *      count); V = t_r + R_r M_p[r', c'] (the product in the row shape, then added to t_r)
+ *          mrh_track_info.pixels and min_pixels count points.  A map that is to be tracked against needs a truncation that
+ *          renders the ground: without it height is unobservable and the pivot gate reports MRH_TRACK_LOST.
+ *
  * Conventions as in mrhash_hip.h.  The tracker is a reader of the map with exactly the raycast's contract (mrhash_raycast.h):
  * a frame that mrh_integrate kept back runs first and the frame pipeline restarts; camera, pose, images, counters, mrh_stats
- * and the last extraction stay as they were; the depth image comes with the call and the frame path's uploaded image is
- * neither read nor replaced.  Its device and pinned buffers grow on demand and are released by mrh_destroy.
+ * and the last extraction stay as they were; the depth image or the cloud comes with the call, and the frame path's uploaded image, the
+ * current scan (mrh_upload_points / mrh_set_points_device), its normals and its layout are neither read nor replaced.  Its device
+ * and pinned buffers grow on demand and are released by mrh_destroy.
  *
  * Errors: MRH_ERR_INVALID_ARG for a null argument, a bad parameter (the raycast's rules, dist_max outside (0, 1], more than 64
- * iterations); MRH_ERR_STATE while an exchange is pending; MRH_ERR_UNSUPPORTED on a sharded context (shard_count > 1).
+ * iterations, more than 2^24 points); MRH_ERR_STATE while an exchange is pending; MRH_ERR_UNSUPPORTED on a sharded context (shard_count > 1).
  */
 #ifndef MRHASH_TRACK_H
 #define MRHASH_TRACK_H
@@ -52,7 +66,7 @@ extern "C" {
 #define MRH_TRACK_MAX_ITERATIONS 64
 
 typedef struct mrh_track_params {
-  float    fx, fy, cx, cy;          /* pinhole intrinsics of the depth image and of the model render       */
+  float    fx, fy, cx, cy;          /* intrinsics of the model render (and of the depth image); scans: spherical */
   int32_t  rows, cols;              /* 1 .. MRH_RAYCAST_MAX_SIDE each                                     */
   float    min_depth, max_depth;    /* 0 < min_depth < max_depth (metres, camera z)                        */
   float    step;                    /* sample spacing of the model render; 0 = 0.5 * sdf_truncation        */
@@ -79,6 +93,19 @@ int mrh_track_depth(mrh_ctx* ctx, const mrh_track_params* p, const float* depth_
  * returns).  Blocks too: the solve is on the host. */
 int mrh_track_depth_device(mrh_ctx* ctx, const mrh_track_params* p, const float* d_depth, const float R_init[9], const float t_init[3],
                            float out_R[9], float out_t[3], mrh_track_info* out_info);
+
+/* Estimates the sensor-to-world pose of a LiDAR scan: n points (host, [n * 3] f32, metres, sensor frame, organised or not;
+ * a missing return is (0, 0, 0)) against one spherical render of the map (see "Scans" above).  p->fx .. p->cols are the
+ * spherical intrinsics of that render as mrh_raycast_spherical takes them, min_depth / max_depth are ranges, min_pixels counts
+ * points.  n <= 2^24; n = 0 returns MRH_OK with status MRH_TRACK_LOST and the pose as given.  The cloud is copied through
+ * pinned staging.  Blocks. */
+int mrh_track_scan(mrh_ctx* ctx, const mrh_track_params* p, const float* points_host, size_t n, const float R_init[9], const float t_init[3],
+                   float out_R[9], float out_t[3], mrh_track_info* out_info);
+
+/* The same with the cloud already on the device ([n * 3] f32 on the context's device, e.g. the points image of
+ * mrh_raycast_spherical_device; it must stay valid until the call returns).  Blocks too. */
+int mrh_track_scan_device(mrh_ctx* ctx, const mrh_track_params* p, const float* d_points, size_t n, const float R_init[9], const float t_init[3],
+                          float out_R[9], float out_t[3], mrh_track_info* out_info);
 
 #ifdef __cplusplus
 }

@@ -140,7 +140,7 @@ class MrhRaycastParams(C.Structure):
 
 
 # every symbol include/mrhash_track.h declares (the HIP library only: the oracle does not track)
-TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device").split()
+TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device mrh_track_scan mrh_track_scan_device").split()
 TRACK_OK, TRACK_LOST = 0, 1
 
 
@@ -276,7 +276,12 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_track_depth.argtypes = [C.c_void_p, P(MrhTrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                         P(MrhTrackInfo)]
         lib.mrh_track_depth_device.argtypes = lib.mrh_track_depth.argtypes
-        for name in TRACK_SYMBOLS:
+        names = TRACK_SYMBOLS[:2]
+        if hasattr(lib, "mrh_track_scan"):  # an A/B build from before scan tracking has the depth pair only (tools/bench_with_lib.py)
+            lib.mrh_track_scan.argtypes = lib.mrh_track_depth.argtypes[:3] + [C.c_size_t] + lib.mrh_track_depth.argtypes[3:]
+            lib.mrh_track_scan_device.argtypes = lib.mrh_track_scan.argtypes
+            names = TRACK_SYMBOLS
+        for name in names:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_estimate_normals"):  # include/mrhash_normals.h
         lib.mrh_estimate_normals_device.argtypes = [C.c_void_p, P(MrhNormalsParams), C.c_void_p, C.c_uint64, C.c_void_p]
@@ -789,13 +794,14 @@ class Engine:
                                                           d_normals or None, d_rgb or None, d_points or None))
 
     # -- tracking (include/mrhash_track.h) ------------------------------------------------------------
-    def _track(self, fn, depth_ptr, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):
+    def _track(self, fn, obs, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):
+        """obs: the arguments between the parameter block and the pose — (depth pointer,) or (points pointer, n)."""
         p = MrhTrackParams(fx, fy, cx, cy, int(rows), int(cols), min_depth, max_depth, step, dist_max, int(iterations), int(min_pixels))
         R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
         t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
         out_R, out_t, info = np.zeros(9, np.float32), np.zeros(3, np.float32), MrhTrackInfo()
         F = C.POINTER(C.c_float)
-        self._check(fn(self._ctx, C.byref(p), depth_ptr, R.ctypes.data_as(F), t.ctypes.data_as(F), out_R.ctypes.data_as(F),
+        self._check(fn(self._ctx, C.byref(p), *obs, R.ctypes.data_as(F), t.ctypes.data_as(F), out_R.ctypes.data_as(F),
                        out_t.ctypes.data_as(F), C.byref(info)))
         return out_R.reshape(3, 3), out_t, info.as_dict()
 
@@ -808,15 +814,31 @@ class Engine:
         d = np.ascontiguousarray(depth, dtype=np.float32)
         if d.size != int(rows) * int(cols):
             raise ValueError(f"track_depth: depth has {d.size} pixels, rows * cols = {int(rows) * int(cols)}")
-        return self._track(self.lib.mrh_track_depth, d.ctypes.data, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max,
+        return self._track(self.lib.mrh_track_depth, (d.ctypes.data,), fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max,
                            iterations, min_pixels)
 
     def track_depth_device(self, ptr_depth: int, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, dist_max=0.0, iterations=0,
                            min_pixels=0):
         """mrh_track_depth_device: as track_depth with the image already on the device (integer pointer, e.g.
         hipmem.DeviceBuffer.ptr, [rows * cols] float32).  Blocks too: the solve is on the host."""
-        return self._track(self.lib.mrh_track_depth_device, ptr_depth or None, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step,
+        return self._track(self.lib.mrh_track_depth_device, (ptr_depth or None,), fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step,
                            dist_max, iterations, min_pixels)
+
+    def track_scan(self, points, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, dist_max=0.0, iterations=0, min_points=0):
+        """Estimates the sensor-to-world pose of a scan (float32 [n, 3], sensor frame, organised or not; (0, 0, 0) = no return) by
+        point-to-plane ICP against one spherical render of the map from the initial pose (R, t) (mrh_track_scan).
+        fx .. cols are the spherical intrinsics of that render as raycast_spherical takes them, min_depth / max_depth ranges.
+        Blocks.  Returns what track_depth returns; info["pixels"] counts points."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        return self._track(self.lib.mrh_track_scan, (pts.ctypes.data, len(pts)), fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step,
+                           dist_max, iterations, min_points)
+
+    def track_scan_device(self, ptr_points: int, n: int, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, dist_max=0.0,
+                          iterations=0, min_points=0):
+        """mrh_track_scan_device: as track_scan with the cloud already on the device (integer pointer, [n, 3] float32), e.g. the
+        points image of raycast_spherical_device after sync().  Blocks too."""
+        return self._track(self.lib.mrh_track_scan_device, (ptr_points or None, int(n)), fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth,
+                           step, dist_max, iterations, min_points)
 
     # -- scan normals (include/mrhash_normals.h) ----------------------------------------------------
     def estimate_normals(self, radius=0.0, min_points=0, min_spread=0.0, max_flatness=0.0, info=False):

@@ -622,11 +622,8 @@ std::array<float, 4> quat_from(const float R[9]) {
 }
 }  // namespace
 
-GeoWrapper::TrackResult GeoWrapper::trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose) {
-  if (!has_camera_) throw std::runtime_error("GeoWrapper::trackDepthImage | setCamera has not been called");
-  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::trackDepthImage | pinhole cameras only (the camera is spherical)");
-  if (!depth || rows != (size_t) camera_rows_ || cols != (size_t) camera_cols_)
-    throw std::runtime_error("GeoWrapper::trackDepthImage | the depth image must have the camera's rows x cols");
+// depth != nullptr: a depth image of the pinhole camera (D14); else the cloud pts [n * 3] against the spherical camera's render (D15)
+GeoWrapper::TrackResult GeoWrapper::trackPose(const char* who, const float* depth, const float* pts, size_t n, const std::array<float, 16>& pose) {
   mrh_track_params p;
   std::memset(&p, 0, sizeof p);  // step, dist_max, iterations, min_pixels: the defaults
   p.fx = camera_fx_; p.fy = camera_fy_; p.cx = camera_cx_; p.cy = camera_cy_;
@@ -636,10 +633,31 @@ GeoWrapper::TrackResult GeoWrapper::trackDepthPose(const float* depth, size_t ro
   const float t[3] = {pose[3], pose[7], pose[11]};
   float out_R[9], out_t[3];
   TrackResult out;
-  check(mrh_track_depth(ctx_, &p, depth, R, t, out_R, out_t, &out.info), "trackDepthImage");
+  check(depth ? mrh_track_depth(ctx_, &p, depth, R, t, out_R, out_t, &out.info) : mrh_track_scan(ctx_, &p, pts, n, R, t, out_R, out_t, &out.info), who);
   out.t = {out_t[0], out_t[1], out_t[2]};
   out.q = quat_from(out_R);
   return out;
+}
+
+GeoWrapper::TrackResult GeoWrapper::trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose) {
+  if (!has_camera_) throw std::runtime_error("GeoWrapper::trackDepthImage | setCamera has not been called");
+  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::trackDepthImage | pinhole cameras only (the camera is spherical)");
+  if (!depth || rows != (size_t) camera_rows_ || cols != (size_t) camera_cols_)
+    throw std::runtime_error("GeoWrapper::trackDepthImage | the depth image must have the camera's rows x cols");
+  return trackPose("trackDepthImage", depth, nullptr, 0, pose);
+}
+
+GeoWrapper::TrackResult GeoWrapper::trackPointCloud(const float* pts, size_t n) { return trackCloudPose(pts, n, pose_); }
+
+GeoWrapper::TrackResult GeoWrapper::trackPointCloud(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q) {
+  return trackCloudPose(pts, n, pose_from(t, q));
+}
+
+GeoWrapper::TrackResult GeoWrapper::trackCloudPose(const float* pts, size_t n, const std::array<float, 16>& pose) {
+  if (!has_camera_) throw std::runtime_error("GeoWrapper::trackPointCloud | setCamera has not been called");
+  if (camera_model_ != MRH_CAMERA_SPHERICAL) throw std::runtime_error("GeoWrapper::trackPointCloud | spherical cameras only (the camera is a pinhole)");
+  if (!pts && n) throw std::runtime_error("GeoWrapper::trackPointCloud | no points");
+  return trackPose("trackPointCloud", nullptr, pts, n, pose);
 }
 
 void GeoWrapper::clearBuffers() {

@@ -130,6 +130,12 @@ public:
   };
   TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols);
   TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q);
+  // The same for a LiDAR scan: n sensor-frame points [n * 3], organised or not, (0, 0, 0) = no return, against one
+  // spherical render of the map with the camera of the last setCamera(..., model = 1).  The loop is trackPointCloud -> setCurrPose
+  // -> setPointCloud -> compute; the cloud given to setPointCloud is neither read nor replaced.  A pinhole camera throws
+  // std::runtime_error.  The map must render the ground for the height to be observable: a truncation of 4 voxels does (D15).
+  TrackResult trackPointCloud(const float* pts, size_t n);
+  TrackResult trackPointCloud(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q);
 
   // ---- multi-GPU (include/mrhash_comm.h; no reference counterpart): one GeoWrapper per process / GPU.
   // commUniqueId() on one rank, the 128 bytes handed to the others by the launcher, then commInit on every rank.
@@ -170,6 +176,8 @@ private:
   RaycastImages raycastPose(const std::array<float, 16>& pose);
   RaycastScan raycastScanPose(const std::array<float, 16>& pose);
   TrackResult trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose);
+  TrackResult trackCloudPose(const float* pts, size_t n, const std::array<float, 16>& pose);
+  TrackResult trackPose(const char* who, const float* depth, const float* pts, size_t n, const std::array<float, 16>& pose);
   mrh_raycast_params raycastParams(uint32_t outputs) const;  // the camera of the last setCamera, step = half the truncation
   bool has_camera_ = false;  // the camera of the last setCamera, for raycast()
   int camera_model_ = MRH_CAMERA_PINHOLE, camera_rows_ = 0, camera_cols_ = 0;

@@ -779,18 +779,30 @@ int mrh_raycast_spherical_device(mrh_ctx* c, const mrh_raycast_params* p, const 
 
 }  // extern "C"
 
-// ---- depth-frame tracking (include/mrhash_track.h, mrh_track.h, mrh_tracksolve.h) ---------------------------------------------
+// ---- tracking (include/mrhash_track.h, mrh_track.h, mrh_tracksolve.h) ---------------------------------------------------------
 namespace {
 
-// mrh_track_depth / mrh_track_depth_device: one render of the model through the raycast's own argument check and launch, then per
-// iteration k_track_linearise, k_track_finish, the 256-byte read-back from pinned memory, and solve + update on the host (blocks)
-int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const float* depth_host, const float* depth_dev, const float* R0, const float* t0,
-              float* out_R, float* out_t, mrh_track_info* out_info) {
+// what is tracked: a pinhole depth image of the model's rows x cols (D14) or a cloud of n sensor-frame points against the
+// spherical render (D15); on the host (staged through pinned memory) or on the device
+struct TrackObs {
+  int model;  // MRH_CAMERA_*: the camera model of the model render, and with it the linearisation
+  const float* host; const float* dev;
+  size_t n;   // points (spherical); a depth image has rows * cols pixels
+};
+
+// mrh_track_depth / mrh_track_scan and their device variants: one render of the model through the raycast's own argument check and
+// launch, then per iteration the linearisation kernel, k_track_finish, the 256-byte read-back from pinned memory, and solve +
+// update on the host (blocks)
+int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const TrackObs& obs, const float* R0, const float* t0, float* out_R, float* out_t,
+              mrh_track_info* out_info) {
   if (!c) return MRH_ERR_INVALID_ARG;
-  if (!p || !(depth_host || depth_dev) || !out_R || !out_t) return fail(c, MRH_ERR_INVALID_ARG, "%s: null argument", who);
-  const mrh_raycast_params rp = {p->fx, p->fy, p->cx, p->cy, p->rows, p->cols, p->min_depth, p->max_depth, p->step, MRH_RAYCAST_NORMALS};
+  const bool scan = obs.model == MRH_CAMERA_SPHERICAL;
+  if (!p || (!(obs.host || obs.dev) && !(scan && obs.n == 0)) || !out_R || !out_t) return fail(c, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (scan && obs.n > ((size_t) 1 << 24)) return fail(c, MRH_ERR_INVALID_ARG, "%s: %zu points in one scan (limit 2^24)", who, obs.n);
+  const mrh_raycast_params rp = {p->fx, p->fy, p->cx, p->cy, p->rows, p->cols, p->min_depth, p->max_depth, p->step,
+                                 MRH_RAYCAST_NORMALS | (scan ? MRH_RAYCAST_POINTS : 0u)};
   RayCam rc;
-  int rc_ = raycast_args(c, who, MRH_CAMERA_PINHOLE, &rp, R0, t0, &rc);
+  int rc_ = raycast_args(c, who, obs.model, &rp, R0, t0, &rc);
   if (rc_) return rc_;
   const float dist_max = p->dist_max == 0.f ? std::fmin(2.f * c->p.sdf_truncation, 1.f) : p->dist_max;
   if (!(dist_max > 0.f && dist_max <= 1.f)) return fail(c, MRH_ERR_INVALID_ARG, "%s: the gate must lie in (0, 1] m (dist_max %g)", who, (double) dist_max);
@@ -802,49 +814,65 @@ int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const floa
   if (rc_) return rc_;
   // the previous call blocked: nothing reads the old buffers
   const size_t npix = (size_t) rc.rows * (size_t) rc.cols;
-  const dim3 grid((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
+  const size_t n_obs = scan ? obs.n : npix;  // lanes of a linearisation
+  const dim3 grid = scan ? dim3((unsigned) ((n_obs + 255) / 256))
+                         : dim3((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
   const size_t n_rows = (size_t) grid.x * grid.y;
-  if ((rc_ = regrow(c, c->trk.d_img, c->trk.cap, npix, npix * 5 * sizeof(float), false))) return rc_;
-  if ((rc_ = regrow(c, c->trk.d_slab, c->trk.slab_cap, n_rows, n_rows * mrh_track::kSumWords * sizeof(i64), false))) return rc_;
-  if (!c->trk.h_sums) HIP_TRY(c, pinned_alloc(c, c->trk.h_sums, mrh_track::kSumWords * sizeof(i64)));
-  float* d_md = (float*) c->trk.d_img;
-  float* d_mn = d_md + npix;
-  const float* d_depth = depth_dev;
-  if (!d_depth) {
-    if ((rc_ = regrow_pinned(c, c->trk.h_depth, c->trk.h_cap, npix, npix * sizeof(float)))) return rc_;
-    memcpy(c->trk.h_depth, depth_host, npix * sizeof(float));
-    HIP_TRY(c, hipMemcpyAsync(d_md + 4 * npix, c->trk.h_depth, npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    d_depth = d_md + 4 * npix;
-  }
-  launch_raycast(c, MRH_CAMERA_PINHOLE, rc, RayOut{d_md, d_mn, nullptr, nullptr});
-  HIP_TRY(c, hipGetLastError());
-
-  TrackLin k;
-  k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.ifx = rc.ifx; k.ify = rc.ify;
-  k.rows = rc.rows; k.cols = rc.cols;
-  k.min_depth = rc.min_depth; k.max_depth = rc.max_depth;
-  k.dmax2 = dist_max * dist_max;
-  k.s_a = mrh_track::angle_scale(rc.max_depth);
   double R[9], t[3];
-  for (int i = 0; i < 9; i++) { k.Rr[i] = R0[i]; R[i] = (double) R0[i]; }
-  for (int i = 0; i < 3; i++) { k.tr[i] = t0[i]; t[i] = (double) t0[i]; }
+  for (int i = 0; i < 9; i++) R[i] = (double) R0[i];
+  for (int i = 0; i < 3; i++) t[i] = (double) t0[i];
   int64_t sums[mrh_track::kSumWords] = {};
   int status = MRH_TRACK_OK, done = 0;
-  for (int it = 0; it < iterations; it++) {
-    for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
-    for (int i = 0; i < 3; i++) k.t[i] = (float) t[i];
-    k_track_linearise<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(k, d_depth, d_md, d_mn, c->trk.d_slab);
-    k_track_finish<<<1, 1024, 0, c->stream>>>(c->trk.d_slab, (int) n_rows, c->trk.h_sums);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
-    for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) c->trk.h_sums)[i];
-    double xi[6];
-    if (!mrh_track::solve(sums, k.s_a, min_pixels, xi)) {
-      status = MRH_TRACK_LOST;
-      break;
+  if (n_obs == 0) status = MRH_TRACK_LOST;  // an empty scan: nothing is rendered or launched
+  else {
+    if ((rc_ = regrow(c, c->trk.d_img, c->trk.cap, npix, npix * 5 * sizeof(float), false))) return rc_;
+    if ((rc_ = regrow(c, c->trk.d_slab, c->trk.slab_cap, n_rows, n_rows * mrh_track::kSumWords * sizeof(i64), false))) return rc_;
+    if (!c->trk.h_sums) HIP_TRY(c, pinned_alloc(c, c->trk.h_sums, mrh_track::kSumWords * sizeof(i64)));
+    if (scan && (rc_ = regrow(c, c->trk.d_mp, c->trk.mp_cap, npix, npix * 3 * sizeof(float), false))) return rc_;
+    float* d_md = (float*) c->trk.d_img;  // the model's depth (range), then its normals
+    float* d_mn = d_md + npix;
+    const float* d_obs = obs.dev;
+    if (!d_obs && scan) {
+      const size_t bytes = n_obs * 3 * sizeof(float);
+      if ((rc_ = regrow_pinned(c, c->trk.h_cloud, c->trk.h_cloud_cap, n_obs, bytes))) return rc_;
+      if ((rc_ = regrow(c, c->trk.d_cloud, c->trk.cloud_cap, n_obs, bytes, false))) return rc_;
+      memcpy(c->trk.h_cloud, obs.host, bytes);
+      HIP_TRY(c, hipMemcpyAsync(c->trk.d_cloud, c->trk.h_cloud, bytes, hipMemcpyHostToDevice, c->stream));
+      d_obs = c->trk.d_cloud;
+    } else if (!d_obs) {
+      if ((rc_ = regrow_pinned(c, c->trk.h_depth, c->trk.h_cap, npix, npix * sizeof(float)))) return rc_;
+      memcpy(c->trk.h_depth, obs.host, npix * sizeof(float));
+      HIP_TRY(c, hipMemcpyAsync(d_md + 4 * npix, c->trk.h_depth, npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
+      d_obs = d_md + 4 * npix;
     }
-    mrh_track::update(R, t, xi);
-    done++;
+    launch_raycast(c, obs.model, rc, RayOut{d_md, d_mn, nullptr, scan ? c->trk.d_mp : nullptr});
+    HIP_TRY(c, hipGetLastError());
+
+    TrackLin k;
+    k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.ifx = rc.ifx; k.ify = rc.ify;
+    k.rows = rc.rows; k.cols = rc.cols;
+    k.min_depth = rc.min_depth; k.max_depth = rc.max_depth;
+    k.dmax2 = dist_max * dist_max;
+    k.s_a = mrh_track::angle_scale(rc.max_depth);
+    for (int i = 0; i < 9; i++) k.Rr[i] = R0[i];
+    for (int i = 0; i < 3; i++) k.tr[i] = t0[i];
+    for (int it = 0; it < iterations; it++) {
+      for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
+      for (int i = 0; i < 3; i++) k.t[i] = (float) t[i];
+      if (scan) k_track_scan_linearise<<<grid, 256, 0, c->stream>>>(k, d_obs, (unsigned) n_obs, d_md, d_mn, c->trk.d_mp, c->trk.d_slab);
+      else k_track_linearise<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(k, d_obs, d_md, d_mn, c->trk.d_slab);
+      k_track_finish<<<1, 1024, 0, c->stream>>>(c->trk.d_slab, (int) n_rows, c->trk.h_sums);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
+      for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) c->trk.h_sums)[i];
+      double xi[6];
+      if (!mrh_track::solve(sums, k.s_a, min_pixels, xi)) {
+        status = MRH_TRACK_LOST;
+        break;
+      }
+      mrh_track::update(R, t, xi);
+      done++;
+    }
   }
   for (int i = 0; i < 9; i++) out_R[i] = (float) R[i];
   for (int i = 0; i < 3; i++) out_t[i] = (float) t[i];
@@ -864,12 +892,22 @@ extern "C" {
 
 int mrh_track_depth(mrh_ctx* c, const mrh_track_params* p, const float* depth_host, const float R_init[9], const float t_init[3], float out_R[9],
                     float out_t[3], mrh_track_info* out_info) {
-  return track_run(c, "mrh_track_depth", p, depth_host, nullptr, R_init, t_init, out_R, out_t, out_info);
+  return track_run(c, "mrh_track_depth", p, TrackObs{MRH_CAMERA_PINHOLE, depth_host, nullptr, 0}, R_init, t_init, out_R, out_t, out_info);
 }
 
 int mrh_track_depth_device(mrh_ctx* c, const mrh_track_params* p, const float* d_depth, const float R_init[9], const float t_init[3], float out_R[9],
                            float out_t[3], mrh_track_info* out_info) {
-  return track_run(c, "mrh_track_depth_device", p, nullptr, d_depth, R_init, t_init, out_R, out_t, out_info);
+  return track_run(c, "mrh_track_depth_device", p, TrackObs{MRH_CAMERA_PINHOLE, nullptr, d_depth, 0}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_scan(mrh_ctx* c, const mrh_track_params* p, const float* points_host, size_t n, const float R_init[9], const float t_init[3], float out_R[9],
+                   float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_scan", p, TrackObs{MRH_CAMERA_SPHERICAL, points_host, nullptr, n}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_scan_device(mrh_ctx* c, const mrh_track_params* p, const float* d_points, size_t n, const float R_init[9], const float t_init[3],
+                          float out_R[9], float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_scan_device", p, TrackObs{MRH_CAMERA_SPHERICAL, nullptr, d_points, n}, R_init, t_init, out_R, out_t, out_info);
 }
 
 }  // extern "C"

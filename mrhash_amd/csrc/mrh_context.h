@@ -423,12 +423,16 @@ struct mrh_ctx {
   char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
   char* h_ray = nullptr; size_t h_ray_cap = 0;
   // depth-frame tracking (mrh_track.h), grow-only — device [model depth f32 | model normals 3 x f32 | the caller's depth f32] per
-  // pixel and the partial slab (one row of 32 words per workgroup); pinned: the staged depth image and the 32 sums the host reads
+  // pixel and the partial slab (one row of 32 words per workgroup); pinned: the staged depth image and the 32 sums the host reads.
+  // Scan tracking (D15) keeps the model's range and normals in d_img too and adds the model's points image and the staged cloud
   struct Track {
     char* d_img = nullptr; size_t cap = 0;           // pixels
     long long* d_slab = nullptr; size_t slab_cap = 0;  // rows
     float* h_depth = nullptr; size_t h_cap = 0;      // pixels
     long long* h_sums = nullptr;
+    float* d_mp = nullptr; size_t mp_cap = 0;        // pixels, 3 x f32 each
+    float* d_cloud = nullptr; size_t cloud_cap = 0;  // points, 3 x f32 each
+    float* h_cloud = nullptr; size_t h_cloud_cap = 0;  // points
   } trk;
   // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of
   // every point, grow-only; two sets of counters, a scan's last launch zeroes the next one's

@@ -1,4 +1,4 @@
-// mrh_track.h — depth-frame tracking against the raycast map: the linearisation of point-to-plane ICP (include/mrhash_track.h;
+// mrh_track.h — depth-frame and scan tracking against the raycast map: the linearisation of point-to-plane ICP (include/mrhash_track.h;
 // DESIGN.md §4.9 and D14, which is normative; tests/track_ref.py restates it).  The reference has no tracker: the definition is
 // this project's.  The model images come from k_raycast<false> (mrh_raycast.h), unchanged; the solve and the pose update are the
 // host's (mrh_tracksolve.h).
@@ -18,6 +18,10 @@
 // waves meet in 1 KiB of LDS and every workgroup writes one row of 32 words into the partial slab with plain vector stores: no
 // atomics of any kind (29 shared words under one 64-bit atomic per workgroup each are the contended shape), no scratch.
 // k_track_finish, one workgroup, sums the slab's rows into the 32 words the host reads from pinned memory.
+//
+// k_track_scan_linearise (tests/track_scan_ref.py): the same for a LiDAR scan — one lane per sensor-frame
+// point, a 1-D grid of 256-lane workgroups — against the range, normals and points images of k_raycast<true>.  Steps 6-8
+// (track_row) and the reduction (track_reduce_store) are shared with the depth kernel; n <= 2^24 points keeps the bounds above.
 #pragma once
 
 #include "mrh_raycast.h"
@@ -39,6 +43,22 @@ struct TrackLin {
 
 __device__ __forceinline__ f3 track_rows(const float* M, const float x, const float y, const float z) {  // (M_i0 x + M_i1 y) + M_i2 z
   return mk3((M[0] * x + M[1] * y) + M[2] * z, (M[3] * x + M[4] * y) + M[5] * z, (M[6] * x + M[7] * y) + M[8] * z);
+}
+
+// steps 6-8 of D14, shared by the depth image and the scan (D15): the gate, the residual and the fixed-point row.  False: rejected.
+__device__ __forceinline__ bool track_row(const TrackLin& k, const f3 a, const f3 pw, const f3 V, const f3 N, int J[6], int& e_fix) {
+  const f3 dl = mk3(V.x - pw.x, V.y - pw.y, V.z - pw.z);
+  if (!((dl.x * dl.x + dl.y * dl.y) + dl.z * dl.z <= k.dmax2)) return false;  // a NaN is rejected
+  const float e = (N.x * dl.x + N.y * dl.y) + N.z * dl.z;
+  const float Jf[6] = {(a.y * N.z - a.z * N.y) * k.s_a, (a.z * N.x - a.x * N.z) * k.s_a, (a.x * N.y - a.y * N.x) * k.s_a,
+                       N.x * mrh_track::kJOne, N.y * mrh_track::kJOne, N.z * mrh_track::kJOne};
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+    if (!(fabsf(Jf[i]) < 32768.0f)) return false;  // a NaN is rejected
+#pragma unroll
+  for (int i = 0; i < 6; ++i) J[i] = (int) rintf(Jf[i]);
+  e_fix = (int) rintf(e * mrh_track::kEOne);
+  return true;
 }
 
 // steps 1-8 of D14 for the pixel (r, c), which lies inside the image.  False: rejected.
@@ -64,18 +84,35 @@ __device__ __forceinline__ bool track_pixel(const TrackLin& k, const float* __re
   const f3 g = track_rows(k.Rr, ex, ey, 1.f);
   const f3 V = mk3(k.tr[0] + m * g.x, k.tr[1] + m * g.y, k.tr[2] + m * g.z);
   const f3 N = mk3(Mn[3 * pix + 0], Mn[3 * pix + 1], Mn[3 * pix + 2]);
-  const f3 dl = mk3(V.x - pw.x, V.y - pw.y, V.z - pw.z);
-  if (!((dl.x * dl.x + dl.y * dl.y) + dl.z * dl.z <= k.dmax2)) return false;  // a NaN is rejected
-  const float e = (N.x * dl.x + N.y * dl.y) + N.z * dl.z;
-  const float Jf[6] = {(a.y * N.z - a.z * N.y) * k.s_a, (a.z * N.x - a.x * N.z) * k.s_a, (a.x * N.y - a.y * N.x) * k.s_a,
-                       N.x * mrh_track::kJOne, N.y * mrh_track::kJOne, N.z * mrh_track::kJOne};
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-    if (!(fabsf(Jf[i]) < 32768.0f)) return false;  // a NaN is rejected
-#pragma unroll
-  for (int i = 0; i < 6; ++i) J[i] = (int) rintf(Jf[i]);
-  e_fix = (int) rintf(e * mrh_track::kEOne);
-  return true;
+  return track_row(k, a, pw, V, N, J, e_fix);
+}
+
+// steps 1-8 of D15 for point i of the cloud (i < n).  Mr, Mn, Mp: range, world-frame normals and sensor-frame points of the
+// spherical render from (Rr, tr); k.fx .. k.cy, rows, cols are that render's.  False: rejected.
+__device__ __forceinline__ bool track_point(const TrackLin& k, const float* __restrict__ pts, const float* __restrict__ Mr, const float* __restrict__ Mn,
+                                            const float* __restrict__ Mp, const size_t i, int J[6], int& e_fix) {
+  const float x = pts[3 * i + 0], y = pts[3 * i + 1], z = pts[3 * i + 2];
+  const float rp = sqrtf((x * x + y * y) + z * z);
+  if (!(rp > k.min_depth && rp <= k.max_depth)) return false;  // (0, 0, 0), a NaN and an infinity fail
+  const f3 a = track_rows(k.R, x, y, z);
+  const f3 pw = mk3(a.x + k.t[0], a.y + k.t[1], a.z + k.t[2]);
+  const f3 w = mk3(pw.x - k.tr[0], pw.y - k.tr[1], pw.z - k.tr[2]);
+  const float qx = (k.Rr[0] * w.x + k.Rr[3] * w.y) + k.Rr[6] * w.z;  // R_r^T w
+  const float qy = (k.Rr[1] * w.x + k.Rr[4] * w.y) + k.Rr[7] * w.z;
+  const float qz = (k.Rr[2] * w.x + k.Rr[5] * w.y) + k.Rr[8] * w.z;
+  const float rq = sqrtf((qx * qx + qy * qy) + qz * qz);
+  if (!(rq > k.min_depth && rq <= k.max_depth)) return false;
+  const float az = mrh_atan2f(qy, qx), el = mrh_asinf(qz / rq);  // project_point_m's expressions
+  const float u = (k.fx * az + k.cx) + 1.0f, v = (k.fy * el + k.cy) + 1.0f;
+  if (!(u >= 0.f && u < (float) k.cols && v >= 0.f && v < (float) k.rows)) return false;  // in float, before any conversion
+  const int c2 = (int) floorf(u), r2 = (int) floorf(v);  // 0 .. cols - 1, 0 .. rows - 1 by the test above
+  const size_t pix = (size_t) r2 * (size_t) k.cols + (size_t) c2;
+  if (Mr[pix] == 0.f) return false;
+  const f3 N = mk3(Mn[3 * pix + 0], Mn[3 * pix + 1], Mn[3 * pix + 2]);
+  if (N.x == 0.f && N.y == 0.f && N.z == 0.f) return false;  // a hit without a gradient: no row, and no count
+  const f3 g = track_rows(k.Rr, Mp[3 * pix + 0], Mp[3 * pix + 1], Mp[3 * pix + 2]);
+  const f3 V = mk3(k.tr[0] + g.x, k.tr[1] + g.y, k.tr[2] + g.z);
+  return track_row(k, a, pw, V, N, J, e_fix);
 }
 
 __device__ __forceinline__ i64 track_xor64(const i64 v, const int mask) {
@@ -83,16 +120,11 @@ __device__ __forceinline__ i64 track_xor64(const i64 v, const int mask) {
   return (i64) (((unsigned long long) (unsigned) hi << 32) | (unsigned long long) (unsigned) lo);
 }
 
-// slab: one row of 32 words per workgroup, row = blockIdx.y * gridDim.x + blockIdx.x
-__global__ __launch_bounds__(256) void k_track_linearise(const TrackLin k, const float* __restrict__ depth, const float* __restrict__ Md,
-                                                         const float* __restrict__ Mn, i64* __restrict__ slab) {
+// Step 9 for one workgroup of four waves, every lane of which arrives: the 29 products of the lane's row (zeros unless ok) summed
+// over the workgroup into row blockIdx.y * gridDim.x + blockIdx.x of the slab (32 words per row).
+__device__ __forceinline__ void track_reduce_store(int J[6], int e, const bool ok, i64* __restrict__ slab) {
   __shared__ i64 part[4][mrh_track::kSumWords];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
-  const int r = blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
-  int J[6] = {0, 0, 0, 0, 0, 0}, e = 0;
-  bool ok = r < k.rows && c < k.cols;
-  if (ok) ok = track_pixel(k, depth, Md, Mn, r, c, J, e);
   if (!ok) {
 #pragma unroll
     for (int i = 0; i < 6; ++i) J[i] = 0;
@@ -129,6 +161,29 @@ __global__ __launch_bounds__(256) void k_track_linearise(const TrackLin k, const
     const int i = threadIdx.x;
     slab[((size_t) blockIdx.y * gridDim.x + blockIdx.x) * mrh_track::kSumWords + i] = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
   }
+}
+
+// the depth image: a 2-D grid of 16 x 16 tiles
+__global__ __launch_bounds__(256) void k_track_linearise(const TrackLin k, const float* __restrict__ depth, const float* __restrict__ Md,
+                                                         const float* __restrict__ Mn, i64* __restrict__ slab) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
+  const int r = blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
+  int J[6] = {0, 0, 0, 0, 0, 0}, e = 0;
+  bool ok = r < k.rows && c < k.cols;
+  if (ok) ok = track_pixel(k, depth, Md, Mn, r, c, J, e);
+  track_reduce_store(J, e, ok, slab);
+}
+
+// the scan (D15): one lane per point, a 1-D grid of ceil(n / 256) workgroups; the cloud need not be organised, so the gathers from
+// the model images go where the points project
+__global__ __launch_bounds__(256) void k_track_scan_linearise(const TrackLin k, const float* __restrict__ pts, const unsigned n, const float* __restrict__ Mr,
+                                                              const float* __restrict__ Mn, const float* __restrict__ Mp, i64* __restrict__ slab) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  int J[6] = {0, 0, 0, 0, 0, 0}, e = 0;
+  bool ok = i < n;
+  if (ok) ok = track_point(k, pts, Mr, Mn, Mp, (size_t) i, J, e);
+  track_reduce_store(J, e, ok, slab);
 }
 
 // one workgroup of 1024: thread (stripe, word) adds the rows stripe, stripe + 32, ... of its word, the stripes meet in LDS

@@ -23,6 +23,22 @@ py::array_t<T> to_array(const std::vector<T>& v, size_t cols) {
   return a;
 }
 
+// (t [3], q [4] = qx,qy,qz,qw, info dict) of a tracking call
+py::tuple track_tuple(const GeoWrapper::TrackResult& r) {
+  py::array_t<float> ot(3), oq(4);
+  std::memcpy(ot.mutable_data(), r.t.data(), 3 * sizeof(float));
+  std::memcpy(oq.mutable_data(), r.q.data(), 4 * sizeof(float));
+  py::array_t<int64_t> sums(32);
+  std::memcpy(sums.mutable_data(), r.info.sums, sizeof r.info.sums);
+  py::dict info;
+  info["status"] = r.info.status;
+  info["iterations_done"] = r.info.iterations_done;
+  info["pixels"] = r.info.pixels;
+  info["rms"] = r.info.rms;
+  info["sums"] = sums;
+  return py::make_tuple(ot, oq, info);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(pygeowrapper, m) {
@@ -211,19 +227,20 @@ PYBIND11_MODULE(pygeowrapper, m) {
       } else {
         r = g.trackDepthImage(depth.data(), (size_t) depth.shape(0), (size_t) depth.shape(1));
       }
-      py::array_t<float> ot(3), oq(4);
-      std::memcpy(ot.mutable_data(), r.t.data(), 3 * sizeof(float));
-      std::memcpy(oq.mutable_data(), r.q.data(), 4 * sizeof(float));
-      py::array_t<int64_t> sums(32);
-      std::memcpy(sums.mutable_data(), r.info.sums, sizeof r.info.sums);
-      py::dict info;
-      info["status"] = r.info.status;
-      info["iterations_done"] = r.info.iterations_done;
-      info["pixels"] = r.info.pixels;
-      info["rms"] = r.info.rms;
-      info["sums"] = sums;
-      return py::make_tuple(ot, oq, info);
+      return track_tuple(r);
     }, py::arg("depth"), py::arg("t") = py::none(), py::arg("q") = py::none())
+    // the same for a LiDAR scan ([N, 3] float32, sensor frame) under the spherical camera of setCamera(..., model = 1); the loop is
+    // trackPointCloud -> setCurrPose -> setPointCloud -> compute
+    .def("trackPointCloud", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> pts,
+                               std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                               std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> q) {
+      if (pts.ndim() != 2 || pts.shape(1) != 3) throw std::runtime_error("GeoWrapper::trackPointCloud|input should be a 2D numpy array with 3 columns");
+      if (t.has_value() != q.has_value()) throw std::runtime_error("GeoWrapper::trackPointCloud|give both t and q, or neither");
+      if (!t) return track_tuple(g.trackPointCloud(pts.data(), (size_t) pts.shape(0)));
+      if (t->size() != 3 || q->size() != 4) throw std::runtime_error("GeoWrapper::trackPointCloud|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+      return track_tuple(g.trackPointCloud(pts.data(), (size_t) pts.shape(0), {t->data()[0], t->data()[1], t->data()[2]},
+                                           {q->data()[0], q->data()[1], q->data()[2], q->data()[3]}));
+    }, py::arg("points"), py::arg("t") = py::none(), py::arg("q") = py::none())
     .def("clearBuffers", &GeoWrapper::clearBuffers)
     .def("serializeData", &GeoWrapper::serializeData, py::arg("filename_hash") = "./data/hash_points.ply",
          py::arg("filename_voxel") = "./data/voxel_points.ply")
