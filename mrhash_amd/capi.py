@@ -139,6 +139,18 @@ class MrhRaycastParams(C.Structure):
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float), ("outputs", C.c_uint32)]
 
 
+# every symbol include/mrhash_esdf.h declares (the HIP library only: the oracle has no distance field)
+ESDF_SYMBOLS = ("mrh_esdf mrh_esdf_device").split()
+ESDF_STATE, ESDF_SQUARED = 1, 2
+ESDF_OBSERVED, ESDF_SITE, ESDF_INSIDE, ESDF_FAR = 1, 2, 4, 8
+ESDF_FAR_D2 = 0xFFFFFFFF
+
+
+class MrhEsdfParams(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("max_distance_voxels", C.c_int32), ("min_weight", C.c_int32),
+                ("surface_band", C.c_float), ("outputs", C.c_uint32)]
+
+
 # every symbol include/mrhash_track.h declares (the HIP library only: the oracle does not track)
 TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device mrh_track_scan mrh_track_scan_device").split()
 TRACK_OK, TRACK_LOST = 0, 1
@@ -271,6 +283,11 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_raycast_spherical.argtypes = lib.mrh_raycast.argtypes + [P(C.c_void_p)]
         lib.mrh_raycast_spherical_device.argtypes = lib.mrh_raycast_device.argtypes + [C.c_void_p]
         for name in RAYCAST_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_esdf"):  # include/mrhash_esdf.h
+        lib.mrh_esdf.argtypes = [C.c_void_p, P(MrhEsdfParams), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
+        lib.mrh_esdf_device.argtypes = [C.c_void_p, P(MrhEsdfParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ESDF_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_track_depth"):  # include/mrhash_track.h
         lib.mrh_track_depth.argtypes = [C.c_void_p, P(MrhTrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
@@ -792,6 +809,38 @@ class Engine:
         F = C.POINTER(C.c_float)
         self._check(self.lib.mrh_raycast_spherical_device(self._ctx, C.byref(p), R.ctypes.data_as(F), t.ctypes.data_as(F), d_range or None,
                                                           d_normals or None, d_rgb or None, d_points or None))
+
+    # -- distance fields (include/mrhash_esdf.h) ------------------------------------------------------
+    @staticmethod
+    def _esdf_params(origin, dims, max_distance_voxels, surface_band, min_weight, state, squared):
+        o, n = [int(x) for x in origin], [int(x) for x in dims]
+        if len(o) != 3 or len(n) != 3:
+            raise ValueError("esdf: origin and dims are triples (x, y, z)")
+        return MrhEsdfParams((C.c_int32 * 3)(*o), (C.c_int32 * 3)(*n), int(max_distance_voxels), int(min_weight), float(surface_band),
+                             (ESDF_STATE if state else 0) | (ESDF_SQUARED if squared else 0))
+
+    def esdf(self, origin, dims, max_distance_voxels, surface_band=0.0, min_weight=0, state=True, squared=False):
+        """The Euclidean signed distance field of the box of finest voxels origin + [0, dims) (x, y, z), exact up to
+        max_distance_voxels (mrh_esdf); only sites inside the box are seen, so pad it by the reach.  Returns
+        numpy copies shaped [nz, ny, nx]: (dist f32 in metres, state u8 or None, d2 u32 or None).  State bits: ESDF_OBSERVED,
+        ESDF_SITE, ESDF_INSIDE, ESDF_FAR; d2 of a far cell is ESDF_FAR_D2."""
+        p = self._esdf_params(origin, dims, max_distance_voxels, surface_band, min_weight, state, squared)
+        pd, ps, pq = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.lib.mrh_esdf(self._ctx, C.byref(p), C.byref(pd), C.byref(ps) if state else None, C.byref(pq) if squared else None))
+        nx, ny, nz = (int(x) for x in dims)
+        n = nx * ny * nz
+
+        def arr(ptr, dt):
+            return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).reshape(nz, ny, nx).copy()
+
+        return arr(pd, np.float32), arr(ps, np.uint8) if state else None, arr(pq, np.uint32) if squared else None
+
+    def esdf_device(self, origin, dims, max_distance_voxels, surface_band=0.0, min_weight=0, d_dist=0, d_state=0, d_d2=0):
+        """mrh_esdf_device: enqueues the field into caller device buffers (integer pointers, e.g. hipmem.DeviceBuffer.ptr:
+        [n] f32, [n] u8, [n] u32 with n = nx * ny * nz; d_dist is required, 0 = skip for the other two).  Ordered on the
+        context's stream; finished by sync() or any blocking call."""
+        p = self._esdf_params(origin, dims, max_distance_voxels, surface_band, min_weight, bool(d_state), bool(d_d2))
+        self._check(self.lib.mrh_esdf_device(self._ctx, C.byref(p), d_dist or None, d_state or None, d_d2 or None))
 
     # -- tracking (include/mrhash_track.h) ------------------------------------------------------------
     def _track(self, fn, obs, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):

@@ -591,6 +591,35 @@ GeoWrapper::RaycastScan GeoWrapper::raycastScanPose(const std::array<float, 16>&
   return out;
 }
 
+GeoWrapper::DistanceField GeoWrapper::distanceField(const std::array<float, 3>& lo, const std::array<float, 3>& hi, const float max_distance) {
+  const double vs = (double) virtual_voxel_size_;
+  mrh_esdf_params p;
+  std::memset(&p, 0, sizeof p);
+  for (int a = 0; a < 3; a++) {
+    if (!(hi[a] >= lo[a])) throw std::runtime_error("GeoWrapper::distanceField|hi < lo on axis " + std::to_string(a));
+    const double first = std::floor((double) lo[a] / vs + 0.5), last = std::floor((double) hi[a] / vs + 0.5);
+    if (!(last - first + 1.0 <= (double) MRH_ESDF_MAX_SIDE))
+      throw std::runtime_error("GeoWrapper::distanceField|axis " + std::to_string(a) + " of the box spans more than " + std::to_string(MRH_ESDF_MAX_SIDE) + " voxels");
+    if (!(std::fabs(first) < 2147483000.0)) throw std::runtime_error("GeoWrapper::distanceField|the box is out of range");
+    p.origin[a] = (int32_t) first;
+    p.dims[a] = (int32_t) (last - first + 1.0);
+  }
+  const double reach = std::ceil((double) max_distance / vs);
+  if (!(reach >= 1.0 && reach <= (double) MRH_ESDF_MAX_REACH))
+    throw std::runtime_error("GeoWrapper::distanceField|max_distance must be within (0, " + std::to_string(MRH_ESDF_MAX_REACH) + " voxels]");
+  p.max_distance_voxels = (int32_t) reach;
+  p.outputs = MRH_ESDF_STATE;
+  const float* dist = nullptr;
+  const uint8_t* state = nullptr;
+  check(mrh_esdf(ctx_, &p, &dist, &state, nullptr), "distanceField");
+  DistanceField out;
+  const size_t n = (size_t) p.dims[0] * (size_t) p.dims[1] * (size_t) p.dims[2];
+  for (int a = 0; a < 3; a++) { out.origin[a] = p.origin[a]; out.dims[a] = p.dims[a]; }
+  out.dist.assign(dist, dist + n);
+  out.state.assign(state, state + n);
+  return out;
+}
+
 GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols) { return trackDepthPose(depth, rows, cols, pose_); }
 
 GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) {

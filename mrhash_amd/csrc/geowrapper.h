@@ -13,6 +13,7 @@
 #include "mrhash_hip.h"
 #include "mrhash_comm.h"
 #include "mrhash_raycast.h"
+#include "mrhash_esdf.h"
 #include "mrhash_track.h"
 #include "mrhash_normals.h"
 
@@ -117,6 +118,18 @@ public:
   };
   RaycastScan raycastScan();
   RaycastScan raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q);
+
+  // ---- distance fields (include/mrhash_esdf.h; no reference counterpart): the Euclidean signed distance to the
+  // nearest surface for every finest voxel of the world box [lo, hi] (metres), exact up to max_distance.  Per axis the box is
+  // origin = floor(lo / vs + 0.5) .. floor(hi / vs + 0.5) in voxels (in double), the reach ceil(max_distance / vs) voxels.  Only
+  // surface inside the box is seen: pad the box by max_distance.  dist [nx * ny * nz] metres and state [nx * ny * nz] (MRH_ESDF_*
+  // bits), x fastest.  Throws std::runtime_error when hi < lo or a side exceeds MRH_ESDF_MAX_SIDE voxels.
+  struct DistanceField {
+    std::array<int32_t, 3> origin{}, dims{};
+    std::vector<float> dist;
+    std::vector<uint8_t> state;
+  };
+  DistanceField distanceField(const std::array<float, 3>& lo, const std::array<float, 3>& hi, float max_distance);
 
   // ---- tracking (include/mrhash_track.h; no reference counterpart): the pose of a depth image (rows x cols as
   // the camera of the last setCamera, metres) by point-to-plane ICP against the map, started from the current pose (setCurrPose)

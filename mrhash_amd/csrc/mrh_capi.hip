@@ -1,7 +1,7 @@
 // mrh_capi.hip — implementation of the C ABI (include/mrhash_hip.h) on top of the gfx950 kernels.
 //
 // Host side of the thin HIP layer: enqueues the per-frame kernel chain with no host round trip, and only synchronises in the
-// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the splat, raycast, tracking and normals glue.
+// calls that hand data back.  Here: the helpers every entry point shares, the entry points, the splat, raycast, distance-field, tracking and normals glue.
 // The context and its lifetime: mrh_context.h; the copy pool: mrh_hostcopy.h; uploads, frame marks, peeks: mrh_upload.h; the
 // host side of a depth frame: mrh_frame.h; extraction, scans, block I/O, RCCL: mrh_extract.h, mrh_points.h, mrh_blocks.h,
 // mrh_comm.h.  One translation unit.
@@ -26,11 +26,13 @@
 #include "../../include/mrhash_hip.h"
 #include "../../include/mrhash_comm.h"
 #include "../../include/mrhash_raycast.h"
+#include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_track.h"
 #include "../../include/mrhash_normals.h"
 #include "mrh_kernels.h"
 #include "mrh_mc.h"
 #include "mrh_raycast.h"
+#include "mrh_esdf.h"
 #include "mrh_track.h"
 #include "mrh_normals.h"
 #include "mrh_fast.h"
@@ -775,6 +777,99 @@ int mrh_raycast_spherical(mrh_ctx* c, const mrh_raycast_params* p, const float R
 int mrh_raycast_spherical_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_range,
                                  float* d_normals, uint8_t* d_rgb, float* d_points) {
   return raycast_device(c, "mrh_raycast_spherical_device", MRH_CAMERA_SPHERICAL, p, R_row_major, t, RayOut{d_range, d_normals, d_rgb, d_points});
+}
+
+}  // extern "C"
+
+// ---- distance fields (include/mrhash_esdf.h, mrh_esdf.h) ---------------------------------------------------------------------
+namespace {
+
+// the arguments both entry points share, checked before the map is touched; fills the kernels' box
+int esdf_args(mrh_ctx* c, const char* who, const mrh_esdf_params* p, EsdfBox* bx) {
+  if (!p) return fail(c, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (c->pending) return fail(c, MRH_ERR_STATE, "%s: an exchange is pending (call mrh_integrate_resume)", who);
+  if (c->map.shard_count > 1) return fail(c, MRH_ERR_UNSUPPORTED, "%s: sharded maps have no distance field (shard_count %d)", who, c->map.shard_count);
+  for (int a = 0; a < 3; a++) {
+    if (p->dims[a] < 1 || p->dims[a] > MRH_ESDF_MAX_SIDE)
+      return fail(c, MRH_ERR_INVALID_ARG, "%s: box of %d x %d x %d cells (1 .. %d per side)", who, p->dims[0], p->dims[1], p->dims[2], MRH_ESDF_MAX_SIDE);
+    const int64_t lo = p->origin[a], hi = lo + p->dims[a] - 1;
+    if (lo < -(1ll << 23) || hi >= (1ll << 23))
+      return fail(c, MRH_ERR_INVALID_ARG, "%s: axis %d of the box spans voxels %lld .. %lld, outside [-2^23, 2^23)", who, a, (long long) lo, (long long) hi);
+  }
+  if (p->max_distance_voxels < 1 || p->max_distance_voxels > MRH_ESDF_MAX_REACH)
+    return fail(c, MRH_ERR_INVALID_ARG, "%s: max_distance_voxels %d (1 .. %d)", who, p->max_distance_voxels, MRH_ESDF_MAX_REACH);
+  if (!std::isfinite(p->surface_band) || p->surface_band < 0.f) return fail(c, MRH_ERR_INVALID_ARG, "%s: surface_band %g", who, (double) p->surface_band);
+  if (p->min_weight < 0) return fail(c, MRH_ERR_INVALID_ARG, "%s: min_weight %d", who, p->min_weight);
+  if (p->outputs & ~(MRH_ESDF_STATE | MRH_ESDF_SQUARED)) return fail(c, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  bx->ox = p->origin[0]; bx->oy = p->origin[1]; bx->oz = p->origin[2];
+  bx->nx = p->dims[0]; bx->ny = p->dims[1]; bx->nz = p->dims[2];
+  bx->reach = (u32) p->max_distance_voxels;
+  bx->w_min = std::max(1, p->min_weight ? p->min_weight : c->map.min_weight_threshold);
+  bx->band = p->surface_band;
+  return MRH_OK;
+}
+
+// the scratch of a box of n cells, before its pointers are handed to launch_esdf
+int esdf_scratch(mrh_ctx* c, const size_t n) {
+  mrh_ctx::Esdf& e = c->esdf;
+  if (n <= e.cap) return MRH_OK;  // an earlier mrh_esdf_device may still read the old scratch: regrow_all drains the stream
+  return regrow_all(c, e.cap, n, {{e.d_state, n}, {e.d_row, n * sizeof(uint16_t)}, {e.d_plane, n * sizeof(u32)}});
+}
+
+// the four launches on the scratch esdf_scratch has sized; out_state (which may be the scratch's own state plane) and out_d2 may be nullptr
+int launch_esdf(mrh_ctx* c, const EsdfBox& bx, float* dist, uint8_t* out_state, u32* out_d2) {
+  mrh_ctx::Esdf& e = c->esdf;
+  hipStream_t s = c->stream;
+  const auto bricks = [](const int o, const int len) { return (unsigned) (((o + len - 1) >> 3) - (o >> 3) + 1); };
+  const unsigned tiles = (unsigned) ((bx.nx + kEsdfTile - 1) / kEsdfTile);
+  k_esdf_classify<<<dim3(bricks(bx.ox, bx.nx), bricks(bx.oy, bx.ny), bricks(bx.oz, bx.nz)), 256, 0, s>>>(c->map, c->tab, bx, e.d_state, dist);
+  k_esdf_rows<<<(unsigned) (((size_t) bx.ny * (size_t) bx.nz + 3) / 4), 256, 0, s>>>(bx, e.d_state, e.d_row);
+  k_esdf_columns_y<<<dim3(tiles, (unsigned) bx.nz), 256, (size_t) kEsdfTile * (size_t) bx.ny * sizeof(u32), s>>>(bx, e.d_row, e.d_plane);
+  k_esdf_columns_z<<<dim3(tiles, (unsigned) bx.ny), 256, (size_t) kEsdfTile * (size_t) bx.nz * sizeof(u32), s>>>(c->map, bx, e.d_plane, e.d_state, dist, out_state, out_d2);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+static_assert((size_t) kEsdfTile * MRH_ESDF_MAX_SIDE * sizeof(u32) <= 65536, "a staged column tile fits the default dynamic LDS limit");
+static_assert(kEsdfMaxSide == MRH_ESDF_MAX_SIDE && kEsdfTile * kEsdfColumnLanes == 256, "mrh_esdf.h and mrhash_esdf.h agree");
+
+}  // namespace
+
+extern "C" {
+
+int mrh_esdf(mrh_ctx* c, const mrh_esdf_params* p, const float** out_dist, const uint8_t** out_state, const uint32_t** out_d2) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  EsdfBox bx;
+  int rc = esdf_args(c, "mrh_esdf", p, &bx);
+  if (rc) return rc;
+  if ((rc = ensure_ready(c, "mrh_esdf"))) return rc;
+  const size_t n = (size_t) bx.nx * (size_t) bx.ny * (size_t) bx.nz;
+  mrh_ctx::Esdf& e = c->esdf;
+  // results per cell: device dist f32 and d2 u32; pinned [dist f32 | d2 u32 | state u8], each plane contiguous
+  if (n > e.out_cap && (rc = regrow_all(c, e.out_cap, n, {{e.d_dist, n * sizeof(float)}, {e.d_d2, n * sizeof(u32)}}))) return rc;
+  if ((rc = regrow_pinned(c, e.h_out, e.h_cap, n, n * 9))) return rc;
+  if ((rc = esdf_scratch(c, n))) return rc;
+  const bool want_s = out_state && (p->outputs & MRH_ESDF_STATE), want_q = out_d2 && (p->outputs & MRH_ESDF_SQUARED);
+  if ((rc = launch_esdf(c, bx, e.d_dist, want_s ? e.d_state : nullptr, want_q ? e.d_d2 : nullptr))) return rc;
+  char* h_dist = e.h_out; char* h_d2 = e.h_out + n * 4; char* h_state = e.h_out + n * 8;
+  if (out_dist) HIP_TRY(c, hipMemcpyAsync(h_dist, e.d_dist, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (want_q) HIP_TRY(c, hipMemcpyAsync(h_d2, e.d_d2, n * sizeof(u32), hipMemcpyDeviceToHost, c->stream));
+  if (want_s) HIP_TRY(c, hipMemcpyAsync(h_state, e.d_state, n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (out_dist) *out_dist = (const float*) h_dist;
+  if (out_state) *out_state = want_s ? (const uint8_t*) h_state : nullptr;
+  if (out_d2) *out_d2 = want_q ? (const uint32_t*) h_d2 : nullptr;
+  return MRH_OK;
+}
+
+int mrh_esdf_device(mrh_ctx* c, const mrh_esdf_params* p, float* d_dist, uint8_t* d_state, uint32_t* d_d2) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  EsdfBox bx;
+  int rc = esdf_args(c, "mrh_esdf_device", p, &bx);
+  if (rc) return rc;
+  if (!d_dist) return fail(c, MRH_ERR_INVALID_ARG, "mrh_esdf_device: d_dist is null");
+  if ((rc = ensure_ready(c, "mrh_esdf_device"))) return rc;
+  if ((rc = esdf_scratch(c, (size_t) bx.nx * (size_t) bx.ny * (size_t) bx.nz))) return rc;
+  return launch_esdf(c, bx, d_dist, (p->outputs & MRH_ESDF_STATE) ? d_state : nullptr, (p->outputs & MRH_ESDF_SQUARED) ? (u32*) d_d2 : nullptr);
 }
 
 }  // extern "C"

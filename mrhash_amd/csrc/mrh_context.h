@@ -422,6 +422,13 @@ struct mrh_ctx {
   // 3 x f32 | points 3 x f32 | rgb 3 x u8] per pixel and the pinned host copy the caller reads
   char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
   char* h_ray = nullptr; size_t h_ray_cap = 0;
+  // distance fields (mrh_esdf.h), grow-only, in cells — scratch of every call: the state byte, the x pass's |dx| (u16: at most 511)
+  // and the y pass's u32 plane; results of mrh_esdf: dist and d2 on the device and the pinned [dist f32 | d2 u32 | state u8] the caller reads
+  struct Esdf {
+    uint8_t* d_state = nullptr; uint16_t* d_row = nullptr; u32* d_plane = nullptr; size_t cap = 0;
+    float* d_dist = nullptr; u32* d_d2 = nullptr; size_t out_cap = 0;
+    char* h_out = nullptr; size_t h_cap = 0;
+  } esdf;
   // depth-frame tracking (mrh_track.h), grow-only — device [model depth f32 | model normals 3 x f32 | the caller's depth f32] per
   // pixel and the partial slab (one row of 32 words per workgroup); pinned: the staged depth image and the 32 sums the host reads.
   // Scan tracking (D15) keeps the model's range and normals in d_img too and adds the model's points image and the staged cloud

@@ -211,6 +211,19 @@ PYBIND11_MODULE(pygeowrapper, m) {
       std::memcpy(points.mutable_data(), im.points.data(), im.points.size() * sizeof(float));
       return py::make_tuple(range, normals, colors, points);
     }, py::arg("t") = py::none(), py::arg("q") = py::none())
+    // not part of the reference binding: the Euclidean signed distance field of the world box [lo, hi] (metres), exact up to
+    // max_distance; returns (dist [nz, ny, nx] f32 metres, state [nz, ny, nx] u8, origin (x, y, z) in voxels, dims (nx, ny, nz))
+    .def("distanceField", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> lo,
+                             py::array_t<float, py::array::c_style | py::array::forcecast> hi, float max_distance) {
+      if (lo.size() != 3 || hi.size() != 3) throw std::runtime_error("GeoWrapper::distanceField|expected two 3-vectors (lo, hi)");
+      const GeoWrapper::DistanceField f = g.distanceField({lo.data()[0], lo.data()[1], lo.data()[2]}, {hi.data()[0], hi.data()[1], hi.data()[2]}, max_distance);
+      const size_t nx = (size_t) f.dims[0], ny = (size_t) f.dims[1], nz = (size_t) f.dims[2];
+      py::array_t<float> dist({nz, ny, nx});
+      py::array_t<uint8_t> state({nz, ny, nx});
+      std::memcpy(dist.mutable_data(), f.dist.data(), f.dist.size() * sizeof(float));
+      std::memcpy(state.mutable_data(), f.state.data(), f.state.size());
+      return py::make_tuple(dist, state, py::make_tuple(f.origin[0], f.origin[1], f.origin[2]), py::make_tuple(f.dims[0], f.dims[1], f.dims[2]));
+    }, py::arg("lo"), py::arg("hi"), py::arg("max_distance"))
     // not part of the reference binding: the pose of a depth image (2-D, the camera's rows x cols, metres) by ICP against the map,
     // started from the current pose or from (t, q); returns (t [3], q [4] = qx,qy,qz,qw, info dict) and leaves the current pose
     // alone — call setCurrPose(t, q) with the result before setDepthImage / compute
