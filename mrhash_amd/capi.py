@@ -309,6 +309,16 @@ def _declare(lib: C.CDLL) -> C.CDLL:
     return lib
 
 
+def _copy_out(ptr: C.c_void_p, count: int, dtype, shape) -> np.ndarray:
+    """A numpy copy, shaped `shape`, of the `count` elements of `dtype` a call handed out at `ptr` (the memory stays the library's).
+    A null pointer holds nothing: the first dimension becomes 0."""
+    if not ptr.value:
+        count, shape = 0, (0,) + tuple(shape)[1:]
+    if count == 0:
+        return np.zeros(shape, dtype)
+    return np.frombuffer((C.c_char * (count * np.dtype(dtype).itemsize)).from_address(ptr.value), dtype=dtype).reshape(shape).copy()
+
+
 def load_library(path: str) -> C.CDLL:
     if not os.path.exists(path):
         raise FileNotFoundError(
@@ -571,24 +581,15 @@ class Engine:
             self._check(self.lib.mrh_extract_triangles(self._ctx, None, C.byref(n)))
             return int(n.value)
         self._check(self.lib.mrh_extract_triangles(self._ctx, C.byref(ptr), C.byref(n)))
-        if n.value == 0:
-            return np.zeros((0, 3), dtype=TRI_DTYPE)
-        buf = (C.c_char * (n.value * 72)).from_address(ptr.value)
-        return np.frombuffer(buf, dtype=TRI_DTYPE).reshape(n.value, 3).copy()
+        return _copy_out(ptr, 3 * n.value, TRI_DTYPE, (n.value, 3))
 
     def extract_mesh(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(V f64[nv,3], F i32[nf,3], C f64[nv,3]) of the last extract_triangles()."""
         pv, pf, pc = C.c_void_p(), C.c_void_p(), C.c_void_p()
         nv, nf = C.c_uint64(), C.c_uint64()
         self._check(self.lib.mrh_extract_mesh(self._ctx, C.byref(pv), C.byref(nv), C.byref(pf), C.byref(nf), C.byref(pc)))
-
-        def arr(p, n, dt):
-            if n == 0 or not p.value:
-                return np.zeros((0, 3), dtype=dt)
-            sz = n * 3 * np.dtype(dt).itemsize
-            return np.frombuffer((C.c_char * sz).from_address(p.value), dtype=dt).reshape(n, 3).copy()
-
-        return arr(pv, nv.value, np.float64), arr(pf, nf.value, np.int32), arr(pc, nv.value, np.float64)
+        return (_copy_out(pv, 3 * nv.value, np.float64, (nv.value, 3)), _copy_out(pf, 3 * nf.value, np.int32, (nf.value, 3)),
+                _copy_out(pc, 3 * nv.value, np.float64, (nv.value, 3)))
 
     def mesh_merge_begin(self):
         """MeshExtractor::merge_mesh_: until mesh_merge_end() every extract_triangles() adds to the running mesh."""
@@ -609,17 +610,13 @@ class Engine:
         per leaf whose centre lands in a voxel of weight 1.  Returns a SEED_DTYPE array in canonical (leaf) order."""
         ptr, n = C.c_void_p(), C.c_uint64()
         self._check(self.lib.mrh_splat_seeds(self._ctx, qtree_thresh, qtree_min_pixel_size, C.byref(ptr), C.byref(n)))
-        if n.value == 0:
-            return np.zeros(0, SEED_DTYPE)
-        return np.frombuffer((C.c_char * (n.value * 20)).from_address(ptr.value), dtype=SEED_DTYPE).copy()
+        return _copy_out(ptr, n.value, SEED_DTYPE, (n.value,))
 
     def qtree_leaves(self) -> np.ndarray:
         """Leaves of the quad-tree of the last splat_seeds() call, canonical order (LEAF_DTYPE)."""
         ptr, n = C.c_void_p(), C.c_uint64()
         self._check(self.lib.mrh_get_qtree_leaves(self._ctx, C.byref(ptr), C.byref(n)))
-        if n.value == 0:
-            return np.zeros(0, LEAF_DTYPE)
-        return np.frombuffer((C.c_char * (n.value * 16)).from_address(ptr.value), dtype=LEAF_DTYPE).copy()
+        return _copy_out(ptr, n.value, LEAF_DTYPE, (n.value,))
 
     def peek_free_blocks(self) -> Tuple[int, int, int]:
         """(free fine, free coarse, frames behind) without waiting for the device (mrh_peek_free_blocks)."""
@@ -714,11 +711,7 @@ class Engine:
         """(descs, per-block triangle counts) of the last extract_triangles(), canonical block order."""
         pd, pc, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
         self._check(self.lib.mrh_get_triangle_blocks(self._ctx, C.byref(pd), C.byref(pc), C.byref(n)))
-        if n.value == 0:
-            return np.zeros(0, DESC_DTYPE), np.zeros(0, np.uint32)
-        d = np.frombuffer((C.c_char * (n.value * 16)).from_address(pd.value), dtype=DESC_DTYPE).copy()
-        c = np.frombuffer((C.c_char * (n.value * 4)).from_address(pc.value), dtype=np.uint32).copy()
-        return d, c
+        return _copy_out(pd, n.value, DESC_DTYPE, (n.value,)), _copy_out(pc, n.value, np.uint32, (n.value,))
 
     def triangles_device(self) -> Tuple[int, int, bool]:
         """(pointer, number of triangles, is_device_memory) of the soup of the last extraction / run merge, where the library keeps it."""
@@ -762,12 +755,9 @@ class Engine:
                                          C.byref(pn) if normals else None, C.byref(pc) if colors else None))
         n = int(rows) * int(cols)
 
-        def arr(ptr, count, dt, shape):
-            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).reshape(shape).copy()
-
-        depth = arr(pd, n, np.float32, (rows, cols))
-        nrm = arr(pn, 3 * n, np.float32, (rows, cols, 3)) if normals else None
-        rgb = arr(pc, 3 * n, np.uint8, (rows, cols, 3)) if colors else None
+        depth = _copy_out(pd, n, np.float32, (rows, cols))
+        nrm = _copy_out(pn, 3 * n, np.float32, (rows, cols, 3)) if normals else None
+        rgb = _copy_out(pc, 3 * n, np.uint8, (rows, cols, 3)) if colors else None
         return depth, nrm, rgb
 
     def raycast_device(self, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, d_depth=0, d_normals=0, d_rgb=0):
@@ -792,13 +782,10 @@ class Engine:
                                                    C.byref(pp) if points else None))
         n = int(rows) * int(cols)
 
-        def arr(ptr, count, dt, shape):
-            return np.frombuffer((C.c_char * (count * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).reshape(shape).copy()
-
-        rng = arr(pd, n, np.float32, (rows, cols))
-        nrm = arr(pn, 3 * n, np.float32, (rows, cols, 3)) if normals else None
-        rgb = arr(pc, 3 * n, np.uint8, (rows, cols, 3)) if colors else None
-        pts = arr(pp, 3 * n, np.float32, (n, 3)) if points else None
+        rng = _copy_out(pd, n, np.float32, (rows, cols))
+        nrm = _copy_out(pn, 3 * n, np.float32, (rows, cols, 3)) if normals else None
+        rgb = _copy_out(pc, 3 * n, np.uint8, (rows, cols, 3)) if colors else None
+        pts = _copy_out(pp, 3 * n, np.float32, (n, 3)) if points else None
         return rng, nrm, rgb, pts
 
     def raycast_spherical_device(self, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, d_range=0, d_normals=0, d_rgb=0,
@@ -829,11 +816,8 @@ class Engine:
         self._check(self.lib.mrh_esdf(self._ctx, C.byref(p), C.byref(pd), C.byref(ps) if state else None, C.byref(pq) if squared else None))
         nx, ny, nz = (int(x) for x in dims)
         n = nx * ny * nz
-
-        def arr(ptr, dt):
-            return np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr.value), dtype=dt).reshape(nz, ny, nx).copy()
-
-        return arr(pd, np.float32), arr(ps, np.uint8) if state else None, arr(pq, np.uint32) if squared else None
+        box = (nz, ny, nx)
+        return _copy_out(pd, n, np.float32, box), _copy_out(ps, n, np.uint8, box) if state else None, _copy_out(pq, n, np.uint32, box) if squared else None
 
     def esdf_device(self, origin, dims, max_distance_voxels, surface_band=0.0, min_weight=0, d_dist=0, d_state=0, d_d2=0):
         """mrh_esdf_device: enqueues the field into caller device buffers (integer pointers, e.g. hipmem.DeviceBuffer.ptr:
@@ -910,9 +894,7 @@ class Engine:
         ptr, n, info = C.c_void_p(), C.c_uint64(), MrhNormalsInfo()
         self._check(self.lib.mrh_get_normals(self._ctx, C.byref(ptr), C.byref(n), C.byref(info)))
         k = int(n.value)
-        if k == 0:
-            return np.zeros((0, 3), np.float32), info.as_dict()
-        return np.frombuffer((C.c_char * (k * 12)).from_address(ptr.value), dtype=np.float32).reshape(k, 3).copy(), info.as_dict()
+        return _copy_out(ptr, 3 * k, np.float32, (k, 3)), info.as_dict()
 
     def get_voxel(self, vx: int, vy: int, vz: int):
         out = np.zeros(1, dtype=VOXEL_DTYPE)

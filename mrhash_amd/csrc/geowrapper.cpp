@@ -127,6 +127,9 @@ std::array<float, 16> pose_from(const std::array<float, 3>& t, const std::array<
           txz - twy, tyz + twx, 1.f - (txx + tyy), t[2],
           0.f, 0.f, 0.f, 1.f};
 }
+// a 4 x 4 row-major pose as the C ABI takes it: the rotation (row-major) and the translation
+struct PoseRt { float R[9], t[3]; };
+PoseRt split_pose(const std::array<float, 16>& T) { return {{T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]}, {T[3], T[7], T[11]}}; }
 }  // namespace
 
 void GeoWrapper::setCurrPose(const std::array<float, 3>& t, const std::array<float, 4>& q) { pose_ = pose_from(t, q); }
@@ -272,9 +275,8 @@ void GeoWrapper::compute() {
     check(mrh_peek_free_blocks(ctx_, &free_fine, nullptr, nullptr), "compute");
     if ((float) free_fine <= kStreamThreshold * (float) num_sdf_blocks_) stream(cam, reach_);
   }
-  const float R[9] = {pose_[0], pose_[1], pose_[2], pose_[4], pose_[5], pose_[6], pose_[8], pose_[9], pose_[10]};
-  const float t[3] = {pose_[3], pose_[7], pose_[11]};
-  check(mrh_set_pose(ctx_, R, t), "compute");
+  const PoseRt at = split_pose(pose_);
+  check(mrh_set_pose(ctx_, at.R, at.t), "compute");
   if (have_depth_ && have_rgb_) {  // geowrapper.cpp:140
     check(mrh_integrate(ctx_, n_frames_invalidate_voxels_), "compute");
     // The reference reports an exhausted pool / a full table from the device (printf, vds.cu:566-569) and carries on without
@@ -539,26 +541,39 @@ GeoWrapper::RaycastImages GeoWrapper::raycast() { return raycastPose(pose_); }
 
 GeoWrapper::RaycastImages GeoWrapper::raycast(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastPose(pose_from(t, q)); }
 
-mrh_raycast_params GeoWrapper::raycastParams(const uint32_t outputs) const {
-  mrh_raycast_params p;
+// intrinsics, image shape and depth range of the last setCamera into a zeroed parameter block (mrh_raycast_params, mrh_track_params):
+// every other field is left at 0, its default
+template <typename Params>
+Params GeoWrapper::cameraParams() const {
+  Params p;
   std::memset(&p, 0, sizeof p);
   p.fx = camera_fx_; p.fy = camera_fy_; p.cx = camera_cx_; p.cy = camera_cy_;
   p.rows = camera_rows_; p.cols = camera_cols_;
   p.min_depth = camera_min_depth_; p.max_depth = max_depth_;
-  p.step = 0.f;  // half the truncation
+  return p;
+}
+
+mrh_raycast_params GeoWrapper::raycastParams(const uint32_t outputs) const {
+  mrh_raycast_params p = cameraParams<mrh_raycast_params>();  // step 0: half the truncation
   p.outputs = outputs;
   return p;
 }
 
+// `method` needs the camera of a setCamera call, of the given model
+void GeoWrapper::requireCamera(const char* method, const int model) const {
+  const std::string who = std::string("GeoWrapper::") + method + " | ";
+  if (!has_camera_) throw std::runtime_error(who + "setCamera has not been called");
+  if (camera_model_ != model)
+    throw std::runtime_error(who + (model == MRH_CAMERA_PINHOLE ? "pinhole cameras only (the camera is spherical)" : "spherical cameras only (the camera is pinhole)"));
+}
+
 GeoWrapper::RaycastImages GeoWrapper::raycastPose(const std::array<float, 16>& pose) {
-  if (!has_camera_) throw std::runtime_error("GeoWrapper::raycast | setCamera has not been called");
-  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::raycast | pinhole cameras only (the camera is spherical)");
+  requireCamera("raycast", MRH_CAMERA_PINHOLE);
   const mrh_raycast_params p = raycastParams(MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS);
-  const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-  const float t[3] = {pose[3], pose[7], pose[11]};
+  const PoseRt at = split_pose(pose);
   const float *depth = nullptr, *normals = nullptr;
   const uint8_t* rgb = nullptr;
-  check(mrh_raycast(ctx_, &p, R, t, &depth, &normals, &rgb), "raycast");
+  check(mrh_raycast(ctx_, &p, at.R, at.t, &depth, &normals, &rgb), "raycast");
   RaycastImages out;
   out.rows = p.rows; out.cols = p.cols;
   const size_t n = (size_t) p.rows * (size_t) p.cols;
@@ -573,14 +588,12 @@ GeoWrapper::RaycastScan GeoWrapper::raycastScan() { return raycastScanPose(pose_
 GeoWrapper::RaycastScan GeoWrapper::raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastScanPose(pose_from(t, q)); }
 
 GeoWrapper::RaycastScan GeoWrapper::raycastScanPose(const std::array<float, 16>& pose) {
-  if (!has_camera_) throw std::runtime_error("GeoWrapper::raycastScan | setCamera has not been called");
-  if (camera_model_ != MRH_CAMERA_SPHERICAL) throw std::runtime_error("GeoWrapper::raycastScan | spherical cameras only (the camera is pinhole)");
+  requireCamera("raycastScan", MRH_CAMERA_SPHERICAL);
   const mrh_raycast_params p = raycastParams(MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS | MRH_RAYCAST_POINTS);
-  const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-  const float t[3] = {pose[3], pose[7], pose[11]};
+  const PoseRt at = split_pose(pose);
   const float *range = nullptr, *normals = nullptr, *points = nullptr;
   const uint8_t* rgb = nullptr;
-  check(mrh_raycast_spherical(ctx_, &p, R, t, &range, &normals, &rgb, &points), "raycastScan");
+  check(mrh_raycast_spherical(ctx_, &p, at.R, at.t, &range, &normals, &rgb, &points), "raycastScan");
   RaycastScan out;
   out.rows = p.rows; out.cols = p.cols;
   const size_t n = (size_t) p.rows * (size_t) p.cols;
@@ -653,24 +666,18 @@ std::array<float, 4> quat_from(const float R[9]) {
 
 // depth != nullptr: a depth image of the pinhole camera (D14); else the cloud pts [n * 3] against the spherical camera's render (D15)
 GeoWrapper::TrackResult GeoWrapper::trackPose(const char* who, const float* depth, const float* pts, size_t n, const std::array<float, 16>& pose) {
-  mrh_track_params p;
-  std::memset(&p, 0, sizeof p);  // step, dist_max, iterations, min_pixels: the defaults
-  p.fx = camera_fx_; p.fy = camera_fy_; p.cx = camera_cx_; p.cy = camera_cy_;
-  p.rows = camera_rows_; p.cols = camera_cols_;
-  p.min_depth = camera_min_depth_; p.max_depth = max_depth_;
-  const float R[9] = {pose[0], pose[1], pose[2], pose[4], pose[5], pose[6], pose[8], pose[9], pose[10]};
-  const float t[3] = {pose[3], pose[7], pose[11]};
+  const mrh_track_params p = cameraParams<mrh_track_params>();  // step, dist_max, iterations, min_pixels: the defaults
+  const PoseRt at = split_pose(pose);
   float out_R[9], out_t[3];
   TrackResult out;
-  check(depth ? mrh_track_depth(ctx_, &p, depth, R, t, out_R, out_t, &out.info) : mrh_track_scan(ctx_, &p, pts, n, R, t, out_R, out_t, &out.info), who);
+  check(depth ? mrh_track_depth(ctx_, &p, depth, at.R, at.t, out_R, out_t, &out.info) : mrh_track_scan(ctx_, &p, pts, n, at.R, at.t, out_R, out_t, &out.info), who);
   out.t = {out_t[0], out_t[1], out_t[2]};
   out.q = quat_from(out_R);
   return out;
 }
 
 GeoWrapper::TrackResult GeoWrapper::trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose) {
-  if (!has_camera_) throw std::runtime_error("GeoWrapper::trackDepthImage | setCamera has not been called");
-  if (camera_model_ != MRH_CAMERA_PINHOLE) throw std::runtime_error("GeoWrapper::trackDepthImage | pinhole cameras only (the camera is spherical)");
+  requireCamera("trackDepthImage", MRH_CAMERA_PINHOLE);
   if (!depth || rows != (size_t) camera_rows_ || cols != (size_t) camera_cols_)
     throw std::runtime_error("GeoWrapper::trackDepthImage | the depth image must have the camera's rows x cols");
   return trackPose("trackDepthImage", depth, nullptr, 0, pose);
@@ -683,8 +690,7 @@ GeoWrapper::TrackResult GeoWrapper::trackPointCloud(const float* pts, size_t n, 
 }
 
 GeoWrapper::TrackResult GeoWrapper::trackCloudPose(const float* pts, size_t n, const std::array<float, 16>& pose) {
-  if (!has_camera_) throw std::runtime_error("GeoWrapper::trackPointCloud | setCamera has not been called");
-  if (camera_model_ != MRH_CAMERA_SPHERICAL) throw std::runtime_error("GeoWrapper::trackPointCloud | spherical cameras only (the camera is a pinhole)");
+  requireCamera("trackPointCloud", MRH_CAMERA_SPHERICAL);
   if (!pts && n) throw std::runtime_error("GeoWrapper::trackPointCloud | no points");
   return trackPose("trackPointCloud", nullptr, pts, n, pose);
 }

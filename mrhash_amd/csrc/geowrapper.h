@@ -191,7 +191,9 @@ private:
   TrackResult trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose);
   TrackResult trackCloudPose(const float* pts, size_t n, const std::array<float, 16>& pose);
   TrackResult trackPose(const char* who, const float* depth, const float* pts, size_t n, const std::array<float, 16>& pose);
+  template <typename Params> Params cameraParams() const;    // intrinsics, shape and depth range of the last setCamera; the rest 0
   mrh_raycast_params raycastParams(uint32_t outputs) const;  // the camera of the last setCamera, step = half the truncation
+  void requireCamera(const char* method, int model) const;   // throws unless setCamera was called with that camera model
   bool has_camera_ = false;  // the camera of the last setCamera, for raycast()
   int camera_model_ = MRH_CAMERA_PINHOLE, camera_rows_ = 0, camera_cols_ = 0;
   float camera_fx_ = 0.f, camera_fy_ = 0.f, camera_cx_ = 0.f, camera_cy_ = 0.f, camera_min_depth_ = 0.f;

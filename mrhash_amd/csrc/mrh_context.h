@@ -1,6 +1,6 @@
 // mrh_context.h — the context (mrh_ctx) and its lifetime: what it holds, how it reports errors, what it owns (the ledger behind
 // dev_alloc / pinned_alloc / event_new), mrh_create's stages and free_all.  Included by mrh_capi.hip after the kernel headers and
-// before every host-path header (mrh_upload.h, mrh_extract.h, mrh_points.h, mrh_blocks.h, mrh_comm.h).  DESIGN.md 4.8.
+// before every host-path header (mrh_upload.h, mrh_extract.h, mrh_points.h, mrh_blocks.h, mrh_seeds.h, mrh_readers.h, mrh_comm.h).  DESIGN.md 4.8.
 #pragma once
 
 constexpr int kPipeRing = 6;  // = mrh::kListSets: frames in flight + 2
@@ -317,21 +317,23 @@ struct mrh_ctx {
     u32 buckets_seq = 0;
     size_t buckets_lds_set = 0;
   } lidar;
-  // 3DGS splat seeds (mrh_splat.h): sized for one (image shape, min pixel size)
-  size_t qt_cap = 0;  // potential nodes the device buffers below hold (regrow_all); it replaces the QTree once recorded here
-  QSum* d_qt_sums = nullptr; u32* d_qt_flags = nullptr; u32* d_qt_unc = nullptr; u64* d_qt_marks = nullptr; u64* d_qt_pos = nullptr;
-  mrh_splat_seed* d_qt_parked = nullptr; mrh_qtree_leaf* d_qt_leaves = nullptr;
-  // what the caller takes from a seeding call is written by its last launch straight into pinned host memory (a few hundred to a few
-  // thousand 20-byte seeds and two counters): one synchronisation, no transfer calls (they were two pageable read-backs, each behind
-  // a synchronisation of its own: ~35 of the call's 135 us)
-  mrh_splat_seed* h_qt_seeds = nullptr; size_t qt_seed_cap = 0;
-  u64* h_qt_out = nullptr;   // [0] totals (leaves | seeds << 32), [1] literal evaluations
-  u64* d_qt_misc = nullptr;  // [0] totals (leaves | seeds << 32), [1] uncertain-node counter (low word)
-  int qt_literal = 0;        // MRH_QTREE_LITERAL=1: every node error through the reference's summation order (cross-check)
-  uint32_t qt_last_literal = 0;
-  std::vector<mrh_qtree_leaf> qt_leaves;
-  uint64_t qt_n_leaves = 0;            // leaves of the last mrh_splat_seeds, still on the device (d_qt_leaves) until someone asks
-  bool qt_leaves_on_host = true;
+  // 3DGS splat seeds (mrh_seeds.h, kernels in mrh_splat.h): sized for one (image shape, min pixel size)
+  struct Seeds {
+    size_t cap = 0;  // potential nodes the device buffers below hold (regrow_all); it replaces the QTree once recorded here
+    QSum* d_sums = nullptr; u32* d_flags = nullptr; u32* d_unc = nullptr; u64* d_marks = nullptr; u64* d_pos = nullptr;
+    mrh_splat_seed* d_parked = nullptr; mrh_qtree_leaf* d_leaves = nullptr;
+    // what the caller takes from a seeding call is written by its last launch straight into pinned host memory (a few hundred to a few
+    // thousand 20-byte seeds and two counters): one synchronisation, no transfer calls (they were two pageable read-backs, each behind
+    // a synchronisation of its own: ~35 of the call's 135 us)
+    mrh_splat_seed* h_seeds = nullptr; size_t seed_cap = 0;
+    u64* h_out = nullptr;   // [0] totals (leaves | seeds << 32), [1] literal evaluations
+    u64* d_misc = nullptr;  // [0] totals (leaves | seeds << 32), [1] uncertain-node counter (low word)
+    int literal = 0;        // MRH_QTREE_LITERAL=1: every node error through the reference's summation order (cross-check)
+    uint32_t last_literal = 0;
+    std::vector<mrh_qtree_leaf> leaves;
+    uint64_t n_leaves = 0;            // leaves of the last mrh_splat_seeds, still on the device (d_leaves) until someone asks
+    bool leaves_on_host = true;
+  } qt;
   int mr_fused = 1;          // MRH_MR_FUSED=0: multi-resolution maps always through the general kernels (mrh_kernels.h)
   bool mr_next_general = true;    // the next multi-resolution frame must take the general path (frame 0 / after a starve frame / after an import)
   bool mr_summaries_valid = false;  // fast.summary / summary_c describe every live block (the general kernels do not maintain them)
@@ -418,28 +420,30 @@ struct mrh_ctx {
   hipEvent_t comm_ev[5] = {};
   mrh_comm_phases comm_phases = {};
   std::vector<EvPair> comm_ev_pool, comm_ev_pending;
-  // raycasting (mrh_raycast.h): the images of mrh_raycast and mrh_raycast_spherical, grow-only — device [depth f32 | normals
-  // 3 x f32 | points 3 x f32 | rgb 3 x u8] per pixel and the pinned host copy the caller reads
-  char* d_ray = nullptr; size_t ray_cap = 0;  // pixels
-  char* h_ray = nullptr; size_t h_ray_cap = 0;
-  // distance fields (mrh_esdf.h), grow-only, in cells — scratch of every call: the state byte, the x pass's |dx| (u16: at most 511)
+  // raycasting (mrh_readers.h, kernels in mrh_raycast.h): the images of mrh_raycast and mrh_raycast_spherical, grow-only — device
+  // [depth f32 | normals 3 x f32 | points 3 x f32 | rgb 3 x u8] per pixel and the pinned host copy the caller reads
+  struct Ray {
+    char* d_img = nullptr; size_t cap = 0;  // pixels
+    char* h_img = nullptr; size_t h_cap = 0;
+  } ray;
+  // distance fields (mrh_readers.h, kernels in mrh_esdf.h), grow-only, in cells — scratch of every call: the state byte, the x pass's |dx| (u16: at most 511)
   // and the y pass's u32 plane; results of mrh_esdf: dist and d2 on the device and the pinned [dist f32 | d2 u32 | state u8] the caller reads
   struct Esdf {
     uint8_t* d_state = nullptr; uint16_t* d_row = nullptr; u32* d_plane = nullptr; size_t cap = 0;
     float* d_dist = nullptr; u32* d_d2 = nullptr; size_t out_cap = 0;
     char* h_out = nullptr; size_t h_cap = 0;
   } esdf;
-  // depth-frame tracking (mrh_track.h), grow-only — device [model depth f32 | model normals 3 x f32 | the caller's depth f32] per
-  // pixel and the partial slab (one row of 32 words per workgroup); pinned: the staged depth image and the 32 sums the host reads.
-  // Scan tracking (D15) keeps the model's range and normals in d_img too and adds the model's points image and the staged cloud
+  // tracking (mrh_readers.h, kernels in mrh_track.h), grow-only — device [model depth or range f32 | model normals 3 x f32] per
+  // pixel, for scans (D15) the model's points image, and the partial slab (one row of 32 words per workgroup); pinned: the 32 sums
+  // the host reads.  An observation that comes from the host — a depth image (D14) or a cloud — is staged through one pair of
+  // buffers, pinned and device (stage_obs)
   struct Track {
     char* d_img = nullptr; size_t cap = 0;           // pixels
     long long* d_slab = nullptr; size_t slab_cap = 0;  // rows
-    float* h_depth = nullptr; size_t h_cap = 0;      // pixels
     long long* h_sums = nullptr;
     float* d_mp = nullptr; size_t mp_cap = 0;        // pixels, 3 x f32 each
-    float* d_cloud = nullptr; size_t cloud_cap = 0;  // points, 3 x f32 each
-    float* h_cloud = nullptr; size_t h_cloud_cap = 0;  // points
+    float* h_obs = nullptr; size_t h_obs_cap = 0;    // floats
+    float* d_obs = nullptr; size_t obs_cap = 0;      // floats
   } trk;
   // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of
   // every point, grow-only; two sets of counters, a scan's last launch zeroes the next one's
@@ -802,7 +806,7 @@ void read_switches(mrh_ctx* c) {
   env_onoff("MRH_MESH_HOST", c->mesh_on_host);
   env_onoff("MRH_MESH_F64_LINK", c->f64_link);
   c->V.pin = c->C.pin = c->f64_link;  // fp32 link: the doubles are written by the host only
-  env_onoff("MRH_QTREE_LITERAL", c->qt_literal);
+  env_onoff("MRH_QTREE_LITERAL", c->qt.literal);
   env_int("MRH_SCAN_ROW_LEN", -kIntMax - 1, kIntMax, c->lidar.layout_hint);
   env_int("MRH_SCAN_PATCH_LOG2", 0, 8, c->lidar.patch_log2);
   env_onoff("MRH_LIDAR_BUCKETS", c->lidar.use_buckets);

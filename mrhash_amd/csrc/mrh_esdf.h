@@ -12,6 +12,7 @@
 #pragma once
 
 #include "mrh_mc.h"
+#include "mrh_readerplan.h"  // EsdfBox
 
 namespace mrh {
 
@@ -22,14 +23,6 @@ constexpr u32 kEsdfFar = 0xFFFFFFFFu;          // d2 of a `far` cell
 constexpr int kEsdfTile = 32;                  // columns (adjacent in x) a workgroup of the column passes owns
 constexpr int kEsdfColumnLanes = 8;            // lanes that share one column (256 / kEsdfTile)
 enum EsdfState : u32 { ESDF_OBSERVED = 1u, ESDF_SITE = 2u, ESDF_INSIDE = 4u, ESDF_FAR = 8u };
-
-struct EsdfBox {
-  int ox, oy, oz;   // origin, finest voxels
-  int nx, ny, nz;   // 1 .. 512 each
-  u32 reach;        // R, 1 .. 4095 voxels
-  int w_min;        // observed: weight >= w_min (>= 1)
-  float band;       // site: |sdf| <= band; 0 = one voxel of the block's own resolution
-};
 
 __device__ __forceinline__ size_t esdf_cell(const EsdfBox& bx, const int i, const int j, const int k) {
   return ((size_t) k * (size_t) bx.ny + (size_t) j) * (size_t) bx.nx + (size_t) i;

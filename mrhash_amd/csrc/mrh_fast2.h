@@ -521,7 +521,7 @@ __device__ __forceinline__ bool variance_says_coarsen(const Map& m, const uint2*
 //         and, if the reference would coarsen it, converted on the spot (checkVarSDF -> reallocBlocks ->
 //         reintegrateDepthMap, vds.cu:1857-2107): same table slot, new coarse unit, fine slot zeroed and released
 // ---- lazy garbage collection of pipelined frames ---------------------------------------------------------------------
-// A pipelining context (mrh_capi.hip: integrate_lazy) launches the FRONT half of frame g + 1 (k_front<..., LAZY>: rays, probes,
+// A pipelining context (mrh_frame.h: integrate_single_res_frame) launches the FRONT half of frame g + 1 (k_front<..., LAZY>: rays, probes,
 // inserts, sweep) on a second stream, where it runs next to the integration of frame g (k_back<..., LZ = 2>) — and possibly of
 // frame g - 1 — instead of behind it.  A block that a frame's garbage collection empties can therefore not leave the table in
 // that launch: erasing a key would break the invariant the lock-free insert rests on (an occupied slot stays occupied while

@@ -642,7 +642,7 @@ __global__ __launch_bounds__(256) void k_count_live(const Tab t) {
 // table maintenance.  Erasing from an open-address table leaves a tombstone (the reference's buckets return the slot to
 // FREE, vds.cu:1727-1824), and GC frees and re-creates the free-space blocks of the truncation band every frame: without
 // upkeep the never-used slots only get fewer, and a lookup of an absent key — 27 per block in k_mc, one per tile key in
-// k_front — walks ever longer runs.  Every few dozen frames (mrh_capi.hip: maintain_table) a census counts the tombstones;
+// k_front — walks ever longer runs.  Every few dozen frames (mrh_frame.h: maintain_table) a census counts the tombstones;
 // above a quarter of the slots (or when a key was left without storage) the key array is cleared and rebuilt from the dense
 // block descriptors: O(live blocks), between two frames, no host round trip — the decision stays on the device.
 // =====================================================================================================

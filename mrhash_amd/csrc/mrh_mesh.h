@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kMeshTile) void k_mesh_vertex_rep(const float* __re
 }
 
 // T = float: V and C leave the device as the fp32 values marching cubes computed (the host widens them while the link is still
-// busy, mrh_extract.h: k_stage_out; mrh_capi.hip: widen_from_staging); T = double: widened here (MRH_MESH_F64_LINK=1, the round-3 path)
+// busy, mrh_extract.h: k_stage_out; mrh_hostcopy.h: widen_from_staging); T = double: widened here (MRH_MESH_F64_LINK=1, the round-3 path)
 template <typename T>
 __global__ __launch_bounds__(256) void k_mesh_emit_vertices(const float* __restrict__ soup, const u32* __restrict__ rep,
                                                             const u32* __restrict__ vloc, const u32* __restrict__ toff, const u32 n,

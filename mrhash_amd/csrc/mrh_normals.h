@@ -17,6 +17,7 @@
 #pragma once
 
 #include "mrh_device.h"
+#include "mrh_readerplan.h"  // NrmPar
 
 namespace mrh {
 
@@ -38,13 +39,6 @@ struct NrmTab {
   u64* ctr;       // NC_N counters of THIS scan
   u64* ctr_next;  // ... of the next one: zeroed by k_normals_sweep
   u32 mask;
-};
-
-struct NrmPar {
-  float rho;          // cell side (metres)
-  u32 min_points;     // gate: points in the 27 cells
-  double min_l1;      // gate: (1024 min_spread)^2, units of (rho / 1024)^2
-  double max_flat;    // gate: lambda0 <= max_flat * lambda1
 };
 
 __device__ __forceinline__ u32 nrm_hash(const u64 key, const u32 mask) {

@@ -2,9 +2,11 @@
 // mrh_upload_normals, mrh_set_scan_layout / mrh_detect_scan_layout) and mrh_integrate_points, a driver over named stages that
 // takes a scan through one of two record paths — the voxel buckets (kernels in mrh_scan.h) or, where their scratch does not fit,
 // the voxel ids need 64-bit keys, a beam is too long or MRH_LIDAR_BUCKETS=0 says so, the sorted records (kernels in mrh_lidar.h,
-// the sort in mrh_sort.h).  The state is mrh_ctx::lidar.  Included by mrh_capi.hip, same translation unit: it needs the context's
-// internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all, ensure_ready, launch_compact_all, mark_frame and, from
-// mrh_frame.h, frame_upkeep, refill_coarse, plan_begin, starve_and_tail).
+// the sort in mrh_sort.h).  At the end, the normals of a scan: mrh_estimate_normals[_device] and mrh_get_normals (kernels in
+// mrh_normals.h, the argument plan in mrh_readerplan.h).  The state is mrh_ctx::lidar, the normals' scratch and counts mrh_ctx::nrm.
+// Included by mrh_capi.hip, same translation unit: it needs the context's internals (mrh_ctx, HIP_TRY, fail, dev_alloc, pinned_alloc,
+// regrow / regrow_all / regrow_pinned, ensure_device, ensure_ready, launch_compact_all, mark_frame and, from mrh_frame.h,
+// frame_upkeep, refill_coarse, plan_begin, starve_and_tail).
 #pragma once
 
 namespace {
@@ -429,6 +431,145 @@ int mrh_integrate_points(mrh_ctx* c, int n_frames_invalidate) {
     if (mrc) return mrc;
   }
   return rc;
+}
+
+}  // extern "C"
+
+// ---- scan normals (include/mrhash_normals.h; kernels in mrh_normals.h): they act on the cloud above.  State: mrh_ctx::nrm -------------
+namespace {
+
+// the parameter block with its defaults filled in, as the kernels take it (mrh_readerplan.h)
+int normals_args(mrh_ctx* c, const char* who, const mrh_normals_params* p, const uint64_t n, NrmPar* out) {
+  char msg[mrh_plan::kMsgBytes];
+  const int rc = mrh_plan::normals(msg, who, p, n, c->p.virtual_voxel_size, out);
+  return rc ? fail(c, rc, "%s", msg) : MRH_OK;
+}
+
+// scratch for n points: grown to the next power of two, born clean
+int normals_scratch(mrh_ctx* c, const uint64_t n) {
+  auto& N = c->nrm;
+  hipStream_t s = c->stream;
+  if (!N.d_ctr) {
+    HIP_TRY(c, dev_alloc(c, N.d_ctr, 2 * NC_N * sizeof(u64)));
+    HIP_TRY(c, hipMemsetAsync(N.d_ctr, 0, 2 * NC_N * sizeof(u64), s));
+  }
+  if (n > N.cap) {
+    const size_t cap = (size_t) next_pow2(std::max<uint64_t>(n, 512)), slots = 2 * cap;
+    NrmTab& t = N.tab;
+    const int rc = regrow_all(c, N.cap, cap, {{t.keys, slots * sizeof(u64)}, {t.sums, slots * kNrmSums * sizeof(u64)}, {t.cell, slots * sizeof(float4)},
+                                              {t.list, cap * sizeof(u32)}, {t.pt_slot, cap * sizeof(u32)}, {t.partial, (cap / 256 + 1) * 3 * sizeof(u32)}});
+    if (rc) return rc;
+    t.mask = (u32) (slots - 1);
+    N.dirty = true;
+  }
+  if (N.dirty) {
+    const size_t slots = (size_t) N.tab.mask + 1;
+    HIP_TRY(c, hipMemsetAsync(N.tab.keys, 0xFF, slots * sizeof(u64), s));
+    HIP_TRY(c, hipMemsetAsync(N.tab.sums, 0, slots * kNrmSums * sizeof(u64), s));
+    HIP_TRY(c, hipMemsetAsync(N.d_ctr, 0, 2 * NC_N * sizeof(u64), s));
+    N.dirty = false;
+  }
+  return MRH_OK;
+}
+
+// The four launches of one scan, n > 0.  *out_ctr: this scan's counters on the device, valid until the scan after the next
+int launch_normals(mrh_ctx* c, const NrmPar& par, const float* d_xyz, const uint64_t n, float* d_nxyz, const u64** out_ctr) {
+  int rc = normals_scratch(c, n);
+  if (rc) return rc;
+  auto& N = c->nrm;
+  hipStream_t s = c->stream;
+  NrmTab t = N.tab;
+  const u32 set = ++N.seq & 1u;
+  t.ctr = N.d_ctr + set * NC_N;
+  t.ctr_next = N.d_ctr + (set ^ 1u) * NC_N;
+  const u32 np = (u32) n, grid = (np + 255u) / 256u;
+  N.dirty = true;
+  if (N.fold) k_normals_accumulate<true><<<grid, 256, 0, s>>>(t, par, d_xyz, np);
+  else k_normals_accumulate<false><<<grid, 256, 0, s>>>(t, par, d_xyz, np);
+  k_normals_solve<<<std::min<u32>(1024u, (np + kNrmSolveCells - 1) / kNrmSolveCells), 1024, 0, s>>>(t, par);
+  k_normals_assign<<<grid, 256, 0, s>>>(t, d_xyz, np, d_nxyz);
+  k_normals_sweep<<<std::min<u32>(1024u, grid), 256, 0, s>>>(t, grid);
+  HIP_TRY(c, hipGetLastError());
+  N.dirty = false;
+  *out_ctr = t.ctr;
+  return MRH_OK;
+}
+
+// the counters of the last mrh_estimate_normals have landed in pinned memory (the caller synchronised): into Normals::info
+void normals_fold_info(mrh_ctx* c) {
+  auto& N = c->nrm;
+  if (!N.info_pending) return;
+  N.info.estimated = N.h_ctr[NC_ESTIMATED]; N.info.fallback = N.h_ctr[NC_FALLBACK];
+  N.info.missing = N.h_ctr[NC_MISSING]; N.info.cells = N.h_ctr[NC_CELLS];
+  N.info_pending = false;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrh_estimate_normals_device(mrh_ctx* c, const mrh_normals_params* p, const float* d_xyz, uint64_t n, float* d_nxyz) {
+  int rc = ensure_device(c, "mrh_estimate_normals_device");
+  if (rc) return rc;
+  if (n && (!d_xyz || !d_nxyz)) return fail(c, MRH_ERR_INVALID_ARG, "mrh_estimate_normals_device: null argument");
+  NrmPar par;
+  rc = normals_args(c, "mrh_estimate_normals_device", p, n, &par);
+  if (rc || n == 0) return rc;
+  const u64* ctr;
+  return launch_normals(c, par, d_xyz, n, d_nxyz, &ctr);
+}
+
+int mrh_estimate_normals(mrh_ctx* c, const mrh_normals_params* p, mrh_normals_info* out_info) {
+  int rc = ensure_device(c, "mrh_estimate_normals");
+  if (rc) return rc;
+  auto& L = c->lidar;
+  auto& N = c->nrm;
+  if (!L.have_cloud) return fail(c, MRH_ERR_STATE, "mrh_estimate_normals: no current scan (mrh_upload_points / mrh_set_points_device)");
+  const uint64_t n = L.num_points;
+  NrmPar par;
+  rc = normals_args(c, "mrh_estimate_normals", p, n, &par);
+  if (rc) return rc;
+  if (!N.h_ctr) {
+    HIP_TRY(c, pinned_alloc(c, N.h_ctr, NC_N * sizeof(u64)));
+    memset(N.h_ctr, 0, NC_N * sizeof(u64));
+  }
+  L.num_normals = 0;  // none valid from the moment the buffer may change
+  rc = regrow(c, L.d_normals, L.normals_cap, (size_t) n, (size_t) n * 3 * sizeof(float));
+  if (rc) return rc;
+  N.info = {};
+  N.info.points = n;
+  N.info_pending = false;
+  if (n) {
+    const u64* ctr;
+    rc = launch_normals(c, par, L.d_points_cur, n, L.d_normals, &ctr);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(N.h_ctr, ctr, NC_N * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+    N.info_pending = true;
+  }
+  L.num_normals = n;
+  if (out_info) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    normals_fold_info(c);
+    *out_info = N.info;
+  }
+  return MRH_OK;
+}
+
+int mrh_get_normals(mrh_ctx* c, const float** out_nxyz, uint64_t* out_n, mrh_normals_info* out_info) {
+  int rc = ensure_device(c, "mrh_get_normals");
+  if (rc) return rc;
+  if (!out_nxyz || !out_n) return fail(c, MRH_ERR_INVALID_ARG, "mrh_get_normals: null argument");
+  auto& L = c->lidar;
+  auto& N = c->nrm;
+  const size_t n = L.num_normals;
+  if ((rc = regrow_pinned(c, N.h_out, N.h_out_cap, n, n * 3 * sizeof(float)))) return rc;
+  if (n) HIP_TRY(c, hipMemcpyAsync(N.h_out, L.d_normals, n * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  normals_fold_info(c);
+  *out_nxyz = N.h_out;
+  *out_n = n;
+  if (out_info) *out_info = N.info;
+  return MRH_OK;
 }
 
 }  // extern "C"

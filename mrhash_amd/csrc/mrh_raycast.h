@@ -13,20 +13,13 @@
 #pragma once
 
 #include "mrh_mc.h"
+#include "mrh_readerplan.h"  // RayCam
 
 namespace mrh {
 
 constexpr int kRenderTile = 16;                 // pixels per side of a workgroup's tile
 constexpr int kRayBisections = 3;               // n_iteration_bisection (params.h:26)
 constexpr float kRaySkipReachVoxels = 65000.f;  // rays that stay within this many voxels of the origin may jump (see ray_skip_absent)
-
-struct RayCam {
-  float ifx, ify, cx, cy;  // ifx = 1 / fx, ify = 1 / fy (host, IEEE)
-  int rows, cols;
-  float min_depth, max_depth, step;
-  u32 n_samples;           // samples z_k <= max_depth, validated on the host: 1 .. 2^20
-  float R[9], t[3];        // camera in world (row-major R)
-};
 
 // z_k, computed afresh for every k (never accumulated)
 __device__ __forceinline__ float ray_z(const RayCam& rc, const u32 k) { return rc.min_depth + (float) k * rc.step; }

@@ -1,0 +1,198 @@
+// mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking)
+// and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
+// parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
+// the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
+// structs, mrh_capi.hip for the plans, and tests/host/readerplan_check.cpp compiles it on its own.  Built with -ffp-contract=off
+// like everything else.  The order of the checks is part of the contract: null block, pending exchange, sharded
+// context, then the limits in the order written.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/mrh_softmath.h"
+#include "../../include/mrhash_esdf.h"
+#include "../../include/mrhash_normals.h"
+#include "../../include/mrhash_track.h"
+
+namespace mrh {
+
+// k_raycast's camera (mrh_raycast.h)
+struct RayCam {
+  float ifx, ify, cx, cy;  // ifx = 1 / fx, ify = 1 / fy (host, IEEE)
+  int rows, cols;
+  float min_depth, max_depth, step;
+  uint32_t n_samples;      // samples z_k <= max_depth, validated on the host: 1 .. 2^20
+  float R[9], t[3];        // camera in world (row-major R)
+};
+
+// the box of the distance-field kernels (mrh_esdf.h)
+struct EsdfBox {
+  int ox, oy, oz;   // origin, finest voxels
+  int nx, ny, nz;   // 1 .. 512 each
+  uint32_t reach;   // R, 1 .. 4095 voxels
+  int w_min;        // observed: weight >= w_min (>= 1)
+  float band;       // site: |sdf| <= band; 0 = one voxel of the block's own resolution
+};
+
+// the parameters of the normal-estimation kernels (mrh_normals.h), defaults filled in
+struct NrmPar {
+  float rho;            // cell side (metres)
+  uint32_t min_points;  // gate: points in the 27 cells
+  double min_l1;        // gate: (1024 min_spread)^2, units of (rho / 1024)^2
+  double max_flat;      // gate: lambda0 <= max_flat * lambda1
+};
+
+}  // namespace mrh
+
+namespace mrh_plan {
+namespace {  // internal to whoever includes the header, like mrh_xplan.h: the library exports none of it
+
+constexpr size_t kMsgBytes = 512;  // = fail()'s buffer: a message passes through it unchanged
+
+// fail() without a context: formats into msg[kMsgBytes] and returns the code
+inline int refuse(char* msg, const int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, kMsgBytes, fmt, ap);
+  va_end(ap);
+  return code;
+}
+
+// What every reader needs of the map before its own limits: no exchange pending, one shard.  `lacks`: what a sharded map does not
+// get from this feature, in the feature's own words
+inline int whole_map(char* msg, const char* who, const char* lacks, const int pending, const int shard_count) {
+  if (pending) return refuse(msg, MRH_ERR_STATE, "%s: an exchange is pending (call mrh_integrate_resume)", who);
+  if (shard_count > 1) return refuse(msg, MRH_ERR_UNSUPPORTED, "%s: sharded maps %s (shard_count %d)", who, lacks, shard_count);
+  return MRH_OK;
+}
+
+inline float ray_z_host(const float min_depth, const float step, const uint32_t k) { return min_depth + (float) k * step; }  // = ray_z (mrh_raycast.h)
+
+// the arguments every raycast entry point shares (and tracking, through its model render); fills the kernel's camera.
+// model: MRH_CAMERA_*; truncation: the context's sdf_truncation, for the default step
+inline int raycast(char* msg, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, const float truncation,
+                   const int pending, const int shard_count, mrh::RayCam* rc) {
+  if (!p || !R || !t) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = whole_map(msg, who, "are not rendered", pending, shard_count)) return e;
+  if (p->rows < 1 || p->rows > MRH_RAYCAST_MAX_SIDE || p->cols < 1 || p->cols > MRH_RAYCAST_MAX_SIDE)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: image of %d x %d pixels (1 .. %d per side)", who, p->rows, p->cols, MRH_RAYCAST_MAX_SIDE);
+  if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || p->fx == 0.f || p->fy == 0.f || !std::isfinite(p->cx) || !std::isfinite(p->cy))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: bad intrinsics", who);
+  if (!(p->min_depth > 0.f) || !(p->max_depth > p->min_depth) || !std::isfinite(p->max_depth))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: need 0 < min_depth < max_depth (got %g, %g)", who, (double) p->min_depth, (double) p->max_depth);
+  const uint32_t known = MRH_RAYCAST_NORMALS | MRH_RAYCAST_COLORS | (model == MRH_CAMERA_SPHERICAL ? MRH_RAYCAST_POINTS : 0u);
+  if (p->outputs & ~known) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  const float step = p->step == 0.f ? 0.5f * truncation : p->step;
+  if (!(step > 0.f) || !std::isfinite(step)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  // samples z_k <= max_depth: z_k is monotone in k (two monotone roundings), so the count is found by bisection on k
+  if (ray_z_host(p->min_depth, step, MRH_RAYCAST_MAX_SAMPLES) <= p->max_depth)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: more than 2^20 samples per ray (min_depth %g, max_depth %g, step %g)", who, (double) p->min_depth,
+                  (double) p->max_depth, (double) step);
+  uint32_t lo = 0, hi = MRH_RAYCAST_MAX_SAMPLES;  // z(lo) <= max_depth < z(hi)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (ray_z_host(p->min_depth, step, mid) <= p->max_depth) lo = mid;
+    else hi = mid;
+  }
+  rc->ifx = 1.0f / p->fx;
+  rc->ify = 1.0f / p->fy;
+  rc->cx = p->cx; rc->cy = p->cy;
+  rc->rows = p->rows; rc->cols = p->cols;
+  if (model == MRH_CAMERA_SPHERICAL) {
+    // every pixel's azimuth and elevation within the range mrh_sincosf is specified on: the kernel's expressions (ray_dir_sensor)
+    // at the corner pixels — they are monotone in the column and in the row, so the corners bound every pixel
+    const float az0 = rc->ifx * (((float) 0 - rc->cx) - 0.5f), az1 = rc->ifx * (((float) (rc->cols - 1) - rc->cx) - 0.5f);
+    const float el0 = rc->ify * (((float) 0 - rc->cy) - 0.5f), el1 = rc->ify * (((float) (rc->rows - 1) - rc->cy) - 0.5f);
+    const float worst = std::fmax(std::fmax(std::fabs(az0), std::fabs(az1)), std::fmax(std::fabs(el0), std::fabs(el1)));
+    if (!(worst <= MRH_SM_SINCOS_MAX))
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a pixel's azimuth or elevation reaches %g rad (sine and cosine are specified up to %g)", who,
+                    (double) worst, (double) MRH_SM_SINCOS_MAX);
+  }
+  rc->min_depth = p->min_depth; rc->max_depth = p->max_depth; rc->step = step;
+  rc->n_samples = hi;
+  for (int i = 0; i < 9; i++) rc->R[i] = R[i];
+  for (int i = 0; i < 3; i++) rc->t[i] = t[i];
+  return MRH_OK;
+}
+
+// the arguments both distance-field entry points share; fills the kernels' box.  min_weight_threshold: the context's, the default of w_min
+inline int esdf(char* msg, const char* who, const mrh_esdf_params* p, const int min_weight_threshold, const int pending, const int shard_count,
+                mrh::EsdfBox* bx) {
+  if (!p) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = whole_map(msg, who, "have no distance field", pending, shard_count)) return e;
+  for (int a = 0; a < 3; a++) {
+    if (p->dims[a] < 1 || p->dims[a] > MRH_ESDF_MAX_SIDE)
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: box of %d x %d x %d cells (1 .. %d per side)", who, p->dims[0], p->dims[1], p->dims[2], MRH_ESDF_MAX_SIDE);
+    const int64_t lo = p->origin[a], hi = lo + p->dims[a] - 1;
+    if (lo < -(1ll << 23) || hi >= (1ll << 23))
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: axis %d of the box spans voxels %lld .. %lld, outside [-2^23, 2^23)", who, a, (long long) lo, (long long) hi);
+  }
+  if (p->max_distance_voxels < 1 || p->max_distance_voxels > MRH_ESDF_MAX_REACH)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: max_distance_voxels %d (1 .. %d)", who, p->max_distance_voxels, MRH_ESDF_MAX_REACH);
+  if (!std::isfinite(p->surface_band) || p->surface_band < 0.f) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: surface_band %g", who, (double) p->surface_band);
+  if (p->min_weight < 0) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: min_weight %d", who, p->min_weight);
+  if (p->outputs & ~(MRH_ESDF_STATE | MRH_ESDF_SQUARED)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  bx->ox = p->origin[0]; bx->oy = p->origin[1]; bx->oz = p->origin[2];
+  bx->nx = p->dims[0]; bx->ny = p->dims[1]; bx->nz = p->dims[2];
+  bx->reach = (uint32_t) p->max_distance_voxels;
+  bx->w_min = std::max(1, p->min_weight ? p->min_weight : min_weight_threshold);
+  bx->band = p->surface_band;
+  return MRH_OK;
+}
+
+// One tracking call with its defaults filled in: the model render's camera, the gate, the iteration count, the fewest pixels
+struct Track {
+  mrh::RayCam cam;
+  float dist_max;
+  int iterations;
+  uint32_t min_pixels;
+};
+// model: MRH_CAMERA_PINHOLE (a depth image) or MRH_CAMERA_SPHERICAL (a scan of n points); have_obs: the image or the cloud was
+// given (an empty scan needs none); have_out: both pose outputs were
+inline int track(char* msg, const char* who, const int model, const mrh_track_params* p, const bool have_obs, const size_t n, const bool have_out,
+                 const float* R0, const float* t0, const float truncation, const int pending, const int shard_count, Track* out) {
+  const bool scan = model == MRH_CAMERA_SPHERICAL;
+  if (!p || (!have_obs && !(scan && n == 0)) || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (scan && n > ((size_t) 1 << 24)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %zu points in one scan (limit 2^24)", who, n);
+  const mrh_raycast_params rp = {p->fx, p->fy, p->cx, p->cy, p->rows, p->cols, p->min_depth, p->max_depth, p->step,
+                                 MRH_RAYCAST_NORMALS | (scan ? MRH_RAYCAST_POINTS : 0u)};
+  if (const int e = raycast(msg, who, model, &rp, R0, t0, truncation, pending, shard_count, &out->cam)) return e;
+  out->dist_max = p->dist_max == 0.f ? std::fmin(2.f * truncation, 1.f) : p->dist_max;
+  if (!(out->dist_max > 0.f && out->dist_max <= 1.f))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the gate must lie in (0, 1] m (dist_max %g)", who, (double) out->dist_max);
+  if (p->iterations < 0 || p->iterations > MRH_TRACK_MAX_ITERATIONS)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %d iterations (1 .. %d, 0 = 10)", who, p->iterations, MRH_TRACK_MAX_ITERATIONS);
+  out->iterations = p->iterations ? p->iterations : 10;
+  out->min_pixels = p->min_pixels ? p->min_pixels : 64u;
+  return MRH_OK;
+}
+
+// the normals' parameter block (null: every default) with its defaults filled in, as the kernels take it.  n: points of the scan;
+// voxel_size: the context's virtual_voxel_size, for the default cell side
+inline int normals(char* msg, const char* who, const mrh_normals_params* p, const uint64_t n, const float voxel_size, mrh::NrmPar* out) {
+  mrh_normals_params q = {0.f, 0u, 0.f, 0.f};
+  if (p) q = *p;
+  auto bad = [](float v) { return !(v >= 0.f) || !std::isfinite(v); };
+  if (bad(q.radius) || bad(q.min_spread) || bad(q.max_flatness) || q.max_flatness >= 1.f)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: bad parameter (radius %g, min_spread %g, max_flatness %g)", who, (double) q.radius, (double) q.min_spread, (double) q.max_flatness);
+  if (n >= (1ull << 24)) return refuse(msg, MRH_ERR_CAPACITY, "%s: %llu points in one scan (limit 2^24 - 1)", who, (unsigned long long) n);
+  out->rho = q.radius == 0.f ? 2.0f * voxel_size : q.radius;
+  if (!(out->rho > 0.f) || !std::isfinite(out->rho)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the cell side must be > 0 (radius %g)", who, (double) out->rho);
+  out->min_points = q.min_points == 0u ? 5u : q.min_points;
+  const double spread = 1024.0 * (q.min_spread == 0.f ? 0.0625 : (double) q.min_spread);
+  out->min_l1 = spread * spread;
+  out->max_flat = q.max_flatness == 0.f ? 0.0625 : (double) q.max_flatness;
+  return MRH_OK;
+}
+
+}  // namespace
+}  // namespace mrh_plan

@@ -1,0 +1,316 @@
+// mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
+// [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h) and tracking (mrh_track_depth / _scan
+// [_device], mrh_track.h; the solve is mrh_tracksolve.h).  What they share is here once: the way in (reader_enter: null context,
+// the feature's argument plan from mrh_readerplan.h, ensure_ready) and the way the blocking calls hand their result planes out of
+// pinned memory (read_planes).  The state is mrh_ctx::ray, ::esdf and ::trk.  Included by mrh_capi.hip, same translation unit: it
+// needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
+#pragma once
+
+namespace {
+
+// Every reader's way in, in the order the C ABI documents: a null context, then what plan(msg) — the feature's
+// argument plan — refuses, before the map is touched; then ensure_ready
+template <typename PlanFn>
+int reader_enter(mrh_ctx* c, const char* who, PlanFn&& plan) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  char msg[mrh_plan::kMsgBytes];
+  const int rc = plan(msg);
+  return rc ? fail(c, rc, "%s", msg) : ensure_ready(c, who);
+}
+
+// One result plane of a blocking reader: where it lies in the pinned result, its size, where the kernels leave it, and whether
+// the caller takes it
+struct Plane {
+  size_t off, bytes;
+  void* dev;
+  bool wanted;
+  const void* host = nullptr;                               // read_planes: what the caller is handed (nullptr: not wanted)
+  void* device() const { return wanted ? dev : nullptr; }   // what the launch is handed
+};
+// the wanted planes into the pinned result `h`, one synchronisation (blocks)
+template <size_t N>
+int read_planes(mrh_ctx* c, char* h, Plane (&planes)[N]) {
+  for (Plane& p : planes)
+    if (p.wanted) HIP_TRY(c, hipMemcpyAsync(h + p.off, p.dev, p.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (Plane& p : planes) p.host = p.wanted ? h + p.off : nullptr;
+  return MRH_OK;
+}
+
+// ---- raycasting (include/mrhash_raycast.h) -----------------------------------------------------------------------------------
+
+// the four images, device pointers (nullptr = not wanted); `points` exists for the spherical model only
+struct RayOut {
+  float* depth; float* normals; uint8_t* rgb; float* points;
+};
+
+int raycast_enter(mrh_ctx* c, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, RayCam* rc) {
+  return reader_enter(c, who, [&](char* msg) { return mrh_plan::raycast(msg, who, model, p, R, t, c->p.sdf_truncation, c->pending, c->map.shard_count, rc); });
+}
+
+int launch_raycast(mrh_ctx* c, const int model, const RayCam& rc, const RayOut& o) {
+  const dim3 grid((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
+  if (model == MRH_CAMERA_SPHERICAL) k_raycast<true><<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, o.depth, o.normals, o.rgb, o.points);
+  else k_raycast<false><<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(c->map, c->tab, rc, o.depth, o.normals, o.rgb, nullptr);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+
+// mrh_raycast / mrh_raycast_spherical: the render into the context's own images and their pinned copy (blocks)
+int raycast_host(mrh_ctx* c, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, const float** out_depth,
+                 const float** out_normals, const uint8_t** out_rgb, const float** out_points) {
+  RayCam rc;
+  int e = raycast_enter(c, who, model, p, R, t, &rc);
+  if (e) return e;
+  mrh_ctx::Ray& r = c->ray;
+  // per pixel [depth f32 | normals 3 x f32 | points 3 x f32 | rgb 3 x u8], each image contiguous, on the device as in the pinned copy
+  const size_t npix = (size_t) rc.rows * (size_t) rc.cols, f = sizeof(float), bytes = npix * (7 * f + 3);
+  if ((e = regrow(c, r.d_img, r.cap, npix, bytes, false))) return e;  // the previous raycast has finished (it blocked): nothing reads the old buffers
+  if ((e = regrow_pinned(c, r.h_img, r.h_cap, npix, bytes))) return e;
+  auto image = [&](const size_t off, const size_t size, const bool wanted) { return Plane{off, size, r.d_img + off, wanted}; };
+  enum { DEPTH, NORMALS, RGB, POINTS };
+  Plane im[4] = {image(0, npix * f, out_depth != nullptr), image(npix * f, npix * 3 * f, out_normals && (p->outputs & MRH_RAYCAST_NORMALS)),
+                 image(npix * 7 * f, npix * 3, out_rgb && (p->outputs & MRH_RAYCAST_COLORS)),
+                 image(npix * 4 * f, npix * 3 * f, out_points && (p->outputs & MRH_RAYCAST_POINTS))};
+  if ((e = launch_raycast(c, model, rc, RayOut{(float*) im[DEPTH].device(), (float*) im[NORMALS].device(), (uint8_t*) im[RGB].device(), (float*) im[POINTS].device()})))
+    return e;
+  if ((e = read_planes(c, r.h_img, im))) return e;
+  if (out_depth) *out_depth = (const float*) im[DEPTH].host;
+  if (out_normals) *out_normals = (const float*) im[NORMALS].host;
+  if (out_rgb) *out_rgb = (const uint8_t*) im[RGB].host;
+  if (out_points) *out_points = (const float*) im[POINTS].host;
+  return MRH_OK;
+}
+
+// mrh_raycast_device / mrh_raycast_spherical_device: the render into the caller's device buffers (enqueues)
+int raycast_device(mrh_ctx* c, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, const RayOut& o) {
+  RayCam rc;
+  const int e = raycast_enter(c, who, model, p, R, t, &rc);
+  if (e) return e;
+  return launch_raycast(c, model, rc, RayOut{o.depth, (p->outputs & MRH_RAYCAST_NORMALS) ? o.normals : nullptr, (p->outputs & MRH_RAYCAST_COLORS) ? o.rgb : nullptr,
+                                             (p->outputs & MRH_RAYCAST_POINTS) ? o.points : nullptr});
+}
+
+// ---- distance fields (include/mrhash_esdf.h) -----------------------------------------------------------------------------------
+
+// have_dist: mrh_esdf_device was given its one required output (mrh_esdf has none: true)
+int esdf_enter(mrh_ctx* c, const char* who, const mrh_esdf_params* p, const bool have_dist, EsdfBox* bx) {
+  return reader_enter(c, who, [&](char* msg) {
+    const int e = mrh_plan::esdf(msg, who, p, c->map.min_weight_threshold, c->pending, c->map.shard_count, bx);
+    return e || have_dist ? e : mrh_plan::refuse(msg, MRH_ERR_INVALID_ARG, "%s: d_dist is null", who);
+  });
+}
+
+// the scratch of a box of n cells, before its pointers are handed to launch_esdf
+int esdf_scratch(mrh_ctx* c, const size_t n) {
+  mrh_ctx::Esdf& e = c->esdf;
+  if (n <= e.cap) return MRH_OK;  // an earlier mrh_esdf_device may still read the old scratch: regrow_all drains the stream
+  return regrow_all(c, e.cap, n, {{e.d_state, n}, {e.d_row, n * sizeof(uint16_t)}, {e.d_plane, n * sizeof(u32)}});
+}
+
+// the four launches on the scratch esdf_scratch has sized; out_state (which may be the scratch's own state plane) and out_d2 may be nullptr
+int launch_esdf(mrh_ctx* c, const EsdfBox& bx, float* dist, uint8_t* out_state, u32* out_d2) {
+  mrh_ctx::Esdf& e = c->esdf;
+  hipStream_t s = c->stream;
+  const auto bricks = [](const int o, const int len) { return (unsigned) (((o + len - 1) >> 3) - (o >> 3) + 1); };
+  const unsigned tiles = (unsigned) ((bx.nx + kEsdfTile - 1) / kEsdfTile);
+  k_esdf_classify<<<dim3(bricks(bx.ox, bx.nx), bricks(bx.oy, bx.ny), bricks(bx.oz, bx.nz)), 256, 0, s>>>(c->map, c->tab, bx, e.d_state, dist);
+  k_esdf_rows<<<(unsigned) (((size_t) bx.ny * (size_t) bx.nz + 3) / 4), 256, 0, s>>>(bx, e.d_state, e.d_row);
+  k_esdf_columns_y<<<dim3(tiles, (unsigned) bx.nz), 256, (size_t) kEsdfTile * (size_t) bx.ny * sizeof(u32), s>>>(bx, e.d_row, e.d_plane);
+  k_esdf_columns_z<<<dim3(tiles, (unsigned) bx.ny), 256, (size_t) kEsdfTile * (size_t) bx.nz * sizeof(u32), s>>>(c->map, bx, e.d_plane, e.d_state, dist, out_state, out_d2);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+static_assert((size_t) kEsdfTile * MRH_ESDF_MAX_SIDE * sizeof(u32) <= 65536, "a staged column tile fits the default dynamic LDS limit");
+static_assert(kEsdfMaxSide == MRH_ESDF_MAX_SIDE && kEsdfTile * kEsdfColumnLanes == 256, "mrh_esdf.h and mrhash_esdf.h agree");
+
+// ---- tracking (include/mrhash_track.h) -----------------------------------------------------------------------------------------
+
+// what is tracked: a pinhole depth image of the model's rows x cols (D14) or a cloud of n sensor-frame points against the
+// spherical render (D15); on the host (staged through pinned memory) or on the device
+struct TrackObs {
+  int model;  // MRH_CAMERA_*: the camera model of the model render, and with it the linearisation
+  const float* host; const float* dev;
+  size_t n;   // points (spherical); a depth image has rows * cols pixels
+};
+
+// what the stages of one call share: the plan, the shape of a linearisation and where the model and the observation lie
+struct TrackJob {
+  mrh_plan::Track plan;
+  bool scan;
+  size_t npix, n_obs, n_rows;  // the model's pixels, lanes of a linearisation, its workgroups (one partial row each)
+  dim3 grid;
+  float* d_md; float* d_mn;    // the model's depth (range), then its normals
+  const float* d_obs;
+};
+
+// the previous call blocked: nothing reads the old buffers
+int track_buffers(mrh_ctx* c, TrackJob& j) {
+  mrh_ctx::Track& T = c->trk;
+  int e = regrow(c, T.d_img, T.cap, j.npix, j.npix * 4 * sizeof(float), false);
+  if (!e) e = regrow(c, T.d_slab, T.slab_cap, j.n_rows, j.n_rows * mrh_track::kSumWords * sizeof(i64), false);
+  if (!e && j.scan) e = regrow(c, T.d_mp, T.mp_cap, j.npix, j.npix * 3 * sizeof(float), false);
+  if (e) return e;
+  if (!T.h_sums) HIP_TRY(c, pinned_alloc(c, T.h_sums, mrh_track::kSumWords * sizeof(i64)));
+  j.d_md = (float*) T.d_img;
+  j.d_mn = j.d_md + j.npix;
+  return MRH_OK;
+}
+
+// An observation of n floats from the host — a depth image or a cloud — through the one pinned staging buffer onto the device
+int stage_obs(mrh_ctx* c, const float* host, const size_t n, const float** d_obs) {
+  mrh_ctx::Track& T = c->trk;
+  int e = regrow_pinned(c, T.h_obs, T.h_obs_cap, n, n * sizeof(float));
+  if (!e) e = regrow(c, T.d_obs, T.obs_cap, n, n * sizeof(float), false);
+  if (e) return e;
+  memcpy(T.h_obs, host, n * sizeof(float));
+  HIP_TRY(c, hipMemcpyAsync(T.d_obs, T.h_obs, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  *d_obs = T.d_obs;
+  return MRH_OK;
+}
+
+// Per iteration the linearisation kernel, k_track_finish, the 256-byte read-back from pinned memory, and solve + update on the host.
+// (R, t): the pose, updated in place; sums: of the last linearisation.  *done: updates applied; returns MRH_TRACK_* or an error
+int track_iterate(mrh_ctx* c, const mrh_track_params* p, const TrackJob& j, const float* R0, const float* t0, double R[9], double t[3],
+                  int64_t sums[mrh_track::kSumWords], int* done) {
+  const mrh_ctx::Track& T = c->trk;
+  const RayCam& rc = j.plan.cam;
+  TrackLin k;
+  k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.ifx = rc.ifx; k.ify = rc.ify;
+  k.rows = rc.rows; k.cols = rc.cols;
+  k.min_depth = rc.min_depth; k.max_depth = rc.max_depth;
+  k.dmax2 = j.plan.dist_max * j.plan.dist_max;
+  k.s_a = mrh_track::angle_scale(rc.max_depth);
+  for (int i = 0; i < 9; i++) k.Rr[i] = R0[i];
+  for (int i = 0; i < 3; i++) k.tr[i] = t0[i];
+  for (int it = 0; it < j.plan.iterations; it++) {
+    for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
+    for (int i = 0; i < 3; i++) k.t[i] = (float) t[i];
+    if (j.scan) k_track_scan_linearise<<<j.grid, 256, 0, c->stream>>>(k, j.d_obs, (unsigned) j.n_obs, j.d_md, j.d_mn, T.d_mp, T.d_slab);
+    else k_track_linearise<<<j.grid, kRenderTile * kRenderTile, 0, c->stream>>>(k, j.d_obs, j.d_md, j.d_mn, T.d_slab);
+    k_track_finish<<<1, 1024, 0, c->stream>>>(T.d_slab, (int) j.n_rows, T.h_sums);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
+    for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) T.h_sums)[i];
+    double xi[6];
+    if (!mrh_track::solve(sums, k.s_a, j.plan.min_pixels, xi)) return MRH_TRACK_LOST;
+    mrh_track::update(R, t, xi);
+    ++*done;
+  }
+  return MRH_TRACK_OK;
+}
+
+// mrh_track_depth / mrh_track_scan and their device variants, a driver over the stages: plan (mrh_readerplan.h), buffers, the
+// observation onto the device, one render of the model through the raycast's own launch, the iterations, the report (blocks)
+int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const TrackObs& obs, const float* R0, const float* t0, float* out_R, float* out_t,
+              mrh_track_info* out_info) {
+  TrackJob j;
+  int e = reader_enter(c, who, [&](char* msg) {
+    return mrh_plan::track(msg, who, obs.model, p, obs.host || obs.dev, obs.n, out_R && out_t, R0, t0, c->p.sdf_truncation, c->pending, c->map.shard_count, &j.plan);
+  });
+  if (e) return e;
+  const RayCam& rc = j.plan.cam;
+  j.scan = obs.model == MRH_CAMERA_SPHERICAL;
+  j.npix = (size_t) rc.rows * (size_t) rc.cols;
+  j.n_obs = j.scan ? obs.n : j.npix;
+  j.grid = j.scan ? dim3((unsigned) ((j.n_obs + 255) / 256))
+                  : dim3((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
+  j.n_rows = (size_t) j.grid.x * j.grid.y;
+  j.d_obs = obs.dev;
+  double R[9], t[3];
+  for (int i = 0; i < 9; i++) R[i] = (double) R0[i];
+  for (int i = 0; i < 3; i++) t[i] = (double) t0[i];
+  int64_t sums[mrh_track::kSumWords] = {};
+  int status = MRH_TRACK_LOST, done = 0;  // an empty scan is lost: nothing is rendered or launched
+  if (j.n_obs) {
+    if ((e = track_buffers(c, j))) return e;
+    if (!j.d_obs && (e = stage_obs(c, obs.host, j.scan ? 3 * j.n_obs : j.npix, &j.d_obs))) return e;
+    if ((e = launch_raycast(c, obs.model, rc, RayOut{j.d_md, j.d_mn, nullptr, j.scan ? c->trk.d_mp : nullptr}))) return e;
+    if ((status = track_iterate(c, p, j, R0, t0, R, t, sums, &done)) < 0) return status;
+  }
+  for (int i = 0; i < 9; i++) out_R[i] = (float) R[i];
+  for (int i = 0; i < 3; i++) out_t[i] = (float) t[i];
+  if (out_info) {
+    out_info->status = status;
+    out_info->iterations_done = done;
+    out_info->pixels = (uint64_t) sums[mrh_track::kSumN];
+    out_info->rms = mrh_track::rms(sums);
+    for (int i = 0; i < mrh_track::kSumWords; i++) out_info->sums[i] = sums[i];
+  }
+  return MRH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrh_raycast(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], const float** out_depth,
+                const float** out_normals, const uint8_t** out_rgb) {
+  return raycast_host(c, "mrh_raycast", MRH_CAMERA_PINHOLE, p, R_row_major, t, out_depth, out_normals, out_rgb, nullptr);
+}
+
+int mrh_raycast_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_depth, float* d_normals,
+                       uint8_t* d_rgb) {
+  return raycast_device(c, "mrh_raycast_device", MRH_CAMERA_PINHOLE, p, R_row_major, t, RayOut{d_depth, d_normals, d_rgb, nullptr});
+}
+
+int mrh_raycast_spherical(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], const float** out_range,
+                          const float** out_normals, const uint8_t** out_rgb, const float** out_points) {
+  return raycast_host(c, "mrh_raycast_spherical", MRH_CAMERA_SPHERICAL, p, R_row_major, t, out_range, out_normals, out_rgb, out_points);
+}
+
+int mrh_raycast_spherical_device(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], float* d_range,
+                                 float* d_normals, uint8_t* d_rgb, float* d_points) {
+  return raycast_device(c, "mrh_raycast_spherical_device", MRH_CAMERA_SPHERICAL, p, R_row_major, t, RayOut{d_range, d_normals, d_rgb, d_points});
+}
+
+int mrh_esdf(mrh_ctx* c, const mrh_esdf_params* p, const float** out_dist, const uint8_t** out_state, const uint32_t** out_d2) {
+  EsdfBox bx;
+  int rc = esdf_enter(c, "mrh_esdf", p, true, &bx);
+  if (rc) return rc;
+  const size_t n = (size_t) bx.nx * (size_t) bx.ny * (size_t) bx.nz;
+  mrh_ctx::Esdf& e = c->esdf;
+  // results per cell: device dist f32 and d2 u32; pinned [dist f32 | d2 u32 | state u8], each plane contiguous
+  if (n > e.out_cap && (rc = regrow_all(c, e.out_cap, n, {{e.d_dist, n * sizeof(float)}, {e.d_d2, n * sizeof(u32)}}))) return rc;
+  if ((rc = regrow_pinned(c, e.h_out, e.h_cap, n, n * 9))) return rc;
+  if ((rc = esdf_scratch(c, n))) return rc;
+  enum { DIST, D2, STATE };
+  Plane pl[3] = {{0, n * sizeof(float), e.d_dist, out_dist != nullptr}, {n * 4, n * sizeof(u32), e.d_d2, out_d2 && (p->outputs & MRH_ESDF_SQUARED)},
+                 {n * 8, n, e.d_state, out_state && (p->outputs & MRH_ESDF_STATE)}};
+  if ((rc = launch_esdf(c, bx, e.d_dist, (uint8_t*) pl[STATE].device(), (u32*) pl[D2].device()))) return rc;
+  if ((rc = read_planes(c, e.h_out, pl))) return rc;
+  if (out_dist) *out_dist = (const float*) pl[DIST].host;
+  if (out_state) *out_state = (const uint8_t*) pl[STATE].host;
+  if (out_d2) *out_d2 = (const uint32_t*) pl[D2].host;
+  return MRH_OK;
+}
+
+int mrh_esdf_device(mrh_ctx* c, const mrh_esdf_params* p, float* d_dist, uint8_t* d_state, uint32_t* d_d2) {
+  EsdfBox bx;
+  int rc = esdf_enter(c, "mrh_esdf_device", p, d_dist != nullptr, &bx);
+  if (rc) return rc;
+  if ((rc = esdf_scratch(c, (size_t) bx.nx * (size_t) bx.ny * (size_t) bx.nz))) return rc;
+  return launch_esdf(c, bx, d_dist, (p->outputs & MRH_ESDF_STATE) ? d_state : nullptr, (p->outputs & MRH_ESDF_SQUARED) ? (u32*) d_d2 : nullptr);
+}
+
+int mrh_track_depth(mrh_ctx* c, const mrh_track_params* p, const float* depth_host, const float R_init[9], const float t_init[3], float out_R[9],
+                    float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_depth", p, TrackObs{MRH_CAMERA_PINHOLE, depth_host, nullptr, 0}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_depth_device(mrh_ctx* c, const mrh_track_params* p, const float* d_depth, const float R_init[9], const float t_init[3], float out_R[9],
+                           float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_depth_device", p, TrackObs{MRH_CAMERA_PINHOLE, nullptr, d_depth, 0}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_scan(mrh_ctx* c, const mrh_track_params* p, const float* points_host, size_t n, const float R_init[9], const float t_init[3], float out_R[9],
+                   float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_scan", p, TrackObs{MRH_CAMERA_SPHERICAL, points_host, nullptr, n}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_scan_device(mrh_ctx* c, const mrh_track_params* p, const float* d_points, size_t n, const float R_init[9], const float t_init[3],
+                          float out_R[9], float out_t[3], mrh_track_info* out_info) {
+  return track_run(c, "mrh_track_scan_device", p, TrackObs{MRH_CAMERA_SPHERICAL, nullptr, d_points, n}, R_init, t_init, out_R, out_t, out_info);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // mrh_tracksolve.h — the host half of depth-frame tracking (include/mrhash_track.h): the fixed-point scale, the
 // binary64 Cholesky solve of the 6 x 6 normal equations from the 29 exact integer sums, and the pose update.  Plain C++, no HIP:
-// mrh_capi.hip includes it, and tests/host/track_solve_check.cpp compiles it on its own.  Built with -ffp-contract=off like
+// mrh_readers.h uses it, and tests/host/track_solve_check.cpp compiles it on its own.  Built with -ffp-contract=off like
 // everything else: every product and every sum below rounds once, in the order written (tests/track_ref.py restates it).
 #pragma once
 

@@ -338,3 +338,49 @@ def test_accuracy_on_the_fused_map(street, scan):
     want = _reference(street, PARAMS, CAM, scan, 0)
     _assert_bit_exact((R, t, info), want)
     tc.check_fused(dict(info, R=R, t=t), int(np.count_nonzero(np.any(scan != 0, axis=1))))
+
+
+# ---- G12 --------------------------------------------------------------------------------------------------------------
+
+def test_depth_images_and_scans_share_one_staging_pair(street, scan):
+    """A host observation of either kind goes through one pinned and one device staging buffer, sized in floats (stage_obs).  On
+    one context: track_depth on an 80 x 60 image (4 800 floats), track_scan with the 16 x 64 scan (3 072 floats: the pair is reused
+    at a smaller size), track_scan with a 32 x 512 scan (49 152 floats: it grows), track_depth again (after a larger scan: reused at a
+    smaller size, over what the cloud left behind), track_scan_device (no staging).  Every pose and its 32 sums equal, bit for
+    bit, what a context that has made no other call returns."""
+    hip = capi.load_hip()
+    scene = synth.street_canyon()
+    frames = [(synth.quat_to_rot(q), t, *synth.spherical_range_image(scene, t, q, CAM_BIG)) for t, q in ts.STREET_POSES]
+
+    def fresh():
+        e = capi.Engine(hip, capi.Params(num_sdf_blocks=131072, **PARAMS))
+        e.set_camera(*ts.cam_args(CAM_BIG), NEAR, FAR, model=1)
+        for R, t, depth, rgb in frames:
+            e.set_pose(R, t)
+            e.upload_depth(depth)
+            e.upload_rgb(rgb)
+            assert not e.integrate()
+        return e
+
+    # the pinhole camera looks along the sensor's x axis (camera z forward, x right, y down), 80 x 60 pixels, 90 degrees wide
+    pin = (40.0, 40.0, 39.5, 29.5, 60, 80)
+    R_pin = (R_LAST @ np.array([[0, 0, 1], [-1, 0, 0], [0, -1, 0]], F)).astype(F)
+    image, _, _ = street.raycast(*pin, R_pin, (T_LAST + np.array([0.2, 0.1, 0.05], F)).astype(F), NEAR, FAR, colors=False)
+    big = tc.fused_scan(32, 512)
+    dev = hipmem.DeviceBuffer.from_numpy(np.ascontiguousarray(scan, F))
+    calls = [lambda e: e.track_depth(image, *pin, R_pin, T_LAST, NEAR, FAR, iterations=3),
+             lambda e: _track(e, CAM, scan, 3),
+             lambda e: _track(e, CAM, big, 1),
+             lambda e: e.track_depth(image, *pin, R_pin, T_LAST, NEAR, FAR, iterations=3),
+             lambda e: e.track_scan_device(dev.ptr, len(scan), *ts.cam_args(CAM), R_LAST, T_LAST, NEAR, FAR, iterations=3)]
+    for i, call in enumerate(calls):
+        got = call(street)
+        e = fresh()
+        try:
+            want = call(e)
+        finally:
+            e.close()
+        print("call %d: status %d, %d iterations, %d pixels" % (i, got[2]["status"], got[2]["iterations_done"], got[2]["pixels"]))
+        assert _same_bits(got[0], want[0]) and _same_bits(got[1], want[1]), i
+        assert np.array_equal(got[2]["sums"], want[2]["sums"]) and got[2]["status"] == want[2]["status"], i
+        assert got[2]["pixels"] >= 64, i  # the observation took part
