@@ -1024,9 +1024,12 @@ def test_two_contexts_on_two_host_threads_share_the_copy_pool(hip, oracle):
 
 
 def test_marching_cubes_prescreen_changes_nothing(hip, monkeypatch):
-    """The count pass skips voxels whose 27 surrounding cells are all clearly positive or all clearly negative; with
-    the prescreen off (MRH_MC_NO_PRESCREEN=1) every voxel takes the full path: same triangle buffer, byte for byte —
-    also with a range-dependent truncation and with noise that puts samples near zero."""
+    """The count pass skips a voxel whose window (3^3 cells, 7^3 next to a coarse block) holds no "anything else" cell and
+    not both clear signs among its weighted cells — unseen cells count as nothing, starved ones (weight 0, sdf kept) as
+    "anything else" on the wide window (mrh_mc.h, k_mc).  With the prescreen off (MRH_MC_NO_PRESCREEN=1) every voxel takes
+    the full path: same triangle buffer, byte for byte, on three noisy single-resolution Replica frames with a
+    range-dependent truncation.  The rule's edges (thresholds, starved cells, the wide window) are
+    tests/test_mc_fields_gpu.py's."""
     K = synth.REPLICA_640
     params = dict(synth.REPLICA_PARAMS, sdf_truncation_scale=0.01, min_weight_threshold=1)
     e = pu.make_engine(hip, K, params, 65536)
