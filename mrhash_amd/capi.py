@@ -151,6 +151,18 @@ class MrhEsdfParams(C.Structure):
                 ("surface_band", C.c_float), ("outputs", C.c_uint32)]
 
 
+# every symbol include/mrhash_query.h declares (the HIP library only: the oracle has no point query)
+QUERY_SYMBOLS = ("mrh_query_points mrh_query_points_device").split()
+QUERY_FIELD_MAP, QUERY_FIELD_SMOOTH = 0, 1
+QUERY_GRADIENT, QUERY_COLOUR = 1, 2
+QUERY_BLOCK, QUERY_DIST, QUERY_GRAD, QUERY_COARSE, QUERY_REFUSED = 1, 2, 4, 8, 0x80
+QUERY_MAX_POINTS = 1 << 24
+
+
+class MrhQueryParams(C.Structure):
+    _fields_ = [("field", C.c_int32), ("outputs", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 # every symbol include/mrhash_track.h declares (the HIP library only: the oracle does not track)
 TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device mrh_track_scan mrh_track_scan_device").split()
 TRACK_OK, TRACK_LOST = 0, 1
@@ -288,6 +300,13 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_esdf.argtypes = [C.c_void_p, P(MrhEsdfParams), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p)]
         lib.mrh_esdf_device.argtypes = [C.c_void_p, P(MrhEsdfParams), C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ESDF_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_query_points"):  # include/mrhash_query.h
+        lib.mrh_query_points.argtypes = [C.c_void_p, P(MrhQueryParams), C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_void_p),
+                                         P(C.c_void_p), P(C.c_void_p)]
+        lib.mrh_query_points_device.argtypes = [C.c_void_p, P(MrhQueryParams), C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+        for name in QUERY_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_track_depth"):  # include/mrhash_track.h
         lib.mrh_track_depth.argtypes = [C.c_void_p, P(MrhTrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
@@ -825,6 +844,43 @@ class Engine:
         context's stream; finished by sync() or any blocking call."""
         p = self._esdf_params(origin, dims, max_distance_voxels, surface_band, min_weight, bool(d_state), bool(d_d2))
         self._check(self.lib.mrh_esdf_device(self._ctx, C.byref(p), d_dist or None, d_state or None, d_d2 or None))
+
+    # -- point queries (include/mrhash_query.h) ------------------------------------------------------
+    @staticmethod
+    def _query_args(R, t, smooth, gradient, colour):
+        if (R is None) != (t is None):
+            raise ValueError("query: give both R and t, or neither")
+        p = MrhQueryParams(QUERY_FIELD_SMOOTH if smooth else QUERY_FIELD_MAP, (QUERY_GRADIENT if gradient else 0) | (QUERY_COLOUR if colour else 0))
+        F = C.POINTER(C.c_float)
+        if R is None:
+            return p, None, None, None
+        R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        return p, R.ctypes.data_as(F), t.ctypes.data_as(F), (R, t)  # the last: keeps the arrays alive across the call
+
+    def query(self, points, R=None, t=None, smooth=False, gradient=True, colour=True):
+        """TSDF distance, gradient and colour at points [n, 3] (mrh_query_points): world-frame points, or with
+        (R, t) sensor-frame points and their sensor-to-world pose ((0, 0, 0) is then a missing return and refused).  smooth =
+        False: the map's own field, the reference's trilinearInterpolation — piecewise constant inside a dual cell; smooth =
+        True: the continuous field with its analytic gradient.  Returns numpy copies (dist f32 [n], grad f32 [n, 3] or None,
+        rgbw u8 [n, 4] = r, g, b, weight or None, state u8 [n]: QUERY_BLOCK | QUERY_DIST | QUERY_GRAD | QUERY_COARSE |
+        QUERY_REFUSED)."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(pts)
+        p, pR, pt, _keep = self._query_args(R, t, smooth, gradient, colour)
+        pd, pg, pc, ps = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.lib.mrh_query_points(self._ctx, C.byref(p), pts.ctypes.data if n else None, n, pR, pt, C.byref(pd), C.byref(pg) if gradient else None,
+                                              C.byref(pc) if colour else None, C.byref(ps)))
+        return (_copy_out(pd, n, np.float32, (n,)), _copy_out(pg, 3 * n, np.float32, (n, 3)) if gradient else None,
+                _copy_out(pc, 4 * n, np.uint8, (n, 4)) if colour else None, _copy_out(ps, n, np.uint8, (n,)))
+
+    def query_device(self, d_points, n, R=None, t=None, smooth=False, d_dist=0, d_grad=0, d_rgbw=0, d_state=0):
+        """mrh_query_points_device: enqueues the query of n points at d_points ([n, 3] f32) into caller device buffers (integer
+        pointers, e.g. hipmem.DeviceBuffer.ptr: [n] f32, [n, 3] f32, [n, 4] u8, [n] u8; d_dist and d_state are required, 0 = skip
+        for the other two).  Ordered on the context's stream; finished by sync() or any blocking call."""
+        p, pR, pt, _keep = self._query_args(R, t, smooth, bool(d_grad), bool(d_rgbw))
+        self._check(self.lib.mrh_query_points_device(self._ctx, C.byref(p), d_points or None, int(n), pR, pt, d_dist or None, d_grad or None,
+                                                     d_rgbw or None, d_state or None))
 
     # -- tracking (include/mrhash_track.h) ------------------------------------------------------------
     def _track(self, fn, obs, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):

@@ -633,6 +633,25 @@ GeoWrapper::DistanceField GeoWrapper::distanceField(const std::array<float, 3>& 
   return out;
 }
 
+GeoWrapper::PointQuery GeoWrapper::queryPoints(const float* pts, const size_t n, const bool smooth, const bool sensor_frame) {
+  mrh_query_params p;
+  std::memset(&p, 0, sizeof p);
+  p.field = smooth ? MRH_QUERY_FIELD_SMOOTH : MRH_QUERY_FIELD_MAP;
+  p.outputs = MRH_QUERY_GRADIENT | MRH_QUERY_COLOUR;
+  const PoseRt at = split_pose(pose_);
+  const float *dist = nullptr, *grad = nullptr;
+  const uint8_t *rgbw = nullptr, *state = nullptr;
+  check(mrh_query_points(ctx_, &p, pts, (uint64_t) n, sensor_frame ? at.R : nullptr, sensor_frame ? at.t : nullptr, &dist, &grad, &rgbw, &state), "queryPoints");
+  PointQuery out;
+  if (n) {
+    out.dist.assign(dist, dist + n);
+    out.grad.assign(grad, grad + 3 * n);
+    out.rgbw.assign(rgbw, rgbw + 4 * n);
+    out.state.assign(state, state + n);
+  }
+  return out;
+}
+
 GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols) { return trackDepthPose(depth, rows, cols, pose_); }
 
 GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) {

@@ -14,6 +14,7 @@
 #include "mrhash_comm.h"
 #include "mrhash_raycast.h"
 #include "mrhash_esdf.h"
+#include "mrhash_query.h"
 #include "mrhash_track.h"
 #include "mrhash_normals.h"
 
@@ -130,6 +131,18 @@ public:
     std::vector<uint8_t> state;
   };
   DistanceField distanceField(const std::array<float, 3>& lo, const std::array<float, 3>& hi, float max_distance);
+
+  // ---- point queries (include/mrhash_query.h; no reference counterpart): TSDF distance (metres), gradient, colour
+  // and weight of the map at n points [n * 3].  smooth = false: the map's own field (the reference's trilinearInterpolation, what
+  // the mesh and the render see: the mean of eight cells, piecewise constant inside a dual cell); smooth = true: the continuous
+  // field with its analytic gradient, for planners and registration.  sensor_frame = false: world points; true: points in the
+  // sensor frame at the pose of the last setCurrPose, (0, 0, 0) = no return (refused) — raycastScan's points as they are.
+  // dist [n], grad [n * 3], rgbw [n * 4] = r, g, b, weight, state [n] (MRH_QUERY_* bits).
+  struct PointQuery {
+    std::vector<float> dist, grad;
+    std::vector<uint8_t> rgbw, state;
+  };
+  PointQuery queryPoints(const float* pts, size_t n, bool smooth = false, bool sensor_frame = false);
 
   // ---- tracking (include/mrhash_track.h; no reference counterpart): the pose of a depth image (rows x cols as
   // the camera of the last setCamera, metres) by point-to-plane ICP against the map, started from the current pose (setCurrPose)

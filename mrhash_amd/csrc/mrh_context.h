@@ -433,6 +433,12 @@ struct mrh_ctx {
     float* d_dist = nullptr; u32* d_d2 = nullptr; size_t out_cap = 0;
     char* h_out = nullptr; size_t h_cap = 0;
   } esdf;
+  // point queries (mrh_readers.h, kernels in mrh_query.h), grow-only, in points — the results of mrh_query_points on the device and
+  // in the pinned copy the caller reads, both [dist f32 | grad 3 x f32 | rgbw 4 x u8 | state u8], each plane contiguous
+  struct Query {
+    char* d_out = nullptr; size_t cap = 0;
+    char* h_out = nullptr; size_t h_cap = 0;
+  } query;
   // tracking (mrh_readers.h, kernels in mrh_track.h), grow-only — device [model depth or range f32 | model normals 3 x f32] per
   // pixel, for scans (D15) the model's points image, and the partial slab (one row of 32 words per workgroup); pinned: the 32 sums
   // the host reads.  An observation that comes from the host — a depth image (D14) or a cloud — is staged through one pair of

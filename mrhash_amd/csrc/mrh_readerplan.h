@@ -1,4 +1,5 @@
-// mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking)
+// mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking,
+// point queries)
 // and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
 // parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
 // the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
@@ -17,6 +18,7 @@
 #include "../../include/mrh_softmath.h"
 #include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_normals.h"
+#include "../../include/mrhash_query.h"
 #include "../../include/mrhash_track.h"
 
 namespace mrh {
@@ -37,6 +39,15 @@ struct EsdfBox {
   uint32_t reach;   // R, 1 .. 4095 voxels
   int w_min;        // observed: weight >= w_min (>= 1)
   float band;       // site: |sdf| <= band; 0 = one voxel of the block's own resolution
+};
+
+// what k_query takes (mrh_query.h): the point count, the refusal bound and the sensor-to-world pose of a posed call
+struct QueryArgs {
+  uint32_t n;          // points, 1 .. 2^24 when the kernel runs
+  float bound;         // (float) (1 << 20) * vs: a point is refused unless |P_a| < bound on every axis
+  bool smooth, posed;  // the field; the points are in the sensor frame
+  uint32_t outputs;    // MRH_QUERY_* bits
+  float R[9], t[3];    // sensor in world (row-major R); identity and 0 when !posed
 };
 
 // the parameters of the normal-estimation kernels (mrh_normals.h), defaults filled in
@@ -173,6 +184,34 @@ inline int track(char* msg, const char* who, const int model, const mrh_track_pa
     return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %d iterations (1 .. %d, 0 = 10)", who, p->iterations, MRH_TRACK_MAX_ITERATIONS);
   out->iterations = p->iterations ? p->iterations : 10;
   out->min_pixels = p->min_pixels ? p->min_pixels : 64u;
+  return MRH_OK;
+}
+
+// the arguments both point-query entry points share; fills the kernel's arguments.  have_points: the point list was given (n == 0
+// needs none); have_out: the required outputs were (the blocking call has none: true); voxel_size: the context's
+// virtual_voxel_size, for the refusal bound
+inline int query(char* msg, const char* who, const mrh_query_params* p, const bool have_points, const bool have_out, const uint64_t n, const float* R,
+                 const float* t, const float voxel_size, const int pending, const int shard_count, mrh::QueryArgs* out) {
+  if (!p || (!have_points && n != 0) || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = whole_map(msg, who, "are not queried", pending, shard_count)) return e;
+  if (p->field != MRH_QUERY_FIELD_MAP && p->field != MRH_QUERY_FIELD_SMOOTH) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: unknown field %d", who, p->field);
+  if (p->outputs & ~(MRH_QUERY_GRADIENT | MRH_QUERY_COLOUR)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  if (p->reserved[0] || p->reserved[1]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  if (n > MRH_QUERY_MAX_POINTS) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %llu points in one call (limit 2^24)", who, (unsigned long long) n);
+  if ((R != nullptr) != (t != nullptr)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: R and t are both null or both set", who);
+  out->posed = R != nullptr;
+  for (int i = 0; i < 9; i++) {
+    out->R[i] = out->posed ? R[i] : (i % 4 == 0 ? 1.f : 0.f);
+    if (!std::isfinite(out->R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  }
+  for (int i = 0; i < 3; i++) {
+    out->t[i] = out->posed ? t[i] : 0.f;
+    if (!std::isfinite(out->t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  }
+  out->n = (uint32_t) n;
+  out->bound = (float) (1 << 20) * voxel_size;
+  out->smooth = p->field == MRH_QUERY_FIELD_SMOOTH;
+  out->outputs = p->outputs;
   return MRH_OK;
 }
 

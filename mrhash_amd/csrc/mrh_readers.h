@@ -1,8 +1,9 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
-// [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h) and tracking (mrh_track_depth / _scan
-// [_device], mrh_track.h; the solve is mrh_tracksolve.h).  What they share is here once: the way in (reader_enter: null context,
-// the feature's argument plan from mrh_readerplan.h, ensure_ready) and the way the blocking calls hand their result planes out of
-// pinned memory (read_planes).  The state is mrh_ctx::ray, ::esdf and ::trk.  Included by mrh_capi.hip, same translation unit: it
+// [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
+// [_device], mrh_track.h; the solve is mrh_tracksolve.h) and point queries (mrh_query_points[_device], mrh_query.h).  What they
+// share is here once: the way in (reader_enter: null context, the feature's argument plan from mrh_readerplan.h, ensure_ready) and
+// the way the blocking calls hand their result planes out of pinned memory (read_planes).  The state is mrh_ctx::ray, ::esdf,
+// ::trk and ::query.  Included by mrh_capi.hip, same translation unit: it
 // needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
 #pragma once
 
@@ -240,9 +241,35 @@ int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const Trac
   return MRH_OK;
 }
 
+// ---- point queries (include/mrhash_query.h) ------------------------------------------------------------------------------------
+
+// the four outputs, device pointers (dist and state always; grad / rgbw nullptr = not produced)
+struct QueryOut {
+  float* dist; float* grad; uint8_t* rgbw; uint8_t* state;
+};
+
+// have_points / have_out: the point list and the required outputs were given (mrh_plan::query)
+int query_enter(mrh_ctx* c, const char* who, const mrh_query_params* p, const bool have_points, const bool have_out, const uint64_t n, const float* R,
+                const float* t, QueryArgs* q) {
+  return reader_enter(c, who, [&](char* msg) { return mrh_plan::query(msg, who, p, have_points, have_out, n, R, t, c->p.virtual_voxel_size, c->pending, c->map.shard_count, q); });
+}
+
+// one launch for q.n >= 1 points; o.grad / o.rgbw are already nullptr where they are not wanted
+int launch_query(mrh_ctx* c, const QueryArgs& q, const float* d_xyz, const QueryOut& o) {
+  const unsigned grid = (unsigned) (((size_t) q.n + kQueryLanes - 1) / kQueryLanes);
+  if (q.smooth && q.posed) k_query<true, true><<<grid, kQueryLanes, 0, c->stream>>>(c->map, c->tab, q, d_xyz, o.dist, o.grad, o.rgbw, o.state);
+  else if (q.smooth) k_query<true, false><<<grid, kQueryLanes, 0, c->stream>>>(c->map, c->tab, q, d_xyz, o.dist, o.grad, o.rgbw, o.state);
+  else if (q.posed) k_query<false, true><<<grid, kQueryLanes, 0, c->stream>>>(c->map, c->tab, q, d_xyz, o.dist, o.grad, o.rgbw, o.state);
+  else k_query<false, false><<<grid, kQueryLanes, 0, c->stream>>>(c->map, c->tab, q, d_xyz, o.dist, o.grad, o.rgbw, o.state);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+static_assert((size_t) kQueryLanes * kQuerySlice * sizeof(u32) <= 65536, "the lane-private slices fit the static LDS limit");
+
 }  // namespace
 
 extern "C" {
+
 
 int mrh_raycast(mrh_ctx* c, const mrh_raycast_params* p, const float R_row_major[9], const float t[3], const float** out_depth,
                 const float** out_normals, const uint8_t** out_rgb) {
@@ -311,6 +338,46 @@ int mrh_track_scan(mrh_ctx* c, const mrh_track_params* p, const float* points_ho
 int mrh_track_scan_device(mrh_ctx* c, const mrh_track_params* p, const float* d_points, size_t n, const float R_init[9], const float t_init[3],
                           float out_R[9], float out_t[3], mrh_track_info* out_info) {
   return track_run(c, "mrh_track_scan_device", p, TrackObs{MRH_CAMERA_SPHERICAL, nullptr, d_points, n}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_query_points(mrh_ctx* c, const mrh_query_params* p, const float* xyz_host, uint64_t n, const float R_row_major[9], const float t[3],
+                     const float** out_dist, const float** out_grad, const uint8_t** out_rgbw, const uint8_t** out_state) {
+  QueryArgs q;
+  int rc = query_enter(c, "mrh_query_points", p, xyz_host != nullptr, true, n, R_row_major, t, &q);
+  if (rc) return rc;
+  if (out_dist) *out_dist = nullptr;
+  if (out_grad) *out_grad = nullptr;
+  if (out_rgbw) *out_rgbw = nullptr;
+  if (out_state) *out_state = nullptr;
+  if (n == 0) return MRH_OK;
+  mrh_ctx::Query& Q = c->query;
+  // per point [dist f32 | grad 3 x f32 | rgbw 4 x u8 | state u8], each plane contiguous, on the device as in the pinned copy
+  const size_t np = (size_t) n, f = sizeof(float), bytes = np * (4 * f + 4 + 1);
+  if ((rc = regrow(c, Q.d_out, Q.cap, np, bytes, false))) return rc;  // the previous mrh_query_points has finished (it blocked): nothing reads the old buffer
+  if ((rc = regrow_pinned(c, Q.h_out, Q.h_cap, np, bytes))) return rc;
+  const float* d_xyz = nullptr;
+  if ((rc = stage_obs(c, xyz_host, 3 * np, &d_xyz))) return rc;
+  auto plane = [&](const size_t off, const size_t size, const bool wanted) { return Plane{off, size, Q.d_out + off, wanted}; };
+  enum { DIST, GRAD, RGBW, STATE };
+  Plane pl[4] = {plane(0, np * f, out_dist != nullptr), plane(np * f, np * 3 * f, out_grad && (p->outputs & MRH_QUERY_GRADIENT)),
+                 plane(np * 4 * f, np * 4, out_rgbw && (p->outputs & MRH_QUERY_COLOUR)), plane(np * 4 * f + np * 4, np, out_state != nullptr)};
+  // dist and state are always computed, the gradient whenever its bit is set: a NULL out-pointer only saves the copy
+  const QueryOut o = {(float*) pl[DIST].dev, (p->outputs & MRH_QUERY_GRADIENT) ? (float*) pl[GRAD].dev : nullptr, (uint8_t*) pl[RGBW].device(), (uint8_t*) pl[STATE].dev};
+  if ((rc = launch_query(c, q, d_xyz, o))) return rc;
+  if ((rc = read_planes(c, Q.h_out, pl))) return rc;
+  if (out_dist) *out_dist = (const float*) pl[DIST].host;
+  if (out_grad) *out_grad = (const float*) pl[GRAD].host;
+  if (out_rgbw) *out_rgbw = (const uint8_t*) pl[RGBW].host;
+  if (out_state) *out_state = (const uint8_t*) pl[STATE].host;
+  return MRH_OK;
+}
+
+int mrh_query_points_device(mrh_ctx* c, const mrh_query_params* p, const float* d_xyz, uint64_t n, const float R_row_major[9], const float t[3],
+                            float* d_dist, float* d_grad, uint8_t* d_rgbw, uint8_t* d_state) {
+  QueryArgs q;
+  const int rc = query_enter(c, "mrh_query_points_device", p, d_xyz != nullptr, d_dist && d_state, n, R_row_major, t, &q);
+  if (rc || n == 0) return rc;
+  return launch_query(c, q, d_xyz, QueryOut{d_dist, (p->outputs & MRH_QUERY_GRADIENT) ? d_grad : nullptr, (p->outputs & MRH_QUERY_COLOUR) ? d_rgbw : nullptr, d_state});
 }
 
 }  // extern "C"

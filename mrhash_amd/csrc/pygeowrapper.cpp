@@ -224,6 +224,27 @@ PYBIND11_MODULE(pygeowrapper, m) {
       std::memcpy(state.mutable_data(), f.state.data(), f.state.size());
       return py::make_tuple(dist, state, py::make_tuple(f.origin[0], f.origin[1], f.origin[2]), py::make_tuple(f.dims[0], f.dims[1], f.dims[2]));
     }, py::arg("lo"), py::arg("hi"), py::arg("max_distance"))
+    // not part of the reference binding: TSDF distance, gradient and colour of the map at points [n, 3] — world points, or with
+    // sensor_frame = True points in the sensor frame at the pose of the last setCurrPose ((0, 0, 0) = no return, refused; what
+    // raycastScan returns).  smooth = False: the map's own, piecewise-constant field; True: the continuous field.  Returns
+    // (dist [n] f32, grad [n, 3] f32, rgbw [n, 4] u8 = r, g, b, weight, state [n] u8 of MRH_QUERY_* bits)
+    .def("queryPoints", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> points, bool smooth, bool sensor_frame) {
+      if (!((points.ndim() == 2 && points.shape(1) == 3) || (points.ndim() == 1 && points.size() % 3 == 0)))
+        throw std::runtime_error("GeoWrapper::queryPoints|expected points of shape [n, 3]");
+      const size_t n = (size_t) points.size() / 3;
+      const GeoWrapper::PointQuery r = g.queryPoints(points.data(), n, smooth, sensor_frame);
+      py::array_t<float> dist({n});
+      py::array_t<float> grad({n, (size_t) 3});
+      py::array_t<uint8_t> rgbw({n, (size_t) 4});
+      py::array_t<uint8_t> state({n});
+      if (n) {
+        std::memcpy(dist.mutable_data(), r.dist.data(), r.dist.size() * sizeof(float));
+        std::memcpy(grad.mutable_data(), r.grad.data(), r.grad.size() * sizeof(float));
+        std::memcpy(rgbw.mutable_data(), r.rgbw.data(), r.rgbw.size());
+        std::memcpy(state.mutable_data(), r.state.data(), r.state.size());
+      }
+      return py::make_tuple(dist, grad, rgbw, state);
+    }, py::arg("points"), py::arg("smooth") = false, py::arg("sensor_frame") = false)
     // not part of the reference binding: the pose of a depth image (2-D, the camera's rows x cols, metres) by ICP against the map,
     // started from the current pose or from (t, q); returns (t [3], q [4] = qx,qy,qz,qw, info dict) and leaves the current pose
     // alone — call setCurrPose(t, q) with the result before setDepthImage / compute
