@@ -163,6 +163,21 @@ class MrhQueryParams(C.Structure):
     _fields_ = [("field", C.c_int32), ("outputs", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+# every symbol include/mrhash_remap.h declares (the HIP library only: the oracle has no map-to-map fusion)
+REMAP_SYMBOLS = ("mrh_resample_map mrh_fuse_map").split()
+
+
+class MrhRemapParams(C.Structure):
+    _fields_ = [("dst_voxel_size", C.c_float), ("min_weight", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class MrhRemapInfo(C.Structure):
+    _fields_ = [("source_blocks", C.c_uint64), ("candidate_blocks", C.c_uint64), ("records", C.c_uint64), ("valid_voxels", C.c_uint64), ("taken", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # every symbol include/mrhash_track.h declares (the HIP library only: the oracle does not track)
 TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device mrh_track_scan mrh_track_scan_device").split()
 TRACK_OK, TRACK_LOST = 0, 1
@@ -307,6 +322,11 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_query_points_device.argtypes = [C.c_void_p, P(MrhQueryParams), C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
         for name in QUERY_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_resample_map"):  # include/mrhash_remap.h
+        lib.mrh_resample_map.argtypes = [C.c_void_p, P(MrhRemapParams), P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_uint64), P(MrhRemapInfo)]
+        lib.mrh_fuse_map.argtypes = [C.c_void_p, C.c_void_p, P(MrhRemapParams), P(C.c_float), P(C.c_float), P(MrhRemapInfo)]
+        for name in REMAP_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_track_depth"):  # include/mrhash_track.h
         lib.mrh_track_depth.argtypes = [C.c_void_p, P(MrhTrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
@@ -881,6 +901,41 @@ class Engine:
         p, pR, pt, _keep = self._query_args(R, t, smooth, bool(d_grad), bool(d_rgbw))
         self._check(self.lib.mrh_query_points_device(self._ctx, C.byref(p), d_points or None, int(n), pR, pt, d_dist or None, d_grad or None,
                                                      d_rgbw or None, d_state or None))
+
+    # -- map-to-map fusion (include/mrhash_remap.h) ----------------------------------------------------
+    @staticmethod
+    def _pose_args(R, t):
+        F = C.POINTER(C.c_float)
+        R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        return R.ctypes.data_as(F), t.ctypes.data_as(F), (R, t)  # the last: keeps the arrays alive across the call
+
+    def resample_map_device(self, R, t, voxel_size=0.0, min_weight=0):
+        """mrh_resample_map: this map, whose frame lies at W = R P + t in the destination's world, resampled onto
+        the lattice of `voxel_size` (0 = its own).  Returns (device pointer to mrh_block_record[n], n, info dict); the records
+        are ordered by block position and belong to the context until its next resample_map / fuse_map as a source."""
+        p = MrhRemapParams(float(voxel_size), int(min_weight))
+        pR, pt, _keep = self._pose_args(R, t)
+        ptr, n, info = C.c_void_p(), C.c_uint64(), MrhRemapInfo()
+        self._check(self.lib.mrh_resample_map(self._ctx, C.byref(p), pR, pt, C.byref(ptr), C.byref(n), C.byref(info)))
+        return int(ptr.value or 0), int(n.value), info.as_dict()
+
+    def resample_map(self, R, t, voxel_size=0.0, min_weight=0):
+        """resample_map_device copied to the host: (descs, voxels [n, 512], info) with the dtypes of dump_blocks."""
+        ptr, n, info = self.resample_map_device(R, t, voxel_size, min_weight)
+        from . import hipmem
+
+        rec = np.frombuffer(hipmem.read(ptr, n * RECORD_BYTES), dtype=RECORD_DTYPE)
+        return rec["desc"].copy(), rec["voxels"].copy(), info
+
+    def fuse_map(self, src: "Engine", R, t, min_weight=0) -> dict:
+        """mrh_fuse_map: `src`, whose frame lies at W = R P + t in this map's world, resampled at this map's voxel size and
+        merged into it (MRH_UNPACK_MERGE).  Returns the info dict; `taken` = records this map took."""
+        p = MrhRemapParams(0.0, int(min_weight))
+        pR, pt, _keep = self._pose_args(R, t)
+        info = MrhRemapInfo()
+        self._check(self.lib.mrh_fuse_map(self._ctx, src._ctx, C.byref(p), pR, pt, C.byref(info)))
+        return info.as_dict()
 
     # -- tracking (include/mrhash_track.h) ------------------------------------------------------------
     def _track(self, fn, obs, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):

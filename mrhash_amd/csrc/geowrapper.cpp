@@ -652,6 +652,17 @@ GeoWrapper::PointQuery GeoWrapper::queryPoints(const float* pts, const size_t n,
   return out;
 }
 
+mrh_remap_info GeoWrapper::fuseMap(GeoWrapper& other, const std::array<float, 3>& t, const std::array<float, 4>& q, const uint32_t min_weight) {
+  mrh_remap_params p;
+  std::memset(&p, 0, sizeof p);
+  p.min_weight = min_weight;
+  const PoseRt at = split_pose(pose_from(t, q));
+  mrh_remap_info info;
+  std::memset(&info, 0, sizeof info);
+  check(mrh_fuse_map(ctx_, other.ctx_, &p, at.R, at.t, &info), "fuseMap");
+  return info;
+}
+
 GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols) { return trackDepthPose(depth, rows, cols, pose_); }
 
 GeoWrapper::TrackResult GeoWrapper::trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) {

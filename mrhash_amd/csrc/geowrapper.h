@@ -15,6 +15,7 @@
 #include "mrhash_raycast.h"
 #include "mrhash_esdf.h"
 #include "mrhash_query.h"
+#include "mrhash_remap.h"
 #include "mrhash_track.h"
 #include "mrhash_normals.h"
 
@@ -143,6 +144,12 @@ public:
     std::vector<uint8_t> rgbw, state;
   };
   PointQuery queryPoints(const float* pts, size_t n, bool smooth = false, bool sensor_frame = false);
+
+  // ---- map-to-map fusion (include/mrhash_remap.h; no reference counterpart): the map of `other`, whose frame lies
+  // at the pose (t, q) — as setCurrPose takes it — in this map's world, resampled at this map's voxel size and merged into it
+  // voxel by voxel (MRH_UNPACK_MERGE).  `other` is only read.  Blocks that either wrapper's host chunk grid has paged out take no
+  // part: only `other`'s device map is resampled, and the records merge into this wrapper's device map.
+  mrh_remap_info fuseMap(GeoWrapper& other, const std::array<float, 3>& t, const std::array<float, 4>& q, uint32_t min_weight = 0);
 
   // ---- tracking (include/mrhash_track.h; no reference counterpart): the pose of a depth image (rows x cols as
   // the camera of the last setCamera, metres) by point-to-plane ICP against the map, started from the current pose (setCurrPose)

@@ -1,6 +1,6 @@
 // mrh_blocks.h — the host side of block I/O behind the C ABI (streamer, dump, get_voxel, the multi-GPU pack / unpack / drop), each
-// entry point a driver over named stages.  dump_compact, free_compact_launch, import_pipe and pack_selected are the one launch site
-// of their kernels (mrh_comm.h packs through the last).  Included by mrh_capi.hip, same translation unit: it needs mrh_ctx's internals.
+// entry point a driver over named stages.  dump_compact, free_compact_launch, import_pipe, pack_selected and unpack_records are the
+// one launch site of their kernels (mrh_comm.h packs through pack_selected, mrh_fuse_map merges through unpack_records).  Included by mrh_capi.hip, same translation unit: it needs mrh_ctx's internals.
 #pragma once
 
 namespace {
@@ -141,6 +141,56 @@ int import_pipe(mrh_ctx* c, const mrh_block_desc* descs, const mrh_voxel* voxels
 void pack_selected(mrh_ctx* c, const int n, char* dst) {
   if (n) k_pack_records<<<n < 4096 ? n : 4096, 512, 0, c->stream>>>(c->tab, 0, n, dst);
 }
+// mrh_unpack_blocks behind its argument checks, and mrh_fuse_map (mrh_readers.h) with the records it has just resampled: n >= 1
+// records (device memory iff is_device_memory) through k_import in `mode`; the one launch site of both forms.  Blocks
+int unpack_records(mrh_ctx* c, const int mode, const mrh_block_record* records, const uint64_t n, const int is_device_memory, uint64_t* out_taken) {
+  int rc;
+  if ((rc = set_aside_flags(c))) return rc;
+  hipStream_t s = c->stream;
+  DevBuf<char> staged;  // host records (tests over gloo) are read from one staged copy
+  const char* d_rec = (const char*) records;
+  if (!is_device_memory) {
+    HIP_TRY(c, staged.alloc((size_t) n * sizeof(mrh_block_record)));
+    HIP_TRY(c, hipMemcpyAsync(staged, records, (size_t) n * sizeof(mrh_block_record), hipMemcpyHostToDevice, s));
+    d_rec = staged;
+  }
+  if (!c->d_taken) HIP_TRY(c, dev_alloc(c, c->d_taken, sizeof(u32)));
+  HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
+  const size_t room = c->halo_upper + n, cap = room + room / 2;  // the halo list takes every record of the call behind its entries
+  if (mode == MRH_UNPACK_HALO && room > c->halo_cap) {
+    if ((rc = regrow_keep(c, c->d_halo, c->halo_cap, cap, cap * sizeof(int4), c->halo_upper * sizeof(int4)))) return rc;
+  }
+  map_changed_in_bulk(c);
+  DevBuf<u32> released;  // a merge into a variance-adaptive map: the fine slots that make way for coarse records ...
+  if (mode == MRH_UNPACK_MERGE && c->tab.multi_res) {  // ... and room on the coarse free list for every coarse record of the call
+    HIP_TRY(c, released.alloc((size_t) n + 1));
+    HIP_TRY(c, hipMemsetAsync(released, 0, sizeof(u32), s));
+    k_count_coarse_records<<<64, 256, 0, s>>>(d_rec, sizeof(mrh_block_record), (int) n, c->d_taken);  // d_taken doubles as the counter
+    u32 need = 0;
+    HIP_TRY(c, hipMemcpyAsync(&need, c->d_taken, sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
+    if ((rc = ensure_coarse_units(c, need))) return rc;
+  }
+  const int grid = (int) (n < 4096 ? n : 4096);
+  const size_t stride = sizeof(mrh_block_record);
+  if (mode == MRH_UNPACK_HALO) {
+    k_import<kImportHalo><<<grid, 512, 0, s>>>(c->map, c->tab, c->fast.summary, (int) n, d_rec, stride, d_rec + sizeof(mrh_block_desc), stride, c->d_halo, c->d_taken);
+    c->halo_upper += n;
+  } else {
+    k_import<kImportMerge><<<grid, 512, 0, s>>>(c->map, c->tab, c->fast.summary, (int) n, d_rec, stride, d_rec + sizeof(mrh_block_desc), stride, nullptr, c->d_taken,
+                                                (u32*) released);
+    if (released.p) k_release_fine<<<1, 256, 0, s>>>(c->tab, released);
+  }
+  u32 taken = 0;
+  HIP_TRY(c, hipMemcpyAsync(&taken, c->d_taken, sizeof(u32), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  if (out_taken) *out_taken = taken;
+  u32 flags = 0;  // what this call raised itself is its own result
+  rc = take_device_flags(c, &flags);
+  return rc ? rc : check_device_flags(c, flags);
+}
 }  // namespace
 
 extern "C" {
@@ -264,51 +314,7 @@ int mrh_unpack_blocks(mrh_ctx* c, int mode, const mrh_block_record* records, uin
   if (!records) return fail(c, MRH_ERR_INVALID_ARG, "mrh_unpack_blocks: null argument");
   if (n > 0x7FFFFFFFull) return fail(c, MRH_ERR_CAPACITY, "mrh_unpack_blocks: %llu records in one call", (unsigned long long) n);
   if (c->pending) return fail(c, MRH_ERR_STATE, "mrh_unpack_blocks: an exchange is pending (call mrh_integrate_resume)");
-  if ((rc = set_aside_flags(c))) return rc;
-  hipStream_t s = c->stream;
-  DevBuf<char> staged;  // host records (tests over gloo) are read from one staged copy
-  const char* d_rec = (const char*) records;
-  if (!is_device_memory) {
-    HIP_TRY(c, staged.alloc((size_t) n * sizeof(mrh_block_record)));
-    HIP_TRY(c, hipMemcpyAsync(staged, records, (size_t) n * sizeof(mrh_block_record), hipMemcpyHostToDevice, s));
-    d_rec = staged;
-  }
-  if (!c->d_taken) HIP_TRY(c, dev_alloc(c, c->d_taken, sizeof(u32)));
-  HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
-  const size_t room = c->halo_upper + n, cap = room + room / 2;  // the halo list takes every record of the call behind its entries
-  if (mode == MRH_UNPACK_HALO && room > c->halo_cap) {
-    if ((rc = regrow_keep(c, c->d_halo, c->halo_cap, cap, cap * sizeof(int4), c->halo_upper * sizeof(int4)))) return rc;
-  }
-  map_changed_in_bulk(c);
-  DevBuf<u32> released;  // a merge into a variance-adaptive map: the fine slots that make way for coarse records ...
-  if (mode == MRH_UNPACK_MERGE && c->tab.multi_res) {  // ... and room on the coarse free list for every coarse record of the call
-    HIP_TRY(c, released.alloc((size_t) n + 1));
-    HIP_TRY(c, hipMemsetAsync(released, 0, sizeof(u32), s));
-    k_count_coarse_records<<<64, 256, 0, s>>>(d_rec, sizeof(mrh_block_record), (int) n, c->d_taken);  // d_taken doubles as the counter
-    u32 need = 0;
-    HIP_TRY(c, hipMemcpyAsync(&need, c->d_taken, sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipMemsetAsync(c->d_taken, 0, sizeof(u32), s));
-    if ((rc = ensure_coarse_units(c, need))) return rc;
-  }
-  const int grid = (int) (n < 4096 ? n : 4096);
-  const size_t stride = sizeof(mrh_block_record);
-  if (mode == MRH_UNPACK_HALO) {
-    k_import<kImportHalo><<<grid, 512, 0, s>>>(c->map, c->tab, c->fast.summary, (int) n, d_rec, stride, d_rec + sizeof(mrh_block_desc), stride, c->d_halo, c->d_taken);
-    c->halo_upper += n;
-  } else {
-    k_import<kImportMerge><<<grid, 512, 0, s>>>(c->map, c->tab, c->fast.summary, (int) n, d_rec, stride, d_rec + sizeof(mrh_block_desc), stride, nullptr, c->d_taken,
-                                                (u32*) released);
-    if (released.p) k_release_fine<<<1, 256, 0, s>>>(c->tab, released);
-  }
-  u32 taken = 0;
-  HIP_TRY(c, hipMemcpyAsync(&taken, c->d_taken, sizeof(u32), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipGetLastError());
-  if (out_taken) *out_taken = taken;
-  u32 flags = 0;  // what this call raised itself is its own result
-  rc = take_device_flags(c, &flags);
-  return rc ? rc : check_device_flags(c, flags);
+  return unpack_records(c, mode, records, n, is_device_memory, out_taken);
 }
 
 int mrh_drop_blocks(mrh_ctx* c, int mode, uint64_t* out_dropped) {

@@ -37,6 +37,7 @@
 #include "mrh_raycast.h"
 #include "mrh_esdf.h"
 #include "mrh_query.h"
+#include "mrh_remap.h"
 #include "mrh_track.h"
 #include "mrh_normals.h"
 #include "mrh_fast.h"

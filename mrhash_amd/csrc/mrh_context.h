@@ -439,6 +439,15 @@ struct mrh_ctx {
     char* d_out = nullptr; size_t cap = 0;
     char* h_out = nullptr; size_t h_cap = 0;
   } query;
+  // map-to-map fusion (mrh_readers.h, kernels in mrh_remap.h), grow-only — per candidate slot the two (key, value) pairs of the
+  // sort, the marks and positions of the scans, with them the sort's histogram and the scans' tile sums; two counters {valid
+  // voxels, the frame path's CTR_COMPACT while the call borrows the compact list}; the records of the last call (bytes)
+  struct Remap {
+    u64* d_keys[2] = {nullptr, nullptr}; u32* d_vals[2] = {nullptr, nullptr};
+    u64* d_marks = nullptr; u64* d_pos = nullptr; u64* d_sums = nullptr; u32* d_sort = nullptr; size_t cap = 0;  // slots
+    u64* d_count = nullptr;
+    char* d_rec = nullptr; size_t rec_cap = 0;
+  } remap;
   // tracking (mrh_readers.h, kernels in mrh_track.h), grow-only — device [model depth or range f32 | model normals 3 x f32] per
   // pixel, for scans (D15) the model's points image, and the partial slab (one row of 32 words per workgroup); pinned: the 32 sums
   // the host reads.  An observation that comes from the host — a depth image (D14) or a cloud — is staged through one pair of

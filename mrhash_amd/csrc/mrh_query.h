@@ -29,7 +29,9 @@ __device__ __forceinline__ i3 query_block_of(const Map& m, const i3 v) {
 }
 
 // The SMOOTH field's corner at world position `pos`: get_voxel_f, except that a corner in the block `b0` of corner (0, 0, 0)
-// reuses that block's table value `val0` (first: this IS corner (0, 0, 0), which resolves them).  False: not found, or weight 0
+// reuses that block's table value `val0` (first: this IS corner (0, 0, 0), which resolves them).  False: not found, or weight 0.
+// SDF = false: the weight alone is read (the validity pass of mrh_remap.h), `sdf` is left as it is
+template <bool SDF>
 __device__ __forceinline__ bool query_corner(const Map& m, const Tab& t, const Neigh& nb, const f3 pos, const bool first, i3& b0, u32& val0, float& sdf) {
   const i3 v = world_to_voxel(m.vs, pos);
   const i3 b = query_block_of(m, v);
@@ -43,11 +45,57 @@ __device__ __forceinline__ bool query_corner(const Map& m, const Tab& t, const N
   if (val == kNbAbsent) return false;
   const VoxPtr vp = vox_ptr(t, val);
   const u32 li = voxel_local_index(v, (val & kValCoarseBit) ? 1 : 0);
-  sdf = vp.sdf[li];
+  if (SDF) sdf = vp.sdf[li];
   return (vp.rgbw[li] >> 24) != 0;
 }
 
 __device__ __forceinline__ float query_lerp(const float a, const float b, const float w) { return a + w * (b - a); }
+
+// The SMOOTH field of D17 at P, h = the local voxel size at P: the eight corners ((f_x + i) h, (f_y + j) h, (f_z + k) h) through
+// query_corner.  False (dist and the gradient untouched) unless all eight are found with weight > 0; the gradient is evaluated
+// when want_grad.  k_query and k_remap_sample (mrh_remap.h) both call it
+__device__ __forceinline__ bool smooth_field(const Map& m, const Tab& t, const Neigh& nb, const f3 P, const float h, const bool want_grad, float& dist, float& gx,
+                                             float& gy, float& gz) {
+  const float ux = P.x / h, uy = P.y / h, uz = P.z / h;
+  const float fx = floorf(ux), fy = floorf(uy), fz = floorf(uz);
+  const float wx = ux - fx, wy = uy - fy, wz = uz - fz;
+  float sv[8];
+  i3 b0 = mki3(0, 0, 0);
+  u32 val0 = kNbAbsent;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const f3 pos = mk3((fx + (float) (c & 1)) * h, (fy + (float) ((c >> 1) & 1)) * h, (fz + (float) ((c >> 2) & 1)) * h);
+    sv[c] = 0.f;
+    ok = ok && query_corner<true>(m, t, nb, pos, c == 0, b0, val0, sv[c]);
+  }
+  if (!ok) return false;
+  // along x for the four (j, k), then y, then z
+  const float c00 = query_lerp(sv[0], sv[1], wx), c10 = query_lerp(sv[2], sv[3], wx), c01 = query_lerp(sv[4], sv[5], wx), c11 = query_lerp(sv[6], sv[7], wx);
+  const float c0 = query_lerp(c00, c10, wy), c1 = query_lerp(c01, c11, wy);
+  dist = query_lerp(c0, c1, wz);
+  if (want_grad) {
+    gx = query_lerp(query_lerp(sv[1] - sv[0], sv[3] - sv[2], wy), query_lerp(sv[5] - sv[4], sv[7] - sv[6], wy), wz) / h;
+    gy = query_lerp(c10 - c00, c11 - c01, wz) / h;
+    gz = (c1 - c0) / h;
+  }
+  return true;
+}
+
+// smooth_field's validity alone: all eight corners found with weight > 0 (the rgbw plane only, no interpolation)
+__device__ __forceinline__ bool smooth_valid(const Map& m, const Tab& t, const Neigh& nb, const f3 P, const float h) {
+  const float fx = floorf(P.x / h), fy = floorf(P.y / h), fz = floorf(P.z / h);
+  i3 b0 = mki3(0, 0, 0);
+  u32 val0 = kNbAbsent;
+  float unused = 0.f;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const f3 pos = mk3((fx + (float) (c & 1)) * h, (fy + (float) ((c >> 1) & 1)) * h, (fz + (float) ((c >> 2) & 1)) * h);
+    ok = ok && query_corner<false>(m, t, nb, pos, c == 0, b0, val0, unused);
+  }
+  return ok;
+}
 
 template <bool SMOOTH, bool POSED>
 __global__ __launch_bounds__(kQueryLanes) void k_query(const Map m, const Tab t, const QueryArgs q, const float* __restrict__ xyz, float* __restrict__ out_dist,
@@ -107,33 +155,9 @@ __global__ __launch_bounds__(kQueryLanes) void k_query(const Map m, const Tab t,
       } else {
         dist = 0.f;
       }
-    } else {
-      const float ux = P.x / h, uy = P.y / h, uz = P.z / h;
-      const float fx = floorf(ux), fy = floorf(uy), fz = floorf(uz);
-      const float wx = ux - fx, wy = uy - fy, wz = uz - fz;
-      float sv[8];
-      i3 b0 = mki3(0, 0, 0);
-      u32 val0 = kNbAbsent;
-      bool ok = true;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const f3 pos = mk3((fx + (float) (c & 1)) * h, (fy + (float) ((c >> 1) & 1)) * h, (fz + (float) ((c >> 2) & 1)) * h);
-        sv[c] = 0.f;
-        ok = ok && query_corner(m, t, nb, pos, c == 0, b0, val0, sv[c]);
-      }
-      if (ok) {
-        state |= MRH_QUERY_DIST;
-        // along x for the four (j, k), then y, then z
-        const float c00 = query_lerp(sv[0], sv[1], wx), c10 = query_lerp(sv[2], sv[3], wx), c01 = query_lerp(sv[4], sv[5], wx), c11 = query_lerp(sv[6], sv[7], wx);
-        const float c0 = query_lerp(c00, c10, wy), c1 = query_lerp(c01, c11, wy);
-        dist = query_lerp(c0, c1, wz);
-        if (out_grad) {
-          state |= MRH_QUERY_GRAD;
-          gx = query_lerp(query_lerp(sv[1] - sv[0], sv[3] - sv[2], wy), query_lerp(sv[5] - sv[4], sv[7] - sv[6], wy), wz) / h;
-          gy = query_lerp(c10 - c00, c11 - c01, wz) / h;
-          gz = (c1 - c0) / h;
-        }
-      }
+    } else if (smooth_field(m, t, nb, P, h, out_grad != nullptr, dist, gx, gy, gz)) {
+      state |= MRH_QUERY_DIST;
+      if (out_grad) state |= MRH_QUERY_GRAD;
     }
   }
   out_dist[i] = dist;

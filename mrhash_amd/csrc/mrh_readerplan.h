@@ -1,5 +1,5 @@
 // mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking,
-// point queries)
+// point queries, map-to-map fusion)
 // and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
 // parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
 // the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
@@ -19,6 +19,7 @@
 #include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_normals.h"
 #include "../../include/mrhash_query.h"
+#include "../../include/mrhash_remap.h"
 #include "../../include/mrhash_track.h"
 
 namespace mrh {
@@ -48,6 +49,17 @@ struct QueryArgs {
   bool smooth, posed;  // the field; the points are in the sensor frame
   uint32_t outputs;    // MRH_QUERY_* bits
   float R[9], t[3];    // sensor in world (row-major R); identity and 0 when !posed
+};
+
+// what the map-to-map kernels take (mrh_remap.h): the pose of the source frame in the destination's world, the destination
+// lattice, the range bound on the source side and the size of a source block's candidate box
+struct RemapArgs {
+  float R[9], t[3];   // W = R P + t (row-major R); the sample kernels apply the transpose to W - t
+  double F[9];        // (R^T)^-1 in binary64, row-major: W = F P + t inverts the sample kernels' P = R^T (W - t) whatever R is
+  float vs_d;         // finest voxel size of the destination lattice
+  float bound;        // (float) (1 << 20) * vs_s: a voxel is invalid unless |P_a| < bound on every axis
+  uint32_t w_min;     // max(1, min_weight)
+  int per_axis;       // destination blocks per axis a source block's candidate box holds at most (remap_per_axis)
 };
 
 // the parameters of the normal-estimation kernels (mrh_normals.h), defaults filled in
@@ -212,6 +224,86 @@ inline int query(char* msg, const char* who, const mrh_query_params* p, const bo
   out->bound = (float) (1 << 20) * voxel_size;
   out->smooth = p->field == MRH_QUERY_FIELD_SMOOTH;
   out->outputs = p->outputs;
+  return MRH_OK;
+}
+
+// ---- map-to-map fusion (include/mrhash_remap.h) ----
+
+constexpr uint64_t kRemapMaxEntries = 0x7FFFFFFFull;  // candidate slots and records of one call: what mrh_unpack_blocks takes, and 32-bit indices
+constexpr uint64_t kRemapRecordBytes = 6160;          // sizeof(mrh_block_record)
+constexpr double kRemapRotationTol = 1.0 / 1024.0;    // |R R^T - I| per entry
+
+// Destination blocks per axis that the candidate box of ONE source block can meet, ratio = vs_d / vs_s.  The box
+// is the axis-aligned bound of the block's cube, transformed: the cube has 8 source voxels a side and is grown by one on each
+// side beyond the shift limit (10), its bound is at most sqrt(3) (1 + 2^-9) times that wide (|R R^T - I| <= 2^-10); the box is
+// grown on each side by one destination voxel, and by the rounding allowance of at most half a destination voxel plus 1.75
+// source voxels (k_remap_candidates).  An interval of length L blocks meets at most floor(L) + 2 blocks.
+inline int remap_per_axis(const double ratio) {
+  const double len = (10.0 * 1.7320508075688774 * (1.0 + 1.0 / 512.0) / ratio + 2.0 * (1.5 + 1.75 / ratio)) / 8.0;
+  return (int) std::floor(len) + 2;
+}
+
+// the arguments mrh_resample_map and mrh_fuse_map share; fills the kernels' arguments.  have_out: the required out-pointers were
+// given (mrh_fuse_map has none: true).  src_*: the source context's voxel size, pending exchange and shard count.  fuse: the
+// call has a destination — same_ctx (dst == src), same_device, and dst_*: the destination's
+inline int remap(char* msg, const char* who, const mrh_remap_params* p, const float* R, const float* t, const bool have_out, const float src_vs,
+                 const int src_pending, const int src_shards, const bool fuse, const bool same_ctx, const bool same_device, const float dst_vs,
+                 const int dst_pending, const int dst_shards, mrh::RemapArgs* out) {
+  if (!p || !R || !t || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (fuse && same_ctx) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the destination is the source", who);
+  if (fuse && !same_device) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the two contexts are on different devices", who);
+  if (const int e = whole_map(msg, who, "are not resampled", src_pending, src_shards)) return e;
+  if (fuse)
+    if (const int e = whole_map(msg, who, "take no resampled map", dst_pending, dst_shards)) return e;
+  if (p->reserved[0] || p->reserved[1]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  if (p->min_weight > 255u) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: min_weight %u (0 .. 255)", who, p->min_weight);
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  double worst = 0.0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double g = 0.0;
+      for (int k = 0; k < 3; k++) g += (double) R[3 * i + k] * (double) R[3 * j + k];
+      worst = std::fmax(worst, std::fabs(g - (i == j ? 1.0 : 0.0)));
+    }
+  if (!(worst <= kRemapRotationTol)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: R is not a rotation (|R R^T - I| reaches %g)", who, worst);
+  if (!std::isfinite(p->dst_voxel_size) || p->dst_voxel_size < 0.f) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: dst_voxel_size %g", who, (double) p->dst_voxel_size);
+  if (fuse && p->dst_voxel_size != 0.f && p->dst_voxel_size != dst_vs)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: dst_voxel_size %g contradicts the destination's %g", who, (double) p->dst_voxel_size, (double) dst_vs);
+  const float vs_d = fuse ? dst_vs : (p->dst_voxel_size == 0.f ? src_vs : p->dst_voxel_size);
+  const double ratio = (double) vs_d / (double) src_vs;
+  if (!(ratio >= 0.25 && ratio <= 4.0))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: voxel sizes %g (destination) and %g (source): the ratio must lie in [1/4, 4]", who, (double) vs_d, (double) src_vs);
+  // (R^T)^-1 = cof(R^T) / det = cof(R)^T / det, in binary64.  |det| >= 0.99 under the rotation test
+  const double a = R[0], b = R[1], c = R[2], d = R[3], e = R[4], f = R[5], g = R[6], h = R[7], i = R[8];
+  const double cof[9] = {e * i - f * h, f * g - d * i, d * h - e * g, c * h - b * i, a * i - c * g, b * g - a * h, b * f - c * e, c * d - a * f, a * e - b * d};
+  const double det = a * cof[0] + b * cof[1] + c * cof[2];
+  // inverse(M)_ij = cof(M)_ji / det; for M = R^T, cof(M) = cof(R)^T, so inverse(R^T)_ij = cof(R)_ij / det
+  for (int k = 0; k < 9; k++) out->F[k] = cof[k] / det;
+  for (int k = 0; k < 9; k++) out->R[k] = R[k];
+  for (int k = 0; k < 3; k++) out->t[k] = t[k];
+  out->vs_d = vs_d;
+  out->bound = (float) (1 << 20) * src_vs;
+  out->w_min = p->min_weight > 1u ? p->min_weight : 1u;
+  out->per_axis = remap_per_axis(ratio);
+  return MRH_OK;
+}
+
+// candidate slots of a call over n_src live source blocks: per_axis^3 each, at most 2^31 - 1 in all
+inline int remap_slots(char* msg, const char* who, const uint64_t n_src, const int per_axis, uint64_t* slots) {
+  const uint64_t each = (uint64_t) per_axis * (uint64_t) per_axis * (uint64_t) per_axis;
+  if (per_axis < 1 || per_axis > 64 || n_src > kRemapMaxEntries || n_src * each > kRemapMaxEntries)
+    return refuse(msg, MRH_ERR_CAPACITY, "%s: %llu source blocks with %llu candidate slots each (limit 2^31 - 1 slots)", who, (unsigned long long) n_src, (unsigned long long) each);
+  *slots = n_src * each;
+  return MRH_OK;
+}
+
+// bytes of n records, at most 2^31 - 1 of them
+inline int remap_record_bytes(char* msg, const char* who, const uint64_t n, uint64_t* bytes) {
+  if (n > kRemapMaxEntries) return refuse(msg, MRH_ERR_CAPACITY, "%s: %llu records in one call (limit 2^31 - 1)", who, (unsigned long long) n);
+  *bytes = n * kRemapRecordBytes;  // < 2^31 * 2^13: no overflow
   return MRH_OK;
 }
 

@@ -1,9 +1,10 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
 // [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
-// [_device], mrh_track.h; the solve is mrh_tracksolve.h) and point queries (mrh_query_points[_device], mrh_query.h).  What they
+// [_device], mrh_track.h; the solve is mrh_tracksolve.h), point queries (mrh_query_points[_device], mrh_query.h) and map-to-map
+// fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records).  What they
 // share is here once: the way in (reader_enter: null context, the feature's argument plan from mrh_readerplan.h, ensure_ready) and
 // the way the blocking calls hand their result planes out of pinned memory (read_planes).  The state is mrh_ctx::ray, ::esdf,
-// ::trk and ::query.  Included by mrh_capi.hip, same translation unit: it
+// ::trk, ::query and ::remap.  Included by mrh_capi.hip, same translation unit: it
 // needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
 #pragma once
 
@@ -266,6 +267,89 @@ int launch_query(mrh_ctx* c, const QueryArgs& q, const float* d_xyz, const Query
 }
 static_assert((size_t) kQueryLanes * kQuerySlice * sizeof(u32) <= 65536, "the lane-private slices fit the static LDS limit");
 
+// ---- map-to-map fusion (include/mrhash_remap.h) --------------------------------------------------------------------------------
+
+// the argument plan of both calls (mrh_plan::remap); dst: the destination of mrh_fuse_map, nullptr for mrh_resample_map
+int remap_plan(char* msg, const char* who, mrh_ctx* src, mrh_ctx* dst, const mrh_remap_params* p, const float* R, const float* t, const bool have_out, RemapArgs* a) {
+  const bool fuse = dst != nullptr;
+  return mrh_plan::remap(msg, who, p, R, t, have_out, src->p.virtual_voxel_size, src->pending, src->map.shard_count, fuse, dst == src,
+                         fuse && dst->device == src->device, fuse ? dst->p.virtual_voxel_size : 0.f, fuse ? dst->pending : 0, fuse ? dst->map.shard_count : 1, a);
+}
+
+// exclusive scan of marks[0, n) into R.d_pos, the marked keys of `keys` in order to `out`; *count = how many (blocks)
+int remap_keep_marked(mrh_ctx* c, const u64* keys, const u32 n, u64* out, uint64_t* count) {
+  mrh_ctx::Remap& R = c->remap;
+  hipStream_t s = c->stream;
+  const u32 tiles = (n + kChainTile - 1) / kChainTile;
+  k_tile_sums_u64<<<tiles, 1024, 0, s>>>(R.d_marks, n, R.d_sums);
+  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(R.d_marks, n, R.d_sums, R.d_pos);
+  k_remap_compact<<<(n + 255) / 256, 256, 0, s>>>(keys, R.d_marks, R.d_pos, n, out);
+  u64 last[2] = {0, 0};  // the position and the mark of the last entry
+  HIP_TRY(c, hipMemcpyAsync(&last[0], R.d_pos + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&last[1], R.d_marks + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  *count = last[0] + last[1];
+  return MRH_OK;
+}
+
+// The resampling behind ensure_ready(src): candidates, sort, distinct keys, flags, kept keys, sample; the records in
+// src->remap.d_rec.  Blocks.  The live blocks come from the kSelAll selection, which borrows the frame path's compact list:
+// its counter — what mrh_stats reports of the last frame — is put back.  info->taken is left alone
+int remap_run(mrh_ctx* c, const char* who, const RemapArgs& a, const mrh_block_record** out_records, uint64_t* out_n, mrh_remap_info* info) {
+  mrh_ctx::Remap& R = c->remap;
+  hipStream_t s = c->stream;
+  *out_records = nullptr;
+  *out_n = 0;
+  info->source_blocks = info->candidate_blocks = info->records = info->valid_voxels = 0;
+  if (!R.d_count) HIP_TRY(c, dev_alloc(c, R.d_count, 2 * sizeof(u64)));
+  HIP_TRY(c, hipMemsetAsync(R.d_count, 0, 2 * sizeof(u64), s));
+  HIP_TRY(c, hipMemcpyAsync(R.d_count + 1, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToDevice, s));
+  int n_src = 0;
+  int rc = select_blocks(c, kSelAll, 0, &n_src);
+  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], R.d_count + 1, sizeof(int), hipMemcpyDeviceToDevice, s));  // Tab::compact[0, n_src) stays: nothing else runs on s
+  if (rc) return rc;
+  info->source_blocks = (uint64_t) n_src;
+  if (n_src == 0) return MRH_OK;
+  char msg[mrh_plan::kMsgBytes];
+  uint64_t slots = 0;
+  if ((rc = mrh_plan::remap_slots(msg, who, (uint64_t) n_src, a.per_axis, &slots))) return fail(c, rc, "%s", msg);
+  const size_t n = (size_t) slots;
+  if (n > R.cap) {  // the previous call blocked: nothing reads the old buffers
+    const size_t cap = n + n / 4, st = (cap + kSortTile - 1) / kSortTile, ct = (cap + kChainTile - 1) / kChainTile;
+    if ((rc = regrow_all(c, R.cap, cap, {{R.d_keys[0], cap * sizeof(u64)}, {R.d_keys[1], cap * sizeof(u64)}, {R.d_vals[0], cap * sizeof(u32)}, {R.d_vals[1], cap * sizeof(u32)},
+                                         {R.d_marks, cap * sizeof(u64)}, {R.d_pos, cap * sizeof(u64)}, {R.d_sums, ct * sizeof(u64)}, {R.d_sort, (256 + 256 * st) * sizeof(u32)}}, false)))
+      return rc;
+    HIP_TRY(c, hipMemsetAsync(R.d_vals[0], 0, cap * sizeof(u32), s));  // the sort carries values along; nothing reads them
+  }
+  k_remap_candidates<<<((u32) n_src + 255) / 256, 256, 0, s>>>(c->map, c->tab, a, (u32) n_src, R.d_keys[0]);
+  const int at = radix_sort_pairs<u64, u32>(s, R.d_keys, R.d_vals, nullptr, n, 64, R.d_sort, R.d_sort + 256);  // kKeyEmpty uses every bit
+  k_remap_mark_first<<<((u32) n + 255) / 256, 256, 0, s>>>(R.d_keys[at], (u32) n, R.d_marks);
+  uint64_t n_cand = 0, n_rec = 0;
+  if ((rc = remap_keep_marked(c, R.d_keys[at], (u32) n, R.d_keys[at ^ 1], &n_cand))) return rc;
+  info->candidate_blocks = n_cand;
+  if (n_cand == 0) return MRH_OK;
+  const u64* cand = R.d_keys[at ^ 1];
+  k_remap_flags<<<(unsigned) std::min<uint64_t>(n_cand, 8192), kRemapLanes, 0, s>>>(c->map, c->tab, a, cand, (u32) n_cand, R.d_marks, R.d_count);
+  if ((rc = remap_keep_marked(c, cand, (u32) n_cand, R.d_keys[at], &n_rec))) return rc;
+  u64 valid = 0;
+  HIP_TRY(c, hipMemcpyAsync(&valid, R.d_count, sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  info->records = n_rec;
+  info->valid_voxels = valid;
+  if (n_rec == 0) return MRH_OK;
+  uint64_t bytes = 0;
+  if ((rc = mrh_plan::remap_record_bytes(msg, who, n_rec, &bytes))) return fail(c, rc, "%s", msg);
+  const size_t room = (size_t) (bytes + bytes / 4);  // the previous call blocked: nothing reads the old buffer
+  if (bytes > R.rec_cap && (rc = regrow(c, R.d_rec, R.rec_cap, room, room, false))) return rc;
+  k_remap_sample<<<(unsigned) std::min<uint64_t>(n_rec, 8192), kRemapLanes, 0, s>>>(c->map, c->tab, a, R.d_keys[at], (u32) n_rec, R.d_rec);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  *out_records = (const mrh_block_record*) R.d_rec;
+  *out_n = n_rec;
+  return MRH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -378,6 +462,37 @@ int mrh_query_points_device(mrh_ctx* c, const mrh_query_params* p, const float* 
   const int rc = query_enter(c, "mrh_query_points_device", p, d_xyz != nullptr, d_dist && d_state, n, R_row_major, t, &q);
   if (rc || n == 0) return rc;
   return launch_query(c, q, d_xyz, QueryOut{d_dist, (p->outputs & MRH_QUERY_GRADIENT) ? d_grad : nullptr, (p->outputs & MRH_QUERY_COLOUR) ? d_rgbw : nullptr, d_state});
+}
+
+int mrh_resample_map(mrh_ctx* src, const mrh_remap_params* p, const float R_row_major[9], const float t[3], const mrh_block_record** out_records, uint64_t* out_n,
+                     mrh_remap_info* out_info) {
+  const char* who = "mrh_resample_map";
+  RemapArgs a;
+  int rc = reader_enter(src, who, [&](char* msg) { return remap_plan(msg, who, src, nullptr, p, R_row_major, t, out_records && out_n, &a); });
+  if (rc) return rc;
+  mrh_remap_info info = {};
+  rc = remap_run(src, who, a, out_records, out_n, &info);
+  if (out_info) *out_info = info;
+  return rc;
+}
+
+int mrh_fuse_map(mrh_ctx* dst, mrh_ctx* src, const mrh_remap_params* p, const float R_row_major[9], const float t[3], mrh_remap_info* out_info) {
+  const char* who = "mrh_fuse_map";
+  if (!dst || !src) return dst ? fail(dst, MRH_ERR_INVALID_ARG, "%s: null argument", who) : MRH_ERR_INVALID_ARG;
+  RemapArgs a;
+  char msg[mrh_plan::kMsgBytes];
+  int rc = remap_plan(msg, who, src, dst, p, R_row_major, t, true, &a);
+  if (rc) return fail(dst, rc, "%s", msg);
+  if ((rc = ensure_ready(dst, who))) return rc;
+  if ((rc = ensure_ready(src, who))) return fail(dst, rc, "%s (source): %s", who, src->err.c_str());
+  mrh_remap_info info = {};
+  const mrh_block_record* records = nullptr;
+  uint64_t n = 0;
+  rc = remap_run(src, who, a, &records, &n, &info);  // it blocks: src's stream is drained before dst's stream reads the records
+  if (rc) rc = fail(dst, rc, "%s (source): %s", who, src->err.c_str());
+  else if (n) rc = unpack_records(dst, MRH_UNPACK_MERGE, records, n, 1, &info.taken);
+  if (out_info) *out_info = info;
+  return rc;
 }
 
 }  // extern "C"

@@ -245,6 +245,18 @@ PYBIND11_MODULE(pygeowrapper, m) {
       }
       return py::make_tuple(dist, grad, rgbw, state);
     }, py::arg("points"), py::arg("smooth") = false, py::arg("sensor_frame") = false)
+    // not part of the reference binding: the map of `other`, whose frame lies at the pose (t, q) in this map's world, resampled at
+    // this map's voxel size and merged into it.  Returns the counts of mrh_remap_info as a dict.  Blocks paged out to
+    // either wrapper's host chunk grid take no part
+    .def("fuseMap", [](GeoWrapper& g, GeoWrapper& other, py::array_t<float, py::array::c_style | py::array::forcecast> t,
+                       py::array_t<float, py::array::c_style | py::array::forcecast> q, uint32_t min_weight) {
+      if (t.size() != 3 || q.size() != 4) throw std::runtime_error("GeoWrapper::fuseMap|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+      const mrh_remap_info r = g.fuseMap(other, {t.data()[0], t.data()[1], t.data()[2]}, {q.data()[0], q.data()[1], q.data()[2], q.data()[3]}, min_weight);
+      py::dict d;
+      d["source_blocks"] = r.source_blocks; d["candidate_blocks"] = r.candidate_blocks; d["records"] = r.records;
+      d["valid_voxels"] = r.valid_voxels; d["taken"] = r.taken;
+      return d;
+    }, py::arg("other"), py::arg("t"), py::arg("q"), py::arg("min_weight") = 0)
     // not part of the reference binding: the pose of a depth image (2-D, the camera's rows x cols, metres) by ICP against the map,
     // started from the current pose or from (t, q); returns (t [3], q [4] = qx,qy,qz,qw, info dict) and leaves the current pose
     // alone — call setCurrPose(t, q) with the result before setDepthImage / compute
