@@ -3,8 +3,9 @@
  * into a second map (libmrhash_hip.so, kernels in mrhash_amd/csrc/mrh_remap.h).
  *
  * A second session, a second robot, a sub-map closed by a loop closure or a frame-sharded rank whose poses were corrected
- * afterwards each leave a second map whose frame differs from the first by a rigid transform — the one mrh_track_depth /
- * mrh_track_scan estimate.  mrh_unpack_blocks(MRH_UNPACK_MERGE) folds sub-maps only when their lattices coincide;
+ * afterwards each leave a second map whose frame differs from the first by a rigid transform — the one mrh_align_map
+ * (mrhash_align.h) estimates from the two maps; mrh_track_depth / mrh_track_scan estimate the pose of one frame, not of a map.
+ * mrh_unpack_blocks(MRH_UNPACK_MERGE) folds sub-maps only when their lattices coincide;
  * mrh_resample_map evaluates the source map on the destination's lattice and hands the result over as mrh_block_record, in the
  * order mrh_pack_blocks produces, so that the existing merge takes it.  mrh_fuse_map is the two in one call.  The reference has
  * no such call; the definition is this project's.  DESIGN.md D18 is the normative statement, tests/remap_ref.py restates it in

@@ -178,6 +178,26 @@ class MrhRemapInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+# every symbol include/mrhash_align.h declares (the HIP library only: the oracle has no registration)
+ALIGN_SYMBOLS = ("mrh_align_map").split()
+ALIGN_OK, ALIGN_LOST = 0, 1
+
+
+class MrhAlignParams(C.Structure):
+    _fields_ = [("band", C.c_float), ("dist_max", C.c_float), ("iterations", C.c_int32), ("min_samples", C.c_uint32), ("min_weight", C.c_uint32),
+                ("pivot", C.c_float * 3), ("extent", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class MrhAlignInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations_done", C.c_int32), ("source_blocks", C.c_uint64), ("samples", C.c_uint64), ("accepted", C.c_uint64),
+                ("rms", C.c_double), ("pivot", C.c_float * 3), ("extent", C.c_float), ("sums", C.c_int64 * 32)]
+
+    def as_dict(self) -> dict:
+        return dict(status=int(self.status), iterations_done=int(self.iterations_done), source_blocks=int(self.source_blocks), samples=int(self.samples),
+                    accepted=int(self.accepted), rms=float(self.rms), pivot=np.array(self.pivot[:], dtype=np.float32), extent=np.float32(self.extent),
+                    sums=np.array(self.sums[:], dtype=np.int64))
+
+
 # every symbol include/mrhash_track.h declares (the HIP library only: the oracle does not track)
 TRACK_SYMBOLS = ("mrh_track_depth mrh_track_depth_device mrh_track_scan mrh_track_scan_device").split()
 TRACK_OK, TRACK_LOST = 0, 1
@@ -328,6 +348,9 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_fuse_map.argtypes = [C.c_void_p, C.c_void_p, P(MrhRemapParams), P(C.c_float), P(C.c_float), P(MrhRemapInfo)]
         for name in REMAP_SYMBOLS:
             getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_align_map"):  # include/mrhash_align.h
+        lib.mrh_align_map.argtypes = [C.c_void_p, C.c_void_p, P(MrhAlignParams), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(MrhAlignInfo)]
+        lib.mrh_align_map.restype = C.c_int
     if hasattr(lib, "mrh_track_depth"):  # include/mrhash_track.h
         lib.mrh_track_depth.argtypes = [C.c_void_p, P(MrhTrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                         P(MrhTrackInfo)]
@@ -936,6 +959,21 @@ class Engine:
         info = MrhRemapInfo()
         self._check(self.lib.mrh_fuse_map(self._ctx, src._ctx, C.byref(p), pR, pt, C.byref(info)))
         return info.as_dict()
+
+    # -- map-to-map registration (include/mrhash_align.h) ----------------------------------------------
+    def align_map(self, src: "Engine", R, t, band=0.0, dist_max=0.0, iterations=0, min_samples=0, min_weight=0, pivot=None, extent=0.0):
+        """mrh_align_map: estimates the pose W = R P + t of `src`'s frame in this map's world from the start (R, t),
+        by SDF-to-SDF registration of the two maps; what fuse_map then takes.  Blocks.  0 = the default of a parameter; `pivot`
+        and `extent` crop the source's samples to a cube and set the lever (extent 0: both automatic).  Returns (R float32 [3, 3],
+        t float32 [3], info) with info = {status (ALIGN_OK / ALIGN_LOST), iterations_done, source_blocks, samples, accepted, rms,
+        pivot, extent, sums int64 [32]}; a lost alignment returns the pose from before the step that failed."""
+        c = np.zeros(3, np.float32) if pivot is None else np.ascontiguousarray(pivot, dtype=np.float32).reshape(3)
+        p = MrhAlignParams(band, dist_max, int(iterations), int(min_samples), int(min_weight), (C.c_float * 3)(*[float(x) for x in c]), extent)
+        pR, pt, _keep = self._pose_args(R, t)
+        out_R, out_t, info = np.zeros(9, np.float32), np.zeros(3, np.float32), MrhAlignInfo()
+        F = C.POINTER(C.c_float)
+        self._check(self.lib.mrh_align_map(self._ctx, src._ctx, C.byref(p), pR, pt, out_R.ctypes.data_as(F), out_t.ctypes.data_as(F), C.byref(info)))
+        return out_R.reshape(3, 3), out_t, info.as_dict()
 
     # -- tracking (include/mrhash_track.h) ------------------------------------------------------------
     def _track(self, fn, obs, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step, dist_max, iterations, min_pixels):

@@ -706,6 +706,21 @@ GeoWrapper::TrackResult GeoWrapper::trackPose(const char* who, const float* dept
   return out;
 }
 
+GeoWrapper::AlignResult GeoWrapper::alignMap(GeoWrapper& other, const std::array<float, 3>& t, const std::array<float, 4>& q, const int iterations, const uint32_t min_weight) {
+  mrh_align_params p;
+  std::memset(&p, 0, sizeof p);
+  p.iterations = iterations;
+  p.min_weight = min_weight;
+  const PoseRt at = split_pose(pose_from(t, q));
+  float out_R[9], out_t[3];
+  AlignResult out;
+  std::memset(&out.info, 0, sizeof out.info);
+  check(mrh_align_map(ctx_, other.ctx_, &p, at.R, at.t, out_R, out_t, &out.info), "alignMap");
+  out.t = {out_t[0], out_t[1], out_t[2]};
+  out.q = quat_from(out_R);
+  return out;
+}
+
 GeoWrapper::TrackResult GeoWrapper::trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose) {
   requireCamera("trackDepthImage", MRH_CAMERA_PINHOLE);
   if (!depth || rows != (size_t) camera_rows_ || cols != (size_t) camera_cols_)

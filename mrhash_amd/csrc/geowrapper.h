@@ -16,6 +16,7 @@
 #include "mrhash_esdf.h"
 #include "mrhash_query.h"
 #include "mrhash_remap.h"
+#include "mrhash_align.h"
 #include "mrhash_track.h"
 #include "mrhash_normals.h"
 
@@ -150,6 +151,18 @@ public:
   // voxel by voxel (MRH_UNPACK_MERGE).  `other` is only read.  Blocks that either wrapper's host chunk grid has paged out take no
   // part: only `other`'s device map is resampled, and the records merge into this wrapper's device map.
   mrh_remap_info fuseMap(GeoWrapper& other, const std::array<float, 3>& t, const std::array<float, 4>& q, uint32_t min_weight = 0);
+
+  // ---- map-to-map registration (include/mrhash_align.h; no reference counterpart): the pose of `other`'s frame in
+  // this map's world, estimated from the two maps alone, started from (t, q) — as fuseMap takes it — with every parameter of
+  // mrh_align_params at its default unless given.  Both wrappers are only read; blocks paged out to either host chunk grid take no
+  // part.  Returns the pose as fuseMap takes it: alignMap -> fuseMap closes the loop.  info.status == MRH_ALIGN_LOST: (t, q) is the
+  // pose from before the step that failed.
+  struct AlignResult {
+    std::array<float, 3> t;
+    std::array<float, 4> q;  // qx, qy, qz, qw
+    mrh_align_info info;
+  };
+  AlignResult alignMap(GeoWrapper& other, const std::array<float, 3>& t, const std::array<float, 4>& q, int iterations = 0, uint32_t min_weight = 0);
 
   // ---- tracking (include/mrhash_track.h; no reference counterpart): the pose of a depth image (rows x cols as
   // the camera of the last setCamera, metres) by point-to-plane ICP against the map, started from the current pose (setCurrPose)

@@ -448,6 +448,18 @@ struct mrh_ctx {
     u64* d_count = nullptr;
     char* d_rec = nullptr; size_t rec_cap = 0;
   } remap;
+  // map-to-map registration (mrh_readers.h, kernels in mrh_align.h), grow-only — as the source of a call: per live block the
+  // count of its samples, their position (the scan), the tile sums of the scan and the block's integer box (lo, hi); the sample
+  // list, 16 bytes each; pinned {lo, hi} of the whole list and its length.  As the destination: the partial slab (one row of 32
+  // words per workgroup) and the pinned 32 sums the host reads
+  struct Align {
+    u64* d_counts = nullptr; u64* d_pos = nullptr; u64* d_sums = nullptr; int4* d_boxes = nullptr; size_t cap = 0;  // blocks
+    float4* d_samples = nullptr; size_t smp_cap = 0;   // samples
+    int4* h_box = nullptr;                             // {lo, hi} of the accepted voxel coordinates
+    int* d_keep = nullptr;                             // the frame path's CTR_COMPACT while the call borrows the compact list
+    long long* d_slab = nullptr; size_t slab_cap = 0;  // rows
+    long long* h_sums = nullptr;
+  } align;
   // tracking (mrh_readers.h, kernels in mrh_track.h), grow-only — device [model depth or range f32 | model normals 3 x f32] per
   // pixel, for scans (D15) the model's points image, and the partial slab (one row of 32 words per workgroup); pinned: the 32 sums
   // the host reads.  An observation that comes from the host — a depth image (D14) or a cloud — is staged through one pair of

@@ -1,5 +1,5 @@
 // mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking,
-// point queries, map-to-map fusion)
+// point queries, map-to-map fusion and registration)
 // and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
 // parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
 // the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
@@ -16,6 +16,7 @@
 #include <cstdio>
 
 #include "../../include/mrh_softmath.h"
+#include "../../include/mrhash_align.h"
 #include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_normals.h"
 #include "../../include/mrhash_query.h"
@@ -60,6 +61,25 @@ struct RemapArgs {
   float bound;        // (float) (1 << 20) * vs_s: a voxel is invalid unless |P_a| < bound on every axis
   uint32_t w_min;     // max(1, min_weight)
   int per_axis;       // destination blocks per axis a source block's candidate box holds at most (remap_per_axis)
+};
+
+// what k_align_gather takes (mrh_align.h): the pose-independent gates of a source cell
+struct AlignGather {
+  float vs_s;         // finest voxel size of the source
+  float band;         // a cell needs fabsf(sdf) < band
+  uint32_t w_min;     // ... and weight >= w_min = max(1, min_weight)
+  bool crop;          // the caller gave pivot and extent: fabsf(P_a - c_a) <= extent on every axis
+  float c[3], extent;
+};
+
+// what k_align_linearise takes (mrh_align.h): the estimate the linearisation is taken at and the gates of D19
+struct AlignLin {
+  float R[9], tau[3];  // R32 and tau32 = (float) (R c + t)
+  float c[3];          // the pivot, source frame
+  float band, dist_max;
+  float s_a;           // mrh_track::angle_scale(extent)
+  float bound;         // (float) (1 << 20) * vs_d: a sample is rejected unless |W_a| < bound on every axis
+  uint32_t n;          // samples, 1 .. 2^26
 };
 
 // the parameters of the normal-estimation kernels (mrh_normals.h), defaults filled in
@@ -233,6 +253,23 @@ constexpr uint64_t kRemapMaxEntries = 0x7FFFFFFFull;  // candidate slots and rec
 constexpr uint64_t kRemapRecordBytes = 6160;          // sizeof(mrh_block_record)
 constexpr double kRemapRotationTol = 1.0 / 1024.0;    // |R R^T - I| per entry
 
+// a pose (R, t) that is finite and whose R is a rotation or a reflection: |R R^T - I| <= 2^-10 in every entry
+inline int rigid_pose(char* msg, const char* who, const float* R, const float* t) {
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  double worst = 0.0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      double g = 0.0;
+      for (int k = 0; k < 3; k++) g += (double) R[3 * i + k] * (double) R[3 * j + k];
+      worst = std::fmax(worst, std::fabs(g - (i == j ? 1.0 : 0.0)));
+    }
+  if (!(worst <= kRemapRotationTol)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: R is not a rotation (|R R^T - I| reaches %g)", who, worst);
+  return MRH_OK;
+}
+
 // Destination blocks per axis that the candidate box of ONE source block can meet, ratio = vs_d / vs_s.  The box
 // is the axis-aligned bound of the block's cube, transformed: the cube has 8 source voxels a side and is grown by one on each
 // side beyond the shift limit (10), its bound is at most sqrt(3) (1 + 2^-9) times that wide (|R R^T - I| <= 2^-10); the box is
@@ -257,18 +294,7 @@ inline int remap(char* msg, const char* who, const mrh_remap_params* p, const fl
     if (const int e = whole_map(msg, who, "take no resampled map", dst_pending, dst_shards)) return e;
   if (p->reserved[0] || p->reserved[1]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
   if (p->min_weight > 255u) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: min_weight %u (0 .. 255)", who, p->min_weight);
-  for (int i = 0; i < 9; i++)
-    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
-  for (int i = 0; i < 3; i++)
-    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
-  double worst = 0.0;
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      double g = 0.0;
-      for (int k = 0; k < 3; k++) g += (double) R[3 * i + k] * (double) R[3 * j + k];
-      worst = std::fmax(worst, std::fabs(g - (i == j ? 1.0 : 0.0)));
-    }
-  if (!(worst <= kRemapRotationTol)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: R is not a rotation (|R R^T - I| reaches %g)", who, worst);
+  if (const int e = rigid_pose(msg, who, R, t)) return e;
   if (!std::isfinite(p->dst_voxel_size) || p->dst_voxel_size < 0.f) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: dst_voxel_size %g", who, (double) p->dst_voxel_size);
   if (fuse && p->dst_voxel_size != 0.f && p->dst_voxel_size != dst_vs)
     return refuse(msg, MRH_ERR_INVALID_ARG, "%s: dst_voxel_size %g contradicts the destination's %g", who, (double) p->dst_voxel_size, (double) dst_vs);
@@ -305,6 +331,74 @@ inline int remap_record_bytes(char* msg, const char* who, const uint64_t n, uint
   if (n > kRemapMaxEntries) return refuse(msg, MRH_ERR_CAPACITY, "%s: %llu records in one call (limit 2^31 - 1)", who, (unsigned long long) n);
   *bytes = n * kRemapRecordBytes;  // < 2^31 * 2^13: no overflow
   return MRH_OK;
+}
+
+// ---- map-to-map registration (include/mrhash_align.h) ----
+
+// One registration call with its defaults filled in
+struct Align {
+  float band, dist_max;
+  int iterations;
+  uint32_t min_samples, w_min;
+  bool crop;               // the caller gave pivot and extent
+  float pivot[3], extent;  // the caller's when crop, else zeros until align_auto_pivot
+};
+// have_out: both pose outputs were given.  same_ctx: dst == src.  *_truncation: the contexts' sdf_truncation, for the default
+// band.  The order: null argument -> dst == src -> devices -> pending, sharded (source, then destination) -> reserved words ->
+// min_weight -> band -> dist_max -> iterations -> pivot -> extent -> the pose
+inline int align(char* msg, const char* who, const mrh_align_params* p, const float* R, const float* t, const bool have_out, const bool same_ctx,
+                 const bool same_device, const float src_truncation, const int src_pending, const int src_shards, const float dst_truncation,
+                 const int dst_pending, const int dst_shards, Align* out) {
+  if (!p || !R || !t || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (same_ctx) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the destination is the source", who);
+  if (!same_device) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the two contexts are on different devices", who);
+  if (const int e = whole_map(msg, who, "are not aligned", src_pending, src_shards)) return e;
+  if (const int e = whole_map(msg, who, "are not aligned to", dst_pending, dst_shards)) return e;
+  if (p->reserved[0] || p->reserved[1] || p->reserved[2]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  if (p->min_weight > 255u) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: min_weight %u (0 .. 255)", who, p->min_weight);
+  out->band = p->band == 0.f ? std::fmin(src_truncation, dst_truncation) : p->band;
+  if (!(out->band > 0.f && out->band <= 1.f)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the band must lie in (0, 1] m (band %g)", who, (double) out->band);
+  out->dist_max = p->dist_max == 0.f ? std::fmin(out->band, 1.f) : p->dist_max;
+  if (!(out->dist_max > 0.f && out->dist_max <= 1.f))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the gate must lie in (0, 1] m (dist_max %g)", who, (double) out->dist_max);
+  if (p->iterations < 0 || p->iterations > MRH_ALIGN_MAX_ITERATIONS)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %d iterations (1 .. %d, 0 = 10)", who, p->iterations, MRH_ALIGN_MAX_ITERATIONS);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(p->pivot[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pivot is not finite", who);
+  if (!std::isfinite(2.0f * p->extent) || p->extent < 0.f) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: extent %g", who, (double) p->extent);  // 2 extent: the lever
+  if (const int e = rigid_pose(msg, who, R, t)) return e;
+  out->iterations = p->iterations ? p->iterations : 10;
+  out->min_samples = p->min_samples ? p->min_samples : 64u;
+  out->w_min = p->min_weight > 1u ? p->min_weight : 1u;
+  out->crop = p->extent > 0.f;
+  for (int i = 0; i < 3; i++) out->pivot[i] = out->crop ? p->pivot[i] : 0.f;
+  out->extent = p->extent;
+  return MRH_OK;
+}
+
+// the sample list of one call: at most 2^26 entries of 16 bytes (the bounds of the 64-bit sums, mrhash_align.h)
+inline int align_sample_bytes(char* msg, const char* who, const uint64_t n, uint64_t* bytes) {
+  if (n > (uint64_t) MRH_ALIGN_MAX_SAMPLES) return refuse(msg, MRH_ERR_CAPACITY, "%s: %llu source samples in one call (limit 2^26)", who, (unsigned long long) n);
+  *bytes = n * 16ull;
+  return MRH_OK;
+}
+
+// the automatic pivot and extent from the integer box lo, hi of the accepted voxel coordinates (D19)
+inline void align_auto_pivot(const int lo[3], const int hi[3], const float vs_s, float c[3], float* extent) {
+  int64_t half = 0;
+  for (int a = 0; a < 3; a++) {
+    c[a] = (float) (((int64_t) lo[a] + (int64_t) hi[a]) >> 1) * vs_s;
+    half = std::max(half, ((int64_t) hi[a] - (int64_t) lo[a]) / 2);
+  }
+  *extent = (float) (half + 1) * vs_s;
+}
+
+// tau = R c + t and back, binary64, each row ((R_i0 c_x + R_i1 c_y) + R_i2 c_z) (+ t_i | subtracted from tau_i)
+inline void align_tau(const double R[9], const float c[3], const double t[3], double tau[3]) {
+  for (int i = 0; i < 3; i++) tau[i] = ((R[3 * i] * (double) c[0] + R[3 * i + 1] * (double) c[1]) + R[3 * i + 2] * (double) c[2]) + t[i];
+}
+inline void align_t(const double R[9], const float c[3], const double tau[3], double t[3]) {
+  for (int i = 0; i < 3; i++) t[i] = tau[i] - ((R[3 * i] * (double) c[0] + R[3 * i + 1] * (double) c[1]) + R[3 * i + 2] * (double) c[2]);
 }
 
 // the normals' parameter block (null: every default) with its defaults filled in, as the kernels take it.  n: points of the scan;

@@ -1,10 +1,11 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
 // [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
 // [_device], mrh_track.h; the solve is mrh_tracksolve.h), point queries (mrh_query_points[_device], mrh_query.h) and map-to-map
-// fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records).  What they
+// fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map
+// registration (mrh_align_map, mrh_align.h; the sums, the solve and the update are the tracker's).  What they
 // share is here once: the way in (reader_enter: null context, the feature's argument plan from mrh_readerplan.h, ensure_ready) and
 // the way the blocking calls hand their result planes out of pinned memory (read_planes).  The state is mrh_ctx::ray, ::esdf,
-// ::trk, ::query and ::remap.  Included by mrh_capi.hip, same translation unit: it
+// ::trk, ::query, ::remap and ::align.  Included by mrh_capi.hip, same translation unit: it
 // needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
 #pragma once
 
@@ -350,6 +351,94 @@ int remap_run(mrh_ctx* c, const char* who, const RemapArgs& a, const mrh_block_r
   return MRH_OK;
 }
 
+// ---- map-to-map registration (include/mrhash_align.h) ----------------------------------------------------------------------------
+
+// The source half behind ensure_ready(src): the live blocks (the kSelAll selection borrows the frame path's compact list as
+// remap_run does, its counter is put back), count, scan, box, emit; the samples in src->align.d_samples.  Fills the automatic
+// pivot and extent into `plan`.  Blocks: src's stream is drained when it returns.  Errors are reported on src
+int align_gather(mrh_ctx* c, const char* who, mrh_plan::Align& plan, uint64_t* n_blocks, uint64_t* n_samples) {
+  mrh_ctx::Align& A = c->align;
+  hipStream_t s = c->stream;
+  *n_blocks = *n_samples = 0;
+  if (!A.d_keep) HIP_TRY(c, dev_alloc(c, A.d_keep, sizeof(int)));
+  if (!A.h_box) HIP_TRY(c, pinned_alloc(c, A.h_box, 2 * sizeof(int4)));
+  HIP_TRY(c, hipMemcpyAsync(A.d_keep, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToDevice, s));
+  int n_src = 0;
+  int rc = select_blocks(c, kSelAll, 0, &n_src);
+  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], A.d_keep, sizeof(int), hipMemcpyDeviceToDevice, s));  // Tab::compact[0, n_src) stays: nothing else runs on s
+  if (rc) return rc;
+  *n_blocks = (uint64_t) n_src;
+  if (n_src == 0) return MRH_OK;
+  const u32 n = (u32) n_src, tiles = (n + kChainTile - 1) / kChainTile, grid = std::min<u32>(n, 8192u);
+  if ((size_t) n > A.cap) {  // the previous call blocked: nothing reads the old buffers
+    const size_t cap = (size_t) n + n / 4, ct = (cap + kChainTile - 1) / kChainTile;
+    if ((rc = regrow_all(c, A.cap, cap, {{A.d_counts, cap * sizeof(u64)}, {A.d_pos, cap * sizeof(u64)}, {A.d_sums, ct * sizeof(u64)}, {A.d_boxes, cap * 2 * sizeof(int4)}}, false)))
+      return rc;
+  }
+  AlignGather g;
+  g.vs_s = c->map.vs; g.band = plan.band; g.w_min = plan.w_min; g.crop = plan.crop; g.extent = plan.extent;
+  for (int i = 0; i < 3; i++) g.c[i] = plan.pivot[i];
+  k_align_gather<false><<<grid, kAlignGatherLanes, 0, s>>>(c->tab, g, n, A.d_counts, A.d_boxes, nullptr, nullptr, 0);
+  k_tile_sums_u64<<<tiles, 1024, 0, s>>>(A.d_counts, n, A.d_sums);
+  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(A.d_counts, n, A.d_sums, A.d_pos);
+  k_align_box<<<1, 1024, 0, s>>>(A.d_boxes, n, A.h_box);
+  u64 last[2] = {0, 0};  // the position and the count of the last block
+  HIP_TRY(c, hipMemcpyAsync(&last[0], A.d_pos + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&last[1], A.d_counts + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));  // k_align_box wrote the box into pinned memory
+  HIP_TRY(c, hipGetLastError());
+  const uint64_t total = last[0] + last[1];
+  char msg[mrh_plan::kMsgBytes];
+  uint64_t bytes = 0;
+  if ((rc = mrh_plan::align_sample_bytes(msg, who, total, &bytes))) return fail(c, rc, "%s", msg);
+  *n_samples = total;
+  if (total == 0) return MRH_OK;
+  if (!plan.crop) {
+    const volatile int4* hb = A.h_box;
+    const int lo[3] = {hb[0].x, hb[0].y, hb[0].z}, hi[3] = {hb[1].x, hb[1].y, hb[1].z};
+    mrh_plan::align_auto_pivot(lo, hi, c->map.vs, plan.pivot, &plan.extent);
+  }
+  const size_t room = (size_t) (total + total / 4);  // the previous call blocked: nothing reads the old buffer
+  if ((size_t) total > A.smp_cap && (rc = regrow(c, A.d_samples, A.smp_cap, room, room * sizeof(float4), false))) return rc;
+  k_align_gather<true><<<grid, kAlignGatherLanes, 0, s>>>(c->tab, g, n, nullptr, nullptr, A.d_pos, A.d_samples, (u64) total);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+
+// The destination half: per iteration k_align_linearise on dst's stream with dst's Map / Tab, k_track_finish, the 256-byte
+// read-back from pinned memory, and solve + update on the host, as track_iterate.  (R, tau): the state, updated in place; sums: of
+// the last linearisation.  *done: updates applied; returns MRH_ALIGN_* or an error
+int align_iterate(mrh_ctx* c, const mrh_plan::Align& plan, const float4* d_samples, const uint64_t n, double R[9], double tau[3],
+                  int64_t sums[mrh_track::kSumWords], int* done) {
+  mrh_ctx::Align& A = c->align;
+  const size_t n_rows = (size_t) ((n + kAlignLanes - 1) / kAlignLanes);
+  int e = regrow(c, A.d_slab, A.slab_cap, n_rows, n_rows * mrh_track::kSumWords * sizeof(i64), false);  // the previous call blocked
+  if (e) return e;
+  if (!A.h_sums) HIP_TRY(c, pinned_alloc(c, A.h_sums, mrh_track::kSumWords * sizeof(i64)));
+  AlignLin k;
+  for (int i = 0; i < 3; i++) k.c[i] = plan.pivot[i];
+  k.band = plan.band; k.dist_max = plan.dist_max;
+  k.s_a = mrh_track::angle_scale(plan.extent);
+  k.bound = (float) (1 << 20) * c->map.vs;
+  k.n = (uint32_t) n;
+  for (int it = 0; it < plan.iterations; it++) {
+    for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
+    for (int i = 0; i < 3; i++) k.tau[i] = (float) tau[i];
+    k_align_linearise<<<(unsigned) n_rows, kAlignLanes, 0, c->stream>>>(c->map, c->tab, k, d_samples, A.d_slab);
+    k_track_finish<<<1, 1024, 0, c->stream>>>(A.d_slab, (int) n_rows, A.h_sums);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
+    for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) A.h_sums)[i];
+    double xi[6];
+    if (!mrh_track::solve(sums, k.s_a, plan.min_samples, xi)) return MRH_ALIGN_LOST;
+    mrh_track::update(R, tau, xi);
+    ++*done;
+  }
+  return MRH_ALIGN_OK;
+}
+static_assert(((uint64_t) MRH_ALIGN_MAX_SAMPLES + kAlignLanes - 1) / kAlignLanes <= 0x7FFFFFFFull, "the slab's rows fit k_track_finish's int");
+
 }  // namespace
 
 extern "C" {
@@ -493,6 +582,46 @@ int mrh_fuse_map(mrh_ctx* dst, mrh_ctx* src, const mrh_remap_params* p, const fl
   else if (n) rc = unpack_records(dst, MRH_UNPACK_MERGE, records, n, 1, &info.taken);
   if (out_info) *out_info = info;
   return rc;
+}
+
+int mrh_align_map(mrh_ctx* dst, mrh_ctx* src, const mrh_align_params* p, const float R_init[9], const float t_init[3], float out_R[9], float out_t[3],
+                  mrh_align_info* out_info) {
+  const char* who = "mrh_align_map";
+  if (!dst || !src) return dst ? fail(dst, MRH_ERR_INVALID_ARG, "%s: null argument", who) : MRH_ERR_INVALID_ARG;
+  mrh_plan::Align plan;
+  char msg[mrh_plan::kMsgBytes];
+  int rc = mrh_plan::align(msg, who, p, R_init, t_init, out_R && out_t, dst == src, dst->device == src->device, src->p.sdf_truncation, src->pending,
+                           src->map.shard_count, dst->p.sdf_truncation, dst->pending, dst->map.shard_count, &plan);
+  if (rc) return fail(dst, rc, "%s", msg);
+  if ((rc = ensure_ready(dst, who))) return rc;
+  if ((rc = ensure_ready(src, who))) return fail(dst, rc, "%s (source): %s", who, src->err.c_str());
+  uint64_t n_blocks = 0, n_samples = 0;
+  rc = align_gather(src, who, plan, &n_blocks, &n_samples);  // it blocks: src's stream is drained before dst's stream reads the samples
+  if (rc) return fail(dst, rc, "%s (source): %s", who, src->err.c_str());
+  double R[9], t[3], tau[3];
+  for (int i = 0; i < 9; i++) R[i] = (double) R_init[i];
+  for (int i = 0; i < 3; i++) t[i] = (double) t_init[i];
+  int64_t sums[mrh_track::kSumWords] = {};
+  int status = MRH_ALIGN_LOST, done = 0;  // an empty sample list is lost: nothing is launched on dst
+  if (n_samples) {
+    mrh_plan::align_tau(R, plan.pivot, t, tau);
+    if ((status = align_iterate(dst, plan, src->align.d_samples, n_samples, R, tau, sums, &done)) < 0) return status;
+    mrh_plan::align_t(R, plan.pivot, tau, t);
+  }
+  for (int i = 0; i < 9; i++) out_R[i] = (float) R[i];
+  for (int i = 0; i < 3; i++) out_t[i] = (float) t[i];
+  if (out_info) {
+    out_info->status = status;
+    out_info->iterations_done = done;
+    out_info->source_blocks = n_blocks;
+    out_info->samples = n_samples;
+    out_info->accepted = (uint64_t) sums[mrh_track::kSumN];
+    out_info->rms = mrh_track::rms(sums);
+    for (int i = 0; i < 3; i++) out_info->pivot[i] = plan.pivot[i];
+    out_info->extent = plan.extent;
+    for (int i = 0; i < mrh_track::kSumWords; i++) out_info->sums[i] = sums[i];
+  }
+  return MRH_OK;
 }
 
 }  // extern "C"

@@ -257,6 +257,24 @@ PYBIND11_MODULE(pygeowrapper, m) {
       d["valid_voxels"] = r.valid_voxels; d["taken"] = r.taken;
       return d;
     }, py::arg("other"), py::arg("t"), py::arg("q"), py::arg("min_weight") = 0)
+    // not part of the reference binding: the pose of `other`'s frame in this map's world, estimated from the two maps alone (DESIGN.md
+    // D19), started from (t, q) as fuseMap takes it.  Returns (t [3], q [4] = qx,qy,qz,qw, info dict): what fuseMap then takes
+    .def("alignMap", [](GeoWrapper& g, GeoWrapper& other, py::array_t<float, py::array::c_style | py::array::forcecast> t,
+                        py::array_t<float, py::array::c_style | py::array::forcecast> q, int iterations, uint32_t min_weight) {
+      if (t.size() != 3 || q.size() != 4) throw std::runtime_error("GeoWrapper::alignMap|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+      const GeoWrapper::AlignResult r = g.alignMap(other, {t.data()[0], t.data()[1], t.data()[2]}, {q.data()[0], q.data()[1], q.data()[2], q.data()[3]}, iterations, min_weight);
+      py::array_t<float> ot(3), oq(4), pivot(3);
+      std::memcpy(ot.mutable_data(), r.t.data(), 3 * sizeof(float));
+      std::memcpy(oq.mutable_data(), r.q.data(), 4 * sizeof(float));
+      std::memcpy(pivot.mutable_data(), r.info.pivot, sizeof r.info.pivot);
+      py::array_t<int64_t> sums(32);
+      std::memcpy(sums.mutable_data(), r.info.sums, sizeof r.info.sums);
+      py::dict info;
+      info["status"] = r.info.status; info["iterations_done"] = r.info.iterations_done; info["source_blocks"] = r.info.source_blocks;
+      info["samples"] = r.info.samples; info["accepted"] = r.info.accepted; info["rms"] = r.info.rms;
+      info["pivot"] = pivot; info["extent"] = r.info.extent; info["sums"] = sums;
+      return py::make_tuple(ot, oq, info);
+    }, py::arg("other"), py::arg("t"), py::arg("q"), py::arg("iterations") = 0, py::arg("min_weight") = 0)
     // not part of the reference binding: the pose of a depth image (2-D, the camera's rows x cols, metres) by ICP against the map,
     // started from the current pose or from (t, q); returns (t [3], q [4] = qx,qy,qz,qw, info dict) and leaves the current pose
     // alone — call setCurrPose(t, q) with the result before setDepthImage / compute
