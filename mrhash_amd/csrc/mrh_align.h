@@ -1,8 +1,8 @@
 // mrh_align.h — map-to-map registration: the linearisation of SDF-to-SDF alignment between two maps (include/mrhash_align.h;
 // DESIGN.md §4.14 and D19, which is normative; tests/align_ref.py restates it).  The reference has no registration: the
 // definition is this project's.  The destination's field is D17's SMOOTH field with its analytic gradient (smooth_field,
-// mrh_query.h), the sums and their reduction are the tracker's (track_reduce_store, k_track_finish, mrh_track.h), the solve and
-// the pose update are the host's (mrh_tracksolve.h); all four are used as they stand.
+// mrh_query.h), the fixed-point step, the sums and their reduction the tracker's (track_fix, track_reduce_store, k_track_finish,
+// mrh_track.h), the loop, the solve and the pose update the host's (mrh_tracksolve.h); all are used as they stand.
 //
 // k_align_gather<EMIT>   one 512-lane workgroup per live source block (Tab::compact[0, n_src), the kSelAll selection; grid-stride),
 //                        one lane per stored voxel (a coarse block uses 64): the pose-independent gates of D19.  EMIT = false
@@ -146,13 +146,7 @@ __device__ __forceinline__ bool align_sample(const Map& m, const Tab& t, const A
   if (!(fabsf(e) <= k.dist_max)) return false;
   const float Jf[6] = {(a.y * gz - a.z * gy) * k.s_a, (a.z * gx - a.x * gz) * k.s_a, (a.x * gy - a.y * gx) * k.s_a,
                        gx * mrh_track::kJOne, gy * mrh_track::kJOne, gz * mrh_track::kJOne};
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-    if (!(fabsf(Jf[i]) < 32768.0f)) return false;  // a NaN is rejected
-#pragma unroll
-  for (int i = 0; i < 6; ++i) J[i] = (int) rintf(Jf[i]);
-  e_fix = (int) rintf(e * mrh_track::kEOne);
-  return true;
+  return track_fix(Jf, e, J, e_fix);
 }
 
 // one lane per sample, a 1-D grid of ceil(n / 256) workgroups, each of which writes one row of the partial slab

@@ -1,6 +1,6 @@
 // mrh_blocks.h — the host side of block I/O behind the C ABI (streamer, dump, get_voxel, the multi-GPU pack / unpack / drop), each
 // entry point a driver over named stages.  dump_compact, free_compact_launch, import_pipe, pack_selected and unpack_records are the
-// one launch site of their kernels (mrh_comm.h packs through pack_selected, mrh_fuse_map merges through unpack_records).  Included by mrh_capi.hip, same translation unit: it needs mrh_ctx's internals.
+// one launch site of their kernels (mrh_comm.h packs through pack_selected, mrh_fuse_map merges through unpack_records; a reader of the whole map, mrh_readers.h, gets its blocks from borrow_live_blocks).  Included by mrh_capi.hip, same translation unit: it needs mrh_ctx's internals.
 #pragma once
 
 namespace {
@@ -49,6 +49,16 @@ int select_blocks(mrh_ctx* c, int sel_mode, int rank_arg, int* out_n) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipGetLastError());
   return MRH_OK;
+}
+// Every live block -> Tab::compact[0, n) for a reader of the whole map (mrh_resample_map / mrh_fuse_map, mrh_align_map): the
+// kSelAll selection borrows the frame path's compact list, and its counter — what mrh_stats reports of the last frame — is put
+// back.  Tab::compact[0, n) itself stays for the reader's kernels: the reader blocks, so nothing else runs on the stream.  Blocks
+int borrow_live_blocks(mrh_ctx* c, int* out_n) {
+  if (!c->d_keep) HIP_TRY(c, dev_alloc(c, c->d_keep, sizeof(int)));
+  HIP_TRY(c, hipMemcpyAsync(c->d_keep, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  const int rc = select_blocks(c, kSelAll, 0, out_n);
+  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], c->d_keep, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  return rc;
 }
 
 // Tab::compact[0, n) -> the caller's descs (and voxels, if asked for), 8 192 blocks (48 MiB of voxels) per round trip; blocking

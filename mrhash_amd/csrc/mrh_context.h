@@ -440,8 +440,8 @@ struct mrh_ctx {
     char* h_out = nullptr; size_t h_cap = 0;
   } query;
   // map-to-map fusion (mrh_readers.h, kernels in mrh_remap.h), grow-only — per candidate slot the two (key, value) pairs of the
-  // sort, the marks and positions of the scans, with them the sort's histogram and the scans' tile sums; two counters {valid
-  // voxels, the frame path's CTR_COMPACT while the call borrows the compact list}; the records of the last call (bytes)
+  // sort, the marks and positions of the scans, with them the sort's histogram and the scans' tile sums; one counter (valid
+  // voxels); the records of the last call (bytes)
   struct Remap {
     u64* d_keys[2] = {nullptr, nullptr}; u32* d_vals[2] = {nullptr, nullptr};
     u64* d_marks = nullptr; u64* d_pos = nullptr; u64* d_sums = nullptr; u32* d_sort = nullptr; size_t cap = 0;  // slots
@@ -450,28 +450,24 @@ struct mrh_ctx {
   } remap;
   // map-to-map registration (mrh_readers.h, kernels in mrh_align.h), grow-only — as the source of a call: per live block the
   // count of its samples, their position (the scan), the tile sums of the scan and the block's integer box (lo, hi); the sample
-  // list, 16 bytes each; pinned {lo, hi} of the whole list and its length.  As the destination: the partial slab (one row of 32
-  // words per workgroup) and the pinned 32 sums the host reads
+  // list, 16 bytes each; pinned {lo, hi} of the whole list.  As the destination it uses `fit` alone
   struct Align {
     u64* d_counts = nullptr; u64* d_pos = nullptr; u64* d_sums = nullptr; int4* d_boxes = nullptr; size_t cap = 0;  // blocks
     float4* d_samples = nullptr; size_t smp_cap = 0;   // samples
     int4* h_box = nullptr;                             // {lo, hi} of the accepted voxel coordinates
-    int* d_keep = nullptr;                             // the frame path's CTR_COMPACT while the call borrows the compact list
-    long long* d_slab = nullptr; size_t slab_cap = 0;  // rows
-    long long* h_sums = nullptr;
   } align;
   // tracking (mrh_readers.h, kernels in mrh_track.h), grow-only — device [model depth or range f32 | model normals 3 x f32] per
-  // pixel, for scans (D15) the model's points image, and the partial slab (one row of 32 words per workgroup); pinned: the 32 sums
-  // the host reads.  An observation that comes from the host — a depth image (D14) or a cloud — is staged through one pair of
-  // buffers, pinned and device (stage_obs)
-  struct Track {
-    char* d_img = nullptr; size_t cap = 0;           // pixels
-    long long* d_slab = nullptr; size_t slab_cap = 0;  // rows
-    long long* h_sums = nullptr;
-    float* d_mp = nullptr; size_t mp_cap = 0;        // pixels, 3 x f32 each
-    float* h_obs = nullptr; size_t h_obs_cap = 0;    // floats
-    float* d_obs = nullptr; size_t obs_cap = 0;      // floats
-  } trk;
+  // pixel and, for scans (D15), the model's points image
+  struct Track { char* d_img = nullptr; size_t cap = 0; float* d_mp = nullptr; size_t mp_cap = 0; } trk;  // both in pixels
+  // what every pose fit reduces through (mrh_readers.h: linearise_sums) — tracking, and registration with this context as the
+  // destination: the partial slab, one row of 32 words per workgroup of a linearisation (grow-only, in rows), and the pinned 32
+  // sums k_track_finish leaves for the host.  One per context is enough: its users run on this context's stream and block
+  struct Fit { long long* d_slab = nullptr; size_t slab_cap = 0; long long* h_sums = nullptr; } fit;
+  // host input staged onto the device (mrh_readers.h: stage_obs), one pair of buffers, pinned and device, grow-only, in floats.
+  // Three users: the depth image of mrh_track_depth, the cloud of mrh_track_scan and the points of mrh_query_points.  Each
+  // overwrites what the last one left, which is safe because every user blocks before it returns: nothing reads the pair then
+  struct Stage { float* h = nullptr; size_t h_cap = 0; float* d = nullptr; size_t d_cap = 0; } stage;
+  int* d_keep = nullptr;  // the frame path's CTR_COMPACT while a reader borrows the compact list (mrh_blocks.h: borrow_live_blocks)
   // normal estimation (mrh_normals.h): the cell table (2 slots per point of `cap`), the list of occupied slots and the slot of
   // every point, grow-only; two sets of counters, a scan's last launch zeroes the next one's
   struct Normals {

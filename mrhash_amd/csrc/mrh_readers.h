@@ -1,12 +1,14 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
 // [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
-// [_device], mrh_track.h; the solve is mrh_tracksolve.h), point queries (mrh_query_points[_device], mrh_query.h) and map-to-map
-// fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map
-// registration (mrh_align_map, mrh_align.h; the sums, the solve and the update are the tracker's).  What they
-// share is here once: the way in (reader_enter: null context, the feature's argument plan from mrh_readerplan.h, ensure_ready) and
-// the way the blocking calls hand their result planes out of pinned memory (read_planes).  The state is mrh_ctx::ray, ::esdf,
-// ::trk, ::query, ::remap and ::align.  Included by mrh_capi.hip, same translation unit: it
-// needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
+// [_device], mrh_track.h), point queries (mrh_query_points[_device], mrh_query.h), map-to-map fusion (mrh_resample_map /
+// mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
+// mrh_align.h).  What they share is here once: the way in (reader_enter: null context, the feature's argument plan from
+// mrh_readerplan.h, ensure_ready; pair_enter and source_rc for the calls on two contexts), the way the blocking calls hand their
+// result planes out of pinned memory (read_planes), the scan of u64 counts with its total (scan_total), host input through the one
+// staging pair (stage_obs) and the two pose fits' reduction (linearise_sums) under the loop, the solve, the update and the
+// report of mrh_tracksolve.h; the live-block list of the readers that walk the whole map is mrh_blocks.h's borrow_live_blocks.
+// The state is mrh_ctx::ray, ::esdf, ::trk, ::query, ::remap, ::align, ::fit and ::stage.  Included by mrh_capi.hip, same translation
+// unit: it needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
 #pragma once
 
 namespace {
@@ -19,6 +21,37 @@ int reader_enter(mrh_ctx* c, const char* who, PlanFn&& plan) {
   char msg[mrh_plan::kMsgBytes];
   const int rc = plan(msg);
   return rc ? fail(c, rc, "%s", msg) : ensure_ready(c, who);
+}
+
+// A failure of the source half of a call on two contexts, reported on dst with src's message; rc = 0 passes through
+int source_rc(mrh_ctx* dst, const mrh_ctx* src, const char* who, const int rc) {
+  return rc ? fail(dst, rc, "%s (source): %s", who, src->err.c_str()) : rc;
+}
+// The way in of the calls on two contexts (mrh_fuse_map, mrh_align_map), in the documented order: a null argument (reported on
+// dst when there is one), what plan(msg) refuses, ensure_ready(dst), ensure_ready(src).  Every error is dst's
+template <typename PlanFn>
+int pair_enter(mrh_ctx* dst, mrh_ctx* src, const char* who, PlanFn&& plan) {
+  if (!dst || !src) return dst ? fail(dst, MRH_ERR_INVALID_ARG, "%s: null argument", who) : MRH_ERR_INVALID_ARG;
+  char msg[mrh_plan::kMsgBytes];
+  if (const int rc = plan(msg)) return fail(dst, rc, "%s", msg);
+  if (const int rc = ensure_ready(dst, who)) return rc;
+  return source_rc(dst, src, who, ensure_ready(src, who));
+}
+
+// Exclusive scan of in[0, n), n >= 1, into pos (tile sums in `sums`: one word per kChainTile entries), and its total
+// pos[n - 1] + in[n - 1].  One synchronisation: whatever the caller launched before it has finished too (blocks)
+int scan_total(mrh_ctx* c, const u64* in, const u32 n, u64* sums, u64* pos, uint64_t* total) {
+  hipStream_t s = c->stream;
+  const u32 tiles = (n + kChainTile - 1) / kChainTile;
+  k_tile_sums_u64<<<tiles, 1024, 0, s>>>(in, n, sums);
+  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(in, n, sums, pos);
+  u64 last[2] = {0, 0};  // the position and the input word of the last entry
+  HIP_TRY(c, hipMemcpyAsync(&last[0], pos + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync(&last[1], in + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipGetLastError());
+  *total = last[0] + last[1];
+  return MRH_OK;
 }
 
 // One result plane of a blocking reader: where it lies in the pinned result, its size, where the kernels leave it, and whether
@@ -137,109 +170,80 @@ struct TrackObs {
   size_t n;   // points (spherical); a depth image has rows * cols pixels
 };
 
-// what the stages of one call share: the plan, the shape of a linearisation and where the model and the observation lie
-struct TrackJob {
-  mrh_plan::Track plan;
-  bool scan;
-  size_t npix, n_obs, n_rows;  // the model's pixels, lanes of a linearisation, its workgroups (one partial row each)
-  dim3 grid;
-  float* d_md; float* d_mn;    // the model's depth (range), then its normals
-  const float* d_obs;
-};
-
-// the previous call blocked: nothing reads the old buffers
-int track_buffers(mrh_ctx* c, TrackJob& j) {
-  mrh_ctx::Track& T = c->trk;
-  int e = regrow(c, T.d_img, T.cap, j.npix, j.npix * 4 * sizeof(float), false);
-  if (!e) e = regrow(c, T.d_slab, T.slab_cap, j.n_rows, j.n_rows * mrh_track::kSumWords * sizeof(i64), false);
-  if (!e && j.scan) e = regrow(c, T.d_mp, T.mp_cap, j.npix, j.npix * 3 * sizeof(float), false);
-  if (e) return e;
-  if (!T.h_sums) HIP_TRY(c, pinned_alloc(c, T.h_sums, mrh_track::kSumWords * sizeof(i64)));
-  j.d_md = (float*) T.d_img;
-  j.d_mn = j.d_md + j.npix;
-  return MRH_OK;
-}
-
-// An observation of n floats from the host — a depth image or a cloud — through the one pinned staging buffer onto the device
+// Host input of n floats — a depth image, a cloud or query points — through the context's one staging pair onto the device
+// (mrh_ctx::Stage: every user blocks before it returns, so the pair is free when the next one fills it)
 int stage_obs(mrh_ctx* c, const float* host, const size_t n, const float** d_obs) {
-  mrh_ctx::Track& T = c->trk;
-  int e = regrow_pinned(c, T.h_obs, T.h_obs_cap, n, n * sizeof(float));
-  if (!e) e = regrow(c, T.d_obs, T.obs_cap, n, n * sizeof(float), false);
+  mrh_ctx::Stage& S = c->stage;
+  int e = regrow_pinned(c, S.h, S.h_cap, n, n * sizeof(float));
+  if (!e) e = regrow(c, S.d, S.d_cap, n, n * sizeof(float), false);
   if (e) return e;
-  memcpy(T.h_obs, host, n * sizeof(float));
-  HIP_TRY(c, hipMemcpyAsync(T.d_obs, T.h_obs, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  *d_obs = T.d_obs;
+  memcpy(S.h, host, n * sizeof(float));
+  HIP_TRY(c, hipMemcpyAsync(S.d, S.h, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  *d_obs = S.d;
   return MRH_OK;
 }
 
-// Per iteration the linearisation kernel, k_track_finish, the 256-byte read-back from pinned memory, and solve + update on the host.
-// (R, t): the pose, updated in place; sums: of the last linearisation.  *done: updates applied; returns MRH_TRACK_* or an error
-int track_iterate(mrh_ctx* c, const mrh_track_params* p, const TrackJob& j, const float* R0, const float* t0, double R[9], double t[3],
-                  int64_t sums[mrh_track::kSumWords], int* done) {
-  const mrh_ctx::Track& T = c->trk;
-  const RayCam& rc = j.plan.cam;
-  TrackLin k;
-  k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.ifx = rc.ifx; k.ify = rc.ify;
-  k.rows = rc.rows; k.cols = rc.cols;
-  k.min_depth = rc.min_depth; k.max_depth = rc.max_depth;
-  k.dmax2 = j.plan.dist_max * j.plan.dist_max;
-  k.s_a = mrh_track::angle_scale(rc.max_depth);
-  for (int i = 0; i < 9; i++) k.Rr[i] = R0[i];
-  for (int i = 0; i < 3; i++) k.tr[i] = t0[i];
-  for (int it = 0; it < j.plan.iterations; it++) {
-    for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
-    for (int i = 0; i < 3; i++) k.t[i] = (float) t[i];
-    if (j.scan) k_track_scan_linearise<<<j.grid, 256, 0, c->stream>>>(k, j.d_obs, (unsigned) j.n_obs, j.d_md, j.d_mn, T.d_mp, T.d_slab);
-    else k_track_linearise<<<j.grid, kRenderTile * kRenderTile, 0, c->stream>>>(k, j.d_obs, j.d_md, j.d_mn, T.d_slab);
-    k_track_finish<<<1, 1024, 0, c->stream>>>(T.d_slab, (int) j.n_rows, T.h_sums);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
-    for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) T.h_sums)[i];
-    double xi[6];
-    if (!mrh_track::solve(sums, k.s_a, j.plan.min_pixels, xi)) return MRH_TRACK_LOST;
-    mrh_track::update(R, t, xi);
-    ++*done;
-  }
-  return MRH_TRACK_OK;
+static_assert(MRH_TRACK_OK == mrh_track::kFitOk && MRH_TRACK_LOST == mrh_track::kFitLost && MRH_ALIGN_OK == mrh_track::kFitOk &&
+              MRH_ALIGN_LOST == mrh_track::kFitLost, "one pair of status values serves tracking and registration (mrh_track::fit_run)");
+// What both fits' callables end in, one linearisation into the 32 sums: launch(slab) starts the kernel whose n_rows workgroups write
+// one row of the context's partial slab each (grown without a drain: its last user blocked), k_track_finish adds the rows into
+// pinned memory, the host reads the 256 bytes.  Blocks
+template <typename Launch>
+int linearise_sums(mrh_ctx* c, const size_t n_rows, Launch&& launch, int64_t sums[mrh_track::kSumWords]) {
+  mrh_ctx::Fit& F = c->fit;
+  if (const int e = regrow(c, F.d_slab, F.slab_cap, n_rows, n_rows * mrh_track::kSumWords * sizeof(i64), false)) return e;
+  if (!F.h_sums) HIP_TRY(c, pinned_alloc(c, F.h_sums, mrh_track::kSumWords * sizeof(i64)));
+  launch(F.d_slab);
+  k_track_finish<<<1, 1024, 0, c->stream>>>(F.d_slab, (int) n_rows, F.h_sums);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
+  for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) F.h_sums)[i];
+  return MRH_OK;
 }
+static_assert(((uint64_t) MRH_ALIGN_MAX_SAMPLES + kAlignLanes - 1) / kAlignLanes <= 0x7FFFFFFFull, "the slab's rows fit k_track_finish's int");
 
 // mrh_track_depth / mrh_track_scan and their device variants, a driver over the stages: plan (mrh_readerplan.h), buffers, the
-// observation onto the device, one render of the model through the raycast's own launch, the iterations, the report (blocks)
+// observation onto the device, one render of the model through the raycast's own launch, the loop with the linearisation kernel
+// of the camera model as its callable, the report (blocks)
 int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const TrackObs& obs, const float* R0, const float* t0, float* out_R, float* out_t,
               mrh_track_info* out_info) {
-  TrackJob j;
+  mrh_plan::Track plan;
   int e = reader_enter(c, who, [&](char* msg) {
-    return mrh_plan::track(msg, who, obs.model, p, obs.host || obs.dev, obs.n, out_R && out_t, R0, t0, c->p.sdf_truncation, c->pending, c->map.shard_count, &j.plan);
+    return mrh_plan::track(msg, who, obs.model, p, obs.host || obs.dev, obs.n, out_R && out_t, R0, t0, c->p.sdf_truncation, c->pending, c->map.shard_count, &plan);
   });
   if (e) return e;
-  const RayCam& rc = j.plan.cam;
-  j.scan = obs.model == MRH_CAMERA_SPHERICAL;
-  j.npix = (size_t) rc.rows * (size_t) rc.cols;
-  j.n_obs = j.scan ? obs.n : j.npix;
-  j.grid = j.scan ? dim3((unsigned) ((j.n_obs + 255) / 256))
-                  : dim3((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
-  j.n_rows = (size_t) j.grid.x * j.grid.y;
-  j.d_obs = obs.dev;
-  double R[9], t[3];
-  for (int i = 0; i < 9; i++) R[i] = (double) R0[i];
-  for (int i = 0; i < 3; i++) t[i] = (double) t0[i];
-  int64_t sums[mrh_track::kSumWords] = {};
-  int status = MRH_TRACK_LOST, done = 0;  // an empty scan is lost: nothing is rendered or launched
-  if (j.n_obs) {
-    if ((e = track_buffers(c, j))) return e;
-    if (!j.d_obs && (e = stage_obs(c, obs.host, j.scan ? 3 * j.n_obs : j.npix, &j.d_obs))) return e;
-    if ((e = launch_raycast(c, obs.model, rc, RayOut{j.d_md, j.d_mn, nullptr, j.scan ? c->trk.d_mp : nullptr}))) return e;
-    if ((status = track_iterate(c, p, j, R0, t0, R, t, sums, &done)) < 0) return status;
+  const RayCam& rc = plan.cam;
+  const bool scan = obs.model == MRH_CAMERA_SPHERICAL;
+  const size_t npix = (size_t) rc.rows * (size_t) rc.cols, n_obs = scan ? obs.n : npix;  // the model's pixels, the lanes of a linearisation
+  const dim3 grid = scan ? dim3((unsigned) ((n_obs + 255) / 256))
+                         : dim3((unsigned) ((rc.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((rc.rows + kRenderTile - 1) / kRenderTile));
+  const size_t n_rows = (size_t) grid.x * grid.y;  // its workgroups: one row of the partial slab each
+  mrh_track::Fit f(R0, t0);  // an empty scan is lost: nothing is rendered or launched
+  if (n_obs) {
+    mrh_ctx::Track& T = c->trk;  // the previous call blocked: nothing reads the old buffers
+    if ((e = regrow(c, T.d_img, T.cap, npix, npix * 4 * sizeof(float), false))) return e;
+    if (scan && (e = regrow(c, T.d_mp, T.mp_cap, npix, npix * 3 * sizeof(float), false))) return e;
+    float *d_md = (float*) T.d_img, *d_mn = d_md + npix;  // the model's depth (range), then its normals
+    const float* d_obs = obs.dev;
+    if (!d_obs && (e = stage_obs(c, obs.host, scan ? 3 * n_obs : npix, &d_obs))) return e;
+    if ((e = launch_raycast(c, obs.model, rc, RayOut{d_md, d_mn, nullptr, scan ? T.d_mp : nullptr}))) return e;
+    TrackLin k;
+    k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.ifx = rc.ifx; k.ify = rc.ify;
+    k.rows = rc.rows; k.cols = rc.cols; k.min_depth = rc.min_depth; k.max_depth = rc.max_depth;
+    k.dmax2 = plan.dist_max * plan.dist_max; k.s_a = mrh_track::angle_scale(rc.max_depth);
+    for (int i = 0; i < 9; i++) k.Rr[i] = R0[i];
+    for (int i = 0; i < 3; i++) k.tr[i] = t0[i];
+    e = mrh_track::fit_run(f, plan.iterations, k.s_a, plan.min_pixels, [&](const float* R, const float* t, int64_t* sums) {
+      for (int i = 0; i < 9; i++) k.R[i] = R[i];
+      for (int i = 0; i < 3; i++) k.t[i] = t[i];
+      return linearise_sums(c, n_rows, [&](i64* slab) {
+        if (scan) k_track_scan_linearise<<<grid, 256, 0, c->stream>>>(k, d_obs, (unsigned) n_obs, d_md, d_mn, T.d_mp, slab);
+        else k_track_linearise<<<grid, kRenderTile * kRenderTile, 0, c->stream>>>(k, d_obs, d_md, d_mn, slab);
+      }, sums);
+    });
+    if (e < 0) return e;
   }
-  for (int i = 0; i < 9; i++) out_R[i] = (float) R[i];
-  for (int i = 0; i < 3; i++) out_t[i] = (float) t[i];
-  if (out_info) {
-    out_info->status = status;
-    out_info->iterations_done = done;
-    out_info->pixels = (uint64_t) sums[mrh_track::kSumN];
-    out_info->rms = mrh_track::rms(sums);
-    for (int i = 0; i < mrh_track::kSumWords; i++) out_info->sums[i] = sums[i];
-  }
+  mrh_track::fit_report(f, out_R, out_t, out_info, &mrh_track_info::pixels);
   return MRH_OK;
 }
 
@@ -277,38 +281,26 @@ int remap_plan(char* msg, const char* who, mrh_ctx* src, mrh_ctx* dst, const mrh
                          fuse && dst->device == src->device, fuse ? dst->p.virtual_voxel_size : 0.f, fuse ? dst->pending : 0, fuse ? dst->map.shard_count : 1, a);
 }
 
-// exclusive scan of marks[0, n) into R.d_pos, the marked keys of `keys` in order to `out`; *count = how many (blocks)
+// exclusive scan of marks[0, n) into R.d_pos, *count = how many are marked (blocks); the marked keys of `keys` in order to `out` (enqueued)
 int remap_keep_marked(mrh_ctx* c, const u64* keys, const u32 n, u64* out, uint64_t* count) {
   mrh_ctx::Remap& R = c->remap;
-  hipStream_t s = c->stream;
-  const u32 tiles = (n + kChainTile - 1) / kChainTile;
-  k_tile_sums_u64<<<tiles, 1024, 0, s>>>(R.d_marks, n, R.d_sums);
-  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(R.d_marks, n, R.d_sums, R.d_pos);
-  k_remap_compact<<<(n + 255) / 256, 256, 0, s>>>(keys, R.d_marks, R.d_pos, n, out);
-  u64 last[2] = {0, 0};  // the position and the mark of the last entry
-  HIP_TRY(c, hipMemcpyAsync(&last[0], R.d_pos + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(&last[1], R.d_marks + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
+  if (const int rc = scan_total(c, R.d_marks, n, R.d_sums, R.d_pos, count)) return rc;
+  k_remap_compact<<<(n + 255) / 256, 256, 0, c->stream>>>(keys, R.d_marks, R.d_pos, n, out);  // behind the read-back: what follows on the stream reads `out`
   HIP_TRY(c, hipGetLastError());
-  *count = last[0] + last[1];
   return MRH_OK;
 }
 
 // The resampling behind ensure_ready(src): candidates, sort, distinct keys, flags, kept keys, sample; the records in
-// src->remap.d_rec.  Blocks.  The live blocks come from the kSelAll selection, which borrows the frame path's compact list:
-// its counter — what mrh_stats reports of the last frame — is put back.  info->taken is left alone
+// src->remap.d_rec.  Blocks.  The live blocks come from borrow_live_blocks (mrh_blocks.h).  info->taken is left alone
 int remap_run(mrh_ctx* c, const char* who, const RemapArgs& a, const mrh_block_record** out_records, uint64_t* out_n, mrh_remap_info* info) {
   mrh_ctx::Remap& R = c->remap;
   hipStream_t s = c->stream;
   *out_records = nullptr;
   *out_n = 0;
   info->source_blocks = info->candidate_blocks = info->records = info->valid_voxels = 0;
-  if (!R.d_count) HIP_TRY(c, dev_alloc(c, R.d_count, 2 * sizeof(u64)));
-  HIP_TRY(c, hipMemsetAsync(R.d_count, 0, 2 * sizeof(u64), s));
-  HIP_TRY(c, hipMemcpyAsync(R.d_count + 1, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToDevice, s));
-  int n_src = 0;
-  int rc = select_blocks(c, kSelAll, 0, &n_src);
-  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], R.d_count + 1, sizeof(int), hipMemcpyDeviceToDevice, s));  // Tab::compact[0, n_src) stays: nothing else runs on s
+  if (!R.d_count) HIP_TRY(c, dev_alloc(c, R.d_count, sizeof(u64)));
+  HIP_TRY(c, hipMemsetAsync(R.d_count, 0, sizeof(u64), s));
+  int n_src = 0, rc = borrow_live_blocks(c, &n_src);
   if (rc) return rc;
   info->source_blocks = (uint64_t) n_src;
   if (n_src == 0) return MRH_OK;
@@ -353,23 +345,19 @@ int remap_run(mrh_ctx* c, const char* who, const RemapArgs& a, const mrh_block_r
 
 // ---- map-to-map registration (include/mrhash_align.h) ----------------------------------------------------------------------------
 
-// The source half behind ensure_ready(src): the live blocks (the kSelAll selection borrows the frame path's compact list as
-// remap_run does, its counter is put back), count, scan, box, emit; the samples in src->align.d_samples.  Fills the automatic
-// pivot and extent into `plan`.  Blocks: src's stream is drained when it returns.  Errors are reported on src
+// The source half behind ensure_ready(src): the live blocks (borrow_live_blocks, mrh_blocks.h), count, box, scan, emit; the
+// samples in src->align.d_samples.  Fills the automatic pivot and extent into `plan`.  Blocks: src's stream is drained when it
+// returns.  Errors are reported on src
 int align_gather(mrh_ctx* c, const char* who, mrh_plan::Align& plan, uint64_t* n_blocks, uint64_t* n_samples) {
   mrh_ctx::Align& A = c->align;
   hipStream_t s = c->stream;
   *n_blocks = *n_samples = 0;
-  if (!A.d_keep) HIP_TRY(c, dev_alloc(c, A.d_keep, sizeof(int)));
   if (!A.h_box) HIP_TRY(c, pinned_alloc(c, A.h_box, 2 * sizeof(int4)));
-  HIP_TRY(c, hipMemcpyAsync(A.d_keep, &c->tab.ctr[CTR_COMPACT], sizeof(int), hipMemcpyDeviceToDevice, s));
-  int n_src = 0;
-  int rc = select_blocks(c, kSelAll, 0, &n_src);
-  HIP_TRY(c, hipMemcpyAsync(&c->tab.ctr[CTR_COMPACT], A.d_keep, sizeof(int), hipMemcpyDeviceToDevice, s));  // Tab::compact[0, n_src) stays: nothing else runs on s
+  int n_src = 0, rc = borrow_live_blocks(c, &n_src);
   if (rc) return rc;
   *n_blocks = (uint64_t) n_src;
   if (n_src == 0) return MRH_OK;
-  const u32 n = (u32) n_src, tiles = (n + kChainTile - 1) / kChainTile, grid = std::min<u32>(n, 8192u);
+  const u32 n = (u32) n_src, grid = std::min<u32>(n, 8192u);
   if ((size_t) n > A.cap) {  // the previous call blocked: nothing reads the old buffers
     const size_t cap = (size_t) n + n / 4, ct = (cap + kChainTile - 1) / kChainTile;
     if ((rc = regrow_all(c, A.cap, cap, {{A.d_counts, cap * sizeof(u64)}, {A.d_pos, cap * sizeof(u64)}, {A.d_sums, ct * sizeof(u64)}, {A.d_boxes, cap * 2 * sizeof(int4)}}, false)))
@@ -379,15 +367,9 @@ int align_gather(mrh_ctx* c, const char* who, mrh_plan::Align& plan, uint64_t* n
   g.vs_s = c->map.vs; g.band = plan.band; g.w_min = plan.w_min; g.crop = plan.crop; g.extent = plan.extent;
   for (int i = 0; i < 3; i++) g.c[i] = plan.pivot[i];
   k_align_gather<false><<<grid, kAlignGatherLanes, 0, s>>>(c->tab, g, n, A.d_counts, A.d_boxes, nullptr, nullptr, 0);
-  k_tile_sums_u64<<<tiles, 1024, 0, s>>>(A.d_counts, n, A.d_sums);
-  k_tile_scan_u64<<<tiles, 1024, 0, s>>>(A.d_counts, n, A.d_sums, A.d_pos);
-  k_align_box<<<1, 1024, 0, s>>>(A.d_boxes, n, A.h_box);
-  u64 last[2] = {0, 0};  // the position and the count of the last block
-  HIP_TRY(c, hipMemcpyAsync(&last[0], A.d_pos + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(&last[1], A.d_counts + (n - 1), sizeof(u64), hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));  // k_align_box wrote the box into pinned memory
-  HIP_TRY(c, hipGetLastError());
-  const uint64_t total = last[0] + last[1];
+  k_align_box<<<1, 1024, 0, s>>>(A.d_boxes, n, A.h_box);  // into pinned memory: scan_total's synchronisation covers it
+  uint64_t total = 0;
+  if ((rc = scan_total(c, A.d_counts, n, A.d_sums, A.d_pos, &total))) return rc;
   char msg[mrh_plan::kMsgBytes];
   uint64_t bytes = 0;
   if ((rc = mrh_plan::align_sample_bytes(msg, who, total, &bytes))) return fail(c, rc, "%s", msg);
@@ -405,39 +387,6 @@ int align_gather(mrh_ctx* c, const char* who, mrh_plan::Align& plan, uint64_t* n
   HIP_TRY(c, hipGetLastError());
   return MRH_OK;
 }
-
-// The destination half: per iteration k_align_linearise on dst's stream with dst's Map / Tab, k_track_finish, the 256-byte
-// read-back from pinned memory, and solve + update on the host, as track_iterate.  (R, tau): the state, updated in place; sums: of
-// the last linearisation.  *done: updates applied; returns MRH_ALIGN_* or an error
-int align_iterate(mrh_ctx* c, const mrh_plan::Align& plan, const float4* d_samples, const uint64_t n, double R[9], double tau[3],
-                  int64_t sums[mrh_track::kSumWords], int* done) {
-  mrh_ctx::Align& A = c->align;
-  const size_t n_rows = (size_t) ((n + kAlignLanes - 1) / kAlignLanes);
-  int e = regrow(c, A.d_slab, A.slab_cap, n_rows, n_rows * mrh_track::kSumWords * sizeof(i64), false);  // the previous call blocked
-  if (e) return e;
-  if (!A.h_sums) HIP_TRY(c, pinned_alloc(c, A.h_sums, mrh_track::kSumWords * sizeof(i64)));
-  AlignLin k;
-  for (int i = 0; i < 3; i++) k.c[i] = plan.pivot[i];
-  k.band = plan.band; k.dist_max = plan.dist_max;
-  k.s_a = mrh_track::angle_scale(plan.extent);
-  k.bound = (float) (1 << 20) * c->map.vs;
-  k.n = (uint32_t) n;
-  for (int it = 0; it < plan.iterations; it++) {
-    for (int i = 0; i < 9; i++) k.R[i] = (float) R[i];
-    for (int i = 0; i < 3; i++) k.tau[i] = (float) tau[i];
-    k_align_linearise<<<(unsigned) n_rows, kAlignLanes, 0, c->stream>>>(c->map, c->tab, k, d_samples, A.d_slab);
-    k_track_finish<<<1, 1024, 0, c->stream>>>(A.d_slab, (int) n_rows, A.h_sums);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the last launch wrote the sums into pinned memory
-    for (int i = 0; i < mrh_track::kSumWords; i++) sums[i] = (int64_t) ((volatile long long*) A.h_sums)[i];
-    double xi[6];
-    if (!mrh_track::solve(sums, k.s_a, plan.min_samples, xi)) return MRH_ALIGN_LOST;
-    mrh_track::update(R, tau, xi);
-    ++*done;
-  }
-  return MRH_ALIGN_OK;
-}
-static_assert(((uint64_t) MRH_ALIGN_MAX_SAMPLES + kAlignLanes - 1) / kAlignLanes <= 0x7FFFFFFFull, "the slab's rows fit k_track_finish's int");
 
 }  // namespace
 
@@ -567,19 +516,14 @@ int mrh_resample_map(mrh_ctx* src, const mrh_remap_params* p, const float R_row_
 
 int mrh_fuse_map(mrh_ctx* dst, mrh_ctx* src, const mrh_remap_params* p, const float R_row_major[9], const float t[3], mrh_remap_info* out_info) {
   const char* who = "mrh_fuse_map";
-  if (!dst || !src) return dst ? fail(dst, MRH_ERR_INVALID_ARG, "%s: null argument", who) : MRH_ERR_INVALID_ARG;
   RemapArgs a;
-  char msg[mrh_plan::kMsgBytes];
-  int rc = remap_plan(msg, who, src, dst, p, R_row_major, t, true, &a);
-  if (rc) return fail(dst, rc, "%s", msg);
-  if ((rc = ensure_ready(dst, who))) return rc;
-  if ((rc = ensure_ready(src, who))) return fail(dst, rc, "%s (source): %s", who, src->err.c_str());
+  int rc = pair_enter(dst, src, who, [&](char* msg) { return remap_plan(msg, who, src, dst, p, R_row_major, t, true, &a); });
+  if (rc) return rc;
   mrh_remap_info info = {};
   const mrh_block_record* records = nullptr;
   uint64_t n = 0;
-  rc = remap_run(src, who, a, &records, &n, &info);  // it blocks: src's stream is drained before dst's stream reads the records
-  if (rc) rc = fail(dst, rc, "%s (source): %s", who, src->err.c_str());
-  else if (n) rc = unpack_records(dst, MRH_UNPACK_MERGE, records, n, 1, &info.taken);
+  rc = source_rc(dst, src, who, remap_run(src, who, a, &records, &n, &info));  // it blocks: src's stream is drained before dst's stream reads the records
+  if (!rc && n) rc = unpack_records(dst, MRH_UNPACK_MERGE, records, n, 1, &info.taken);
   if (out_info) *out_info = info;
   return rc;
 }
@@ -587,39 +531,39 @@ int mrh_fuse_map(mrh_ctx* dst, mrh_ctx* src, const mrh_remap_params* p, const fl
 int mrh_align_map(mrh_ctx* dst, mrh_ctx* src, const mrh_align_params* p, const float R_init[9], const float t_init[3], float out_R[9], float out_t[3],
                   mrh_align_info* out_info) {
   const char* who = "mrh_align_map";
-  if (!dst || !src) return dst ? fail(dst, MRH_ERR_INVALID_ARG, "%s: null argument", who) : MRH_ERR_INVALID_ARG;
   mrh_plan::Align plan;
-  char msg[mrh_plan::kMsgBytes];
-  int rc = mrh_plan::align(msg, who, p, R_init, t_init, out_R && out_t, dst == src, dst->device == src->device, src->p.sdf_truncation, src->pending,
+  int rc = pair_enter(dst, src, who, [&](char* msg) {
+    return mrh_plan::align(msg, who, p, R_init, t_init, out_R && out_t, dst == src, dst->device == src->device, src->p.sdf_truncation, src->pending,
                            src->map.shard_count, dst->p.sdf_truncation, dst->pending, dst->map.shard_count, &plan);
-  if (rc) return fail(dst, rc, "%s", msg);
-  if ((rc = ensure_ready(dst, who))) return rc;
-  if ((rc = ensure_ready(src, who))) return fail(dst, rc, "%s (source): %s", who, src->err.c_str());
+  });
+  if (rc) return rc;
   uint64_t n_blocks = 0, n_samples = 0;
-  rc = align_gather(src, who, plan, &n_blocks, &n_samples);  // it blocks: src's stream is drained before dst's stream reads the samples
-  if (rc) return fail(dst, rc, "%s (source): %s", who, src->err.c_str());
-  double R[9], t[3], tau[3];
-  for (int i = 0; i < 9; i++) R[i] = (double) R_init[i];
-  for (int i = 0; i < 3; i++) t[i] = (double) t_init[i];
-  int64_t sums[mrh_track::kSumWords] = {};
-  int status = MRH_ALIGN_LOST, done = 0;  // an empty sample list is lost: nothing is launched on dst
+  // align_gather blocks: src's stream is drained before dst's stream reads the samples
+  if ((rc = source_rc(dst, src, who, align_gather(src, who, plan, &n_blocks, &n_samples)))) return rc;
+  mrh_track::Fit f(R_init, t_init);  // an empty sample list is lost: nothing is launched on dst
   if (n_samples) {
-    mrh_plan::align_tau(R, plan.pivot, t, tau);
-    if ((status = align_iterate(dst, plan, src->align.d_samples, n_samples, R, tau, sums, &done)) < 0) return status;
-    mrh_plan::align_t(R, plan.pivot, tau, t);
+    const size_t n_rows = (size_t) ((n_samples + kAlignLanes - 1) / kAlignLanes);  // the destination half: on dst's stream with dst's Map / Tab
+    AlignLin k;
+    for (int i = 0; i < 3; i++) k.c[i] = plan.pivot[i];
+    k.band = plan.band; k.dist_max = plan.dist_max; k.s_a = mrh_track::angle_scale(plan.extent);
+    k.bound = (float) (1 << 20) * dst->map.vs; k.n = (uint32_t) n_samples;
+    mrh_plan::align_tau(f.R, plan.pivot, f.t, f.t);  // the loop's translation is tau, about the pivot (element by element: in place)
+    rc = mrh_track::fit_run(f, plan.iterations, k.s_a, plan.min_samples, [&](const float* R, const float* tau, int64_t* sums) {
+      for (int i = 0; i < 9; i++) k.R[i] = R[i];
+      for (int i = 0; i < 3; i++) k.tau[i] = tau[i];
+      return linearise_sums(dst, n_rows, [&](i64* slab) {
+        k_align_linearise<<<(unsigned) n_rows, kAlignLanes, 0, dst->stream>>>(dst->map, dst->tab, k, src->align.d_samples, slab);
+      }, sums);
+    });
+    if (rc < 0) return rc;
+    mrh_plan::align_t(f.R, plan.pivot, f.t, f.t);
   }
-  for (int i = 0; i < 9; i++) out_R[i] = (float) R[i];
-  for (int i = 0; i < 3; i++) out_t[i] = (float) t[i];
+  mrh_track::fit_report(f, out_R, out_t, out_info, &mrh_align_info::accepted);
   if (out_info) {
-    out_info->status = status;
-    out_info->iterations_done = done;
     out_info->source_blocks = n_blocks;
     out_info->samples = n_samples;
-    out_info->accepted = (uint64_t) sums[mrh_track::kSumN];
-    out_info->rms = mrh_track::rms(sums);
     for (int i = 0; i < 3; i++) out_info->pivot[i] = plan.pivot[i];
     out_info->extent = plan.extent;
-    for (int i = 0; i < mrh_track::kSumWords; i++) out_info->sums[i] = sums[i];
   }
   return MRH_OK;
 }

@@ -1,7 +1,7 @@
 // mrh_track.h — depth-frame and scan tracking against the raycast map: the linearisation of point-to-plane ICP (include/mrhash_track.h;
 // DESIGN.md §4.9 and D14, which is normative; tests/track_ref.py restates it).  The reference has no tracker: the definition is
-// this project's.  The model images come from k_raycast<false> (mrh_raycast.h), unchanged; the solve and the pose update are the
-// host's (mrh_tracksolve.h).
+// this project's.  The model images come from k_raycast<false> (mrh_raycast.h), unchanged; the loop, the solve and the pose update
+// are the host's (mrh_tracksolve.h).  Map-to-map registration (mrh_align.h) reuses track_fix, track_reduce_store and k_track_finish.
 //
 // k_track_linearise: one lane per depth pixel, a wave64 an 8 x 8 tile and a workgroup of four waves a 16 x 16 tile as in k_raycast,
 // so that the gathers from the model images stay within a few rows of a few tiles.  Steps 1-8 of D14 run per lane in registers
@@ -45,13 +45,8 @@ __device__ __forceinline__ f3 track_rows(const float* M, const float x, const fl
   return mk3((M[0] * x + M[1] * y) + M[2] * z, (M[3] * x + M[4] * y) + M[5] * z, (M[6] * x + M[7] * y) + M[8] * z);
 }
 
-// steps 6-8 of D14, shared by the depth image and the scan (D15): the gate, the residual and the fixed-point row.  False: rejected.
-__device__ __forceinline__ bool track_row(const TrackLin& k, const f3 a, const f3 pw, const f3 V, const f3 N, int J[6], int& e_fix) {
-  const f3 dl = mk3(V.x - pw.x, V.y - pw.y, V.z - pw.z);
-  if (!((dl.x * dl.x + dl.y * dl.y) + dl.z * dl.z <= k.dmax2)) return false;  // a NaN is rejected
-  const float e = (N.x * dl.x + N.y * dl.y) + N.z * dl.z;
-  const float Jf[6] = {(a.y * N.z - a.z * N.y) * k.s_a, (a.z * N.x - a.x * N.z) * k.s_a, (a.x * N.y - a.y * N.x) * k.s_a,
-                       N.x * mrh_track::kJOne, N.y * mrh_track::kJOne, N.z * mrh_track::kJOne};
+// the fixed-point step (D14 step 8, D19 step 7: align_sample, mrh_align.h): the row and the residual to integers.  False: |Jf_i| >= 2^15
+__device__ __forceinline__ bool track_fix(const float Jf[6], const float e, int J[6], int& e_fix) {
 #pragma unroll
   for (int i = 0; i < 6; ++i)
     if (!(fabsf(Jf[i]) < 32768.0f)) return false;  // a NaN is rejected
@@ -59,6 +54,16 @@ __device__ __forceinline__ bool track_row(const TrackLin& k, const f3 a, const f
   for (int i = 0; i < 6; ++i) J[i] = (int) rintf(Jf[i]);
   e_fix = (int) rintf(e * mrh_track::kEOne);
   return true;
+}
+
+// steps 6-8 of D14, shared by the depth image and the scan (D15): the gate, the residual and the fixed-point row.  False: rejected.
+__device__ __forceinline__ bool track_row(const TrackLin& k, const f3 a, const f3 pw, const f3 V, const f3 N, int J[6], int& e_fix) {
+  const f3 dl = mk3(V.x - pw.x, V.y - pw.y, V.z - pw.z);
+  if (!((dl.x * dl.x + dl.y * dl.y) + dl.z * dl.z <= k.dmax2)) return false;  // a NaN is rejected
+  const float e = (N.x * dl.x + N.y * dl.y) + N.z * dl.z;
+  const float Jf[6] = {(a.y * N.z - a.z * N.y) * k.s_a, (a.z * N.x - a.x * N.z) * k.s_a, (a.x * N.y - a.y * N.x) * k.s_a,
+                       N.x * mrh_track::kJOne, N.y * mrh_track::kJOne, N.z * mrh_track::kJOne};
+  return track_fix(Jf, e, J, e_fix);
 }
 
 // steps 1-8 of D14 for the pixel (r, c), which lies inside the image.  False: rejected.

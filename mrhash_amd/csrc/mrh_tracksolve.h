@@ -1,7 +1,9 @@
-// mrh_tracksolve.h — the host half of depth-frame tracking (include/mrhash_track.h): the fixed-point scale, the
-// binary64 Cholesky solve of the 6 x 6 normal equations from the 29 exact integer sums, and the pose update.  Plain C++, no HIP:
-// mrh_readers.h uses it, and tests/host/track_solve_check.cpp compiles it on its own.  Built with -ffp-contract=off like
-// everything else: every product and every sum below rounds once, in the order written (tests/track_ref.py restates it).
+// mrh_tracksolve.h — the host half of every pose fit (tracking, include/mrhash_track.h; map-to-map registration,
+// include/mrhash_align.h, D19): the fixed-point scale, the binary64 Cholesky solve of the 6 x 6 normal equations from the 29 exact
+// integer sums, the pose update, and the Gauss-Newton loop around them (Fit, fit_run, fit_report) with the linearisation as the
+// caller's callable.  Plain C++, no HIP, no context: mrh_readers.h runs it with callables that launch kernels, tests/host/
+// track_solve_check.cpp compiles it on its own and replays recorded sums.  Built with -ffp-contract=off like everything else:
+// every product and every sum below rounds once, in the order written (tests/track_ref.py restates it).
 #pragma once
 
 #include <cmath>
@@ -79,6 +81,53 @@ inline void update(double R[9], double t[3], const double xi[6]) {
 // rms of the point-to-plane residual over the accepted pixels, metres
 inline double rms(const int64_t sums[kSumWords]) {
   return sums[kSumN] > 0 ? std::sqrt((double) sums[kSumEE] / (double) sums[kSumN]) / (double) kEOne : 0.0;
+}
+
+// ---- the loop (D14 "Loop"; D15 and D19 by reference) ----------------------------------------------------------------------------
+constexpr int kFitOk = 0, kFitLost = 1;  // the value of MRH_TRACK_OK / _LOST and of MRH_ALIGN_OK / _LOST (mrh_readers.h asserts it)
+// What a fit owns: the pose in binary64, the sums of the last linearisation, the status and the number of updates applied.  A
+// fit that is never run — an empty observation — stays lost, with zero sums and the start pose
+struct Fit {
+  double R[9], t[3];
+  int64_t sums[kSumWords] = {};
+  int status = kFitLost, done = 0;
+  Fit(const float R0[9], const float t0[3]) {
+    for (int i = 0; i < 9; i++) R[i] = (double) R0[i];
+    for (int i = 0; i < 3; i++) t[i] = (double) t0[i];
+  }
+};
+
+// `iterations` steps on f.  linearise(R32, t32, sums) takes the linearisation at (float) of the state and fills the 32 sums, or
+// returns a negative error, which ends the loop and is returned as it is.  A step that solve refuses ends the loop as lost: the
+// pose is the one from before that step, f.done its index, f.sums its sums.  Returns f.status otherwise: OK after the last update
+template <typename Linearise>
+inline int fit_run(Fit& f, const int iterations, const float s_a, const uint32_t min_count, Linearise&& linearise) {
+  for (int it = 0; it < iterations; it++) {
+    float R32[9], t32[3];
+    for (int i = 0; i < 9; i++) R32[i] = (float) f.R[i];
+    for (int i = 0; i < 3; i++) t32[i] = (float) f.t[i];
+    const int e = linearise(R32, t32, f.sums);
+    if (e < 0) return e;
+    double xi[6];
+    if (!solve(f.sums, s_a, min_count, xi)) return f.status = kFitLost;
+    update(f.R, f.t, xi);
+    f.done++;
+  }
+  return f.status = kFitOk;
+}
+
+// What a call reports of a fit: the pose narrowed to binary32 and, into the caller's info struct (null: not wanted), status,
+// updates, rms and sums under the names mrh_track_info and mrh_align_info share; `count` is the struct's field for n
+template <typename Info>
+inline void fit_report(const Fit& f, float out_R[9], float out_t[3], Info* info, uint64_t Info::*count) {
+  for (int i = 0; i < 9; i++) out_R[i] = (float) f.R[i];
+  for (int i = 0; i < 3; i++) out_t[i] = (float) f.t[i];
+  if (!info) return;
+  info->status = f.status;
+  info->iterations_done = f.done;
+  info->*count = (uint64_t) f.sums[kSumN];
+  info->rms = rms(f.sums);
+  for (int i = 0; i < kSumWords; i++) info->sums[i] = f.sums[i];
 }
 
 }  // namespace mrh_track

@@ -347,7 +347,15 @@ def test_depth_images_and_scans_share_one_staging_pair(street, scan):
     one context: track_depth on an 80 x 60 image (4 800 floats), track_scan with the 16 x 64 scan (3 072 floats: the pair is reused
     at a smaller size), track_scan with a 32 x 512 scan (49 152 floats: it grows), track_depth again (after a larger scan: reused at a
     smaller size, over what the cloud left behind), track_scan_device (no staging).  Every pose and its 32 sums equal, bit for
-    bit, what a context that has made no other call returns."""
+    bit, what a context that has made no other call returns.
+
+    Two more users share that state (mrh_ctx::Stage and ::Fit).  Between the big cloud and the second depth image a host point
+    query stages the scan's valid points (under 3 000 floats, over what the 49 152 of the cloud left) — its four outputs are
+    compared; the depth image after it reuses the pair again.  Between the second depth image and the device scan a registration
+    with this context as the destination reduces more than 8 192 accepted samples through the slab and the pinned sums that
+    tracking uses: more than the 32 rows one stripe pass of k_track_finish covers and than the 20 rows of the 80 x 60 image, so
+    the tracking call after it reuses the slab at a smaller row count.  Its source is a second context that imported this one's
+    blocks; the fresh side is a fresh pair."""
     hip = capi.load_hip()
     scene = synth.street_canyon()
     frames = [(synth.quat_to_rot(q), t, *synth.spherical_range_image(scene, t, q, CAM_BIG)) for t, q in ts.STREET_POSES]
@@ -368,19 +376,54 @@ def test_depth_images_and_scans_share_one_staging_pair(street, scan):
     image, _, _ = street.raycast(*pin, R_pin, (T_LAST + np.array([0.2, 0.1, 0.05], F)).astype(F), NEAR, FAR, colors=False)
     big = tc.fused_scan(32, 512)
     dev = hipmem.DeviceBuffer.from_numpy(np.ascontiguousarray(scan, F))
+    walls = scan[np.any(scan != 0, axis=1)]  # sensor-frame points on the street's surfaces, about 1 000
+    assert 900 <= len(walls) <= 1024
+    blocks = street.dump_blocks()
+
+    def source():
+        s = capi.Engine(hip, capi.Params(num_sdf_blocks=131072, **PARAMS))
+        s.import_blocks(*blocks)
+        return s
+
+    street_source = source()
+
+    def register(e):  # a few centimetres off the identity, cropped to a cube around the sensor
+        s = street_source if e is street else source()
+        try:
+            return e.align_map(s, np.eye(3, dtype=F), np.array([0.03, -0.02, 0.01], F), iterations=2, pivot=T_LAST, extent=8.0)
+        finally:
+            if s is not street_source:
+                s.close()
+
     calls = [lambda e: e.track_depth(image, *pin, R_pin, T_LAST, NEAR, FAR, iterations=3),
              lambda e: _track(e, CAM, scan, 3),
              lambda e: _track(e, CAM, big, 1),
+             lambda e: e.query(walls, R_LAST, T_LAST),
              lambda e: e.track_depth(image, *pin, R_pin, T_LAST, NEAR, FAR, iterations=3),
+             register,
              lambda e: e.track_scan_device(dev.ptr, len(scan), *ts.cam_args(CAM), R_LAST, T_LAST, NEAR, FAR, iterations=3)]
-    for i, call in enumerate(calls):
-        got = call(street)
-        e = fresh()
-        try:
-            want = call(e)
-        finally:
-            e.close()
-        print("call %d: status %d, %d iterations, %d pixels" % (i, got[2]["status"], got[2]["iterations_done"], got[2]["pixels"]))
-        assert _same_bits(got[0], want[0]) and _same_bits(got[1], want[1]), i
-        assert np.array_equal(got[2]["sums"], want[2]["sums"]) and got[2]["status"] == want[2]["status"], i
-        assert got[2]["pixels"] >= 64, i  # the observation took part
+    try:
+        for i, call in enumerate(calls):
+            got = call(street)
+            e = fresh()
+            try:
+                want = call(e)
+            finally:
+                e.close()
+            if call is calls[3]:  # the query: dist, grad, rgbw, state
+                print("call %d: %d of %d points have a distance" % (i, np.count_nonzero(got[3] & capi.QUERY_DIST), len(walls)))
+                assert all(_same_bits(g, w) for g, w in zip(got, want)) and len(got) == len(want) == 4, i
+                assert np.count_nonzero(got[3] & capi.QUERY_DIST) >= 64, i  # the points took part
+                continue
+            count = "accepted" if call is register else "pixels"
+            print("call %d: status %d, %d iterations, %d %s" % (i, got[2]["status"], got[2]["iterations_done"], got[2][count], count))
+            assert _same_bits(got[0], want[0]) and _same_bits(got[1], want[1]), i
+            assert np.array_equal(got[2]["sums"], want[2]["sums"]) and got[2]["status"] == want[2]["status"], i
+            assert got[2].keys() == want[2].keys()
+            for key in got[2]:  # iterations_done, the counts, rms and, for the registration, pivot and extent
+                assert _same_bits(np.asarray(got[2][key]), np.asarray(want[2][key])), (i, key)
+            assert got[2][count] >= 64, i  # the observation took part
+            if call is register:
+                assert got[2]["accepted"] > 8192 and got[2]["iterations_done"] >= 1, got[2]
+    finally:
+        street_source.close()
