@@ -217,6 +217,16 @@ class MrhTrackInfo(C.Structure):
                     sums=np.array(self.sums[:], dtype=np.int64))
 
 
+# every symbol include/mrhash_sdftrack.h declares (the HIP library only); the info and the status values are tracking's
+SDFTRACK_SYMBOLS = ("mrh_track_depth_sdf mrh_track_depth_sdf_device mrh_track_points_sdf mrh_track_points_sdf_device").split()
+
+
+class MrhSdftrackParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("band", C.c_float), ("iterations", C.c_int32), ("min_pixels", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 # every symbol include/mrhash_normals.h declares (the HIP library only: the oracle is given its normals)
 NORMALS_SYMBOLS = ("mrh_estimate_normals_device mrh_estimate_normals mrh_get_normals").split()
 
@@ -361,6 +371,14 @@ def _declare(lib: C.CDLL) -> C.CDLL:
             lib.mrh_track_scan_device.argtypes = lib.mrh_track_scan.argtypes
             names = TRACK_SYMBOLS
         for name in names:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_track_depth_sdf"):  # include/mrhash_sdftrack.h
+        lib.mrh_track_depth_sdf.argtypes = [C.c_void_p, P(MrhSdftrackParams), C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                            P(MrhTrackInfo)]
+        lib.mrh_track_depth_sdf_device.argtypes = lib.mrh_track_depth_sdf.argtypes
+        lib.mrh_track_points_sdf.argtypes = lib.mrh_track_depth_sdf.argtypes[:3] + [C.c_size_t] + lib.mrh_track_depth_sdf.argtypes[3:]
+        lib.mrh_track_points_sdf_device.argtypes = lib.mrh_track_points_sdf.argtypes
+        for name in SDFTRACK_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_estimate_normals"):  # include/mrhash_normals.h
         lib.mrh_estimate_normals_device.argtypes = [C.c_void_p, P(MrhNormalsParams), C.c_void_p, C.c_uint64, C.c_void_p]
@@ -1021,6 +1039,51 @@ class Engine:
         points image of raycast_spherical_device after sync().  Blocks too."""
         return self._track(self.lib.mrh_track_scan_device, (ptr_points or None, int(n)), fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth,
                            step, dist_max, iterations, min_points)
+
+    # -- render-free tracking (include/mrhash_sdftrack.h) ----------------------------------------------
+    def _track_sdf(self, fn, obs, K, R, t, min_depth, max_depth, band, iterations, min_pixels):
+        """obs: the arguments between the parameter block and the pose — (depth pointer,) or (points pointer, n); K = (fx, fy, cx, cy,
+        rows, cols), zeros for the points form."""
+        fx, fy, cx, cy, rows, cols = K
+        p = MrhSdftrackParams(fx, fy, cx, cy, int(rows), int(cols), min_depth, max_depth, band, int(iterations), int(min_pixels), 0)
+        R = np.ascontiguousarray(R, dtype=np.float32).reshape(9)
+        t = np.ascontiguousarray(t, dtype=np.float32).reshape(3)
+        out_R, out_t, info = np.zeros(9, np.float32), np.zeros(3, np.float32), MrhTrackInfo()
+        F = C.POINTER(C.c_float)
+        self._check(fn(self._ctx, C.byref(p), *obs, R.ctypes.data_as(F), t.ctypes.data_as(F), out_R.ctypes.data_as(F),
+                       out_t.ctypes.data_as(F), C.byref(info)))
+        return out_R.reshape(3, 3), out_t, info.as_dict()
+
+    def track_depth_sdf(self, depth, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, band=0.0, iterations=0, min_pixels=0):
+        """Estimates the camera-to-world pose of the depth image (float32 [rows, cols], metres) by registering its back-projected
+        pixels against the map's distance field, without a render (mrh_track_depth_sdf), from the start (R, t).
+        Blocks.  0 = the default of band (the truncation), iterations (10) and min_pixels (64).  A pixel further than `band`
+        from the surface gives no row.  Returns what track_depth returns."""
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if d.size != int(rows) * int(cols):
+            raise ValueError(f"track_depth_sdf: depth has {d.size} pixels, rows * cols = {int(rows) * int(cols)}")
+        return self._track_sdf(self.lib.mrh_track_depth_sdf, (d.ctypes.data,), (fx, fy, cx, cy, rows, cols), R, t, min_depth, max_depth, band, iterations,
+                               min_pixels)
+
+    def track_depth_sdf_device(self, ptr_depth: int, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, band=0.0, iterations=0, min_pixels=0):
+        """mrh_track_depth_sdf_device: as track_depth_sdf with the image already on the device (integer pointer, [rows * cols]
+        float32).  Blocks too: the solve is on the host."""
+        return self._track_sdf(self.lib.mrh_track_depth_sdf_device, (ptr_depth or None,), (fx, fy, cx, cy, rows, cols), R, t, min_depth, max_depth, band,
+                               iterations, min_pixels)
+
+    def track_points_sdf(self, points, R, t, min_depth, max_depth, band=0.0, iterations=0, min_points=0):
+        """Estimates the sensor-to-world pose of a cloud (float32 [n, 3], sensor frame, any order, any sensor; (0, 0, 0) = no return)
+        against the map's distance field (mrh_track_points_sdf): no camera model, no field of view, no seam.
+        min_depth / max_depth are ranges.  Blocks.  Returns what track_depth returns; info["pixels"] counts points."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        return self._track_sdf(self.lib.mrh_track_points_sdf, (pts.ctypes.data, len(pts)), (0.0, 0.0, 0.0, 0.0, 0, 0), R, t, min_depth, max_depth, band,
+                               iterations, min_points)
+
+    def track_points_sdf_device(self, ptr_points: int, n: int, R, t, min_depth, max_depth, band=0.0, iterations=0, min_points=0):
+        """mrh_track_points_sdf_device: as track_points_sdf with the cloud already on the device (integer pointer, [n, 3] float32,
+        read as it lies).  Blocks too."""
+        return self._track_sdf(self.lib.mrh_track_points_sdf_device, (ptr_points or None, int(n)), (0.0, 0.0, 0.0, 0.0, 0, 0), R, t, min_depth, max_depth,
+                               band, iterations, min_points)
 
     # -- scan normals (include/mrhash_normals.h) ----------------------------------------------------
     def estimate_normals(self, radius=0.0, min_points=0, min_spread=0.0, max_flatness=0.0, info=False):

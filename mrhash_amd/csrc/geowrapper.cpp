@@ -740,6 +740,41 @@ GeoWrapper::TrackResult GeoWrapper::trackCloudPose(const float* pts, size_t n, c
   return trackPose("trackPointCloud", nullptr, pts, n, pose);
 }
 
+GeoWrapper::TrackResult GeoWrapper::trackDepthImageSDF(const float* depth, size_t rows, size_t cols) { return trackSdfPose("trackDepthImageSDF", depth, rows, cols, nullptr, 0, pose_); }
+
+GeoWrapper::TrackResult GeoWrapper::trackDepthImageSDF(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) {
+  return trackSdfPose("trackDepthImageSDF", depth, rows, cols, nullptr, 0, pose_from(t, q));
+}
+
+GeoWrapper::TrackResult GeoWrapper::trackPointCloudSDF(const float* pts, size_t n) { return trackSdfPose("trackPointCloudSDF", nullptr, 0, 0, pts, n, pose_); }
+
+GeoWrapper::TrackResult GeoWrapper::trackPointCloudSDF(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q) {
+  return trackSdfPose("trackPointCloudSDF", nullptr, 0, 0, pts, n, pose_from(t, q));
+}
+
+// depth != nullptr: the depth form of D20 on an image of the pinhole camera; else the points form on the cloud pts [n * 3], which
+// reads the depth limits of the last setCamera and nothing else of it
+GeoWrapper::TrackResult GeoWrapper::trackSdfPose(const char* who, const float* depth, size_t rows, size_t cols, const float* pts, size_t n,
+                                                 const std::array<float, 16>& pose) {
+  const std::string at_who = std::string("GeoWrapper::") + who + " | ";
+  if (depth) {
+    requireCamera(who, MRH_CAMERA_PINHOLE);
+    if (rows != (size_t) camera_rows_ || cols != (size_t) camera_cols_) throw std::runtime_error(at_who + "the depth image must have the camera's rows x cols");
+  } else {
+    if (!has_camera_) throw std::runtime_error(at_who + "setCamera has not been called");
+    if (!pts && n) throw std::runtime_error(at_who + "no points");
+  }
+  const mrh_sdftrack_params p = cameraParams<mrh_sdftrack_params>();  // band, iterations, min_pixels: the defaults
+  const PoseRt at = split_pose(pose);
+  float out_R[9], out_t[3];
+  TrackResult out;
+  std::memset(&out.info, 0, sizeof out.info);
+  check(depth ? mrh_track_depth_sdf(ctx_, &p, depth, at.R, at.t, out_R, out_t, &out.info) : mrh_track_points_sdf(ctx_, &p, pts, n, at.R, at.t, out_R, out_t, &out.info), who);
+  out.t = {out_t[0], out_t[1], out_t[2]};
+  out.q = quat_from(out_R);
+  return out;
+}
+
 void GeoWrapper::clearBuffers() {
   std::cout << "clearing buffers..." << std::endl;
   cacheMesh();  // the mesh of the last extractMesh outlives the map, as the reference's host matrices do

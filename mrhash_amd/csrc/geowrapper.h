@@ -18,6 +18,7 @@
 #include "mrhash_remap.h"
 #include "mrhash_align.h"
 #include "mrhash_track.h"
+#include "mrhash_sdftrack.h"
 #include "mrhash_normals.h"
 
 namespace pygeowrapper {
@@ -182,6 +183,15 @@ public:
   // std::runtime_error.  The map must render the ground for the height to be observable: a truncation of 4 voxels does (D15).
   TrackResult trackPointCloud(const float* pts, size_t n);
   TrackResult trackPointCloud(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q);
+  // ---- render-free tracking (include/mrhash_sdftrack.h; no reference counterpart): the same two calls without the
+  // render — the image's back-projected pixels, or the cloud's points, are registered against the map's own distance field.
+  // Intrinsics and depth limits are those of the last setCamera; band, iterations and min_pixels at their defaults.  The depth
+  // form needs a pinhole camera; the points form reads the depth limits only and accepts either camera model: no field of view,
+  // no azimuth seam, and no ground that has to render.  A point further than the truncation from the surface gives no row.
+  TrackResult trackDepthImageSDF(const float* depth, size_t rows, size_t cols);
+  TrackResult trackDepthImageSDF(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q);
+  TrackResult trackPointCloudSDF(const float* pts, size_t n);
+  TrackResult trackPointCloudSDF(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q);
 
   // ---- multi-GPU (include/mrhash_comm.h; no reference counterpart): one GeoWrapper per process / GPU.
   // commUniqueId() on one rank, the 128 bytes handed to the others by the launcher, then commInit on every rank.
@@ -224,6 +234,7 @@ private:
   TrackResult trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose);
   TrackResult trackCloudPose(const float* pts, size_t n, const std::array<float, 16>& pose);
   TrackResult trackPose(const char* who, const float* depth, const float* pts, size_t n, const std::array<float, 16>& pose);
+  TrackResult trackSdfPose(const char* who, const float* depth, size_t rows, size_t cols, const float* pts, size_t n, const std::array<float, 16>& pose);
   template <typename Params> Params cameraParams() const;    // intrinsics, shape and depth range of the last setCamera; the rest 0
   mrh_raycast_params raycastParams(uint32_t outputs) const;  // the camera of the last setCamera, step = half the truncation
   void requireCamera(const char* method, int model) const;   // throws unless setCamera was called with that camera model

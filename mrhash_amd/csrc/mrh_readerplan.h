@@ -1,5 +1,5 @@
 // mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking,
-// point queries, map-to-map fusion and registration)
+// render-free tracking, point queries, map-to-map fusion and registration)
 // and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
 // parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
 // the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
@@ -21,6 +21,7 @@
 #include "../../include/mrhash_normals.h"
 #include "../../include/mrhash_query.h"
 #include "../../include/mrhash_remap.h"
+#include "../../include/mrhash_sdftrack.h"
 #include "../../include/mrhash_track.h"
 
 namespace mrh {
@@ -80,6 +81,19 @@ struct AlignLin {
   float s_a;           // mrh_track::angle_scale(extent)
   float bound;         // (float) (1 << 20) * vs_d: a sample is rejected unless |W_a| < bound on every axis
   uint32_t n;          // samples, 1 .. 2^26
+};
+
+// what k_sdftrack_depth_linearise and k_sdftrack_points_linearise take (mrh_sdftrack.h): the observation's gates, the gates of
+// D20 and the estimate the linearisation is taken at
+struct SdfTrackLin {
+  float ifx, ify, cx, cy;  // depth form: ifx = 1 / fx, ify = 1 / fy (host, IEEE)
+  int rows, cols;          // depth form: the image
+  uint32_t n;              // points form: points, 1 .. 2^24
+  float min_depth, max_depth;
+  float band;
+  float s_a;               // mrh_track::angle_scale(max_depth)
+  float bound;             // (float) (1 << 20) * vs: a sample is rejected unless |W_a| < bound on every axis
+  float R[9], t[3];        // R32 and t32
 };
 
 // the parameters of the normal-estimation kernels (mrh_normals.h), defaults filled in
@@ -214,6 +228,55 @@ inline int track(char* msg, const char* who, const int model, const mrh_track_pa
     return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the gate must lie in (0, 1] m (dist_max %g)", who, (double) out->dist_max);
   if (p->iterations < 0 || p->iterations > MRH_TRACK_MAX_ITERATIONS)
     return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %d iterations (1 .. %d, 0 = 10)", who, p->iterations, MRH_TRACK_MAX_ITERATIONS);
+  out->iterations = p->iterations ? p->iterations : 10;
+  out->min_pixels = p->min_pixels ? p->min_pixels : 64u;
+  return MRH_OK;
+}
+
+// ---- render-free tracking (include/mrhash_sdftrack.h) ----
+
+// One render-free tracking call with its defaults filled in
+struct Sdftrack {
+  bool depth_form;
+  float ifx, ify, cx, cy;  // depth form; zeros for the points form
+  int rows, cols;
+  float min_depth, max_depth, band;
+  int iterations;
+  uint32_t min_pixels;
+};
+// depth_form: a depth image of p->rows x p->cols pixels, else a cloud of n points; have_obs: the image or the cloud was given (an
+// empty cloud needs none); have_out: both pose outputs were; truncation: the context's sdf_truncation, the default band.  The
+// order: null argument -> more than 2^24 points -> pending, sharded -> reserved word -> (depth form) image shape, intrinsics ->
+// depth range -> band -> iterations -> the pose
+inline int sdftrack(char* msg, const char* who, const bool depth_form, const mrh_sdftrack_params* p, const bool have_obs, const size_t n, const bool have_out,
+                    const float* R0, const float* t0, const float truncation, const int pending, const int shard_count, Sdftrack* out) {
+  if (!p || (!have_obs && (depth_form || n != 0)) || !have_out || !R0 || !t0) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (!depth_form && n > (size_t) MRH_SDFTRACK_MAX_POINTS) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %zu points in one call (limit 2^24)", who, n);
+  if (const int e = whole_map(msg, who, "are not tracked against", pending, shard_count)) return e;
+  if (p->reserved) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  out->depth_form = depth_form;
+  out->ifx = out->ify = out->cx = out->cy = 0.f;
+  out->rows = out->cols = 0;
+  if (depth_form) {
+    if (p->rows < 1 || p->rows > MRH_RAYCAST_MAX_SIDE || p->cols < 1 || p->cols > MRH_RAYCAST_MAX_SIDE)
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: image of %d x %d pixels (1 .. %d per side)", who, p->rows, p->cols, MRH_RAYCAST_MAX_SIDE);
+    if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || p->fx == 0.f || p->fy == 0.f || !std::isfinite(p->cx) || !std::isfinite(p->cy))
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: bad intrinsics", who);
+    out->ifx = 1.0f / p->fx; out->ify = 1.0f / p->fy;
+    out->cx = p->cx; out->cy = p->cy;
+    out->rows = p->rows; out->cols = p->cols;
+  }
+  if (!(p->min_depth > 0.f) || !(p->max_depth > p->min_depth) || !std::isfinite(p->max_depth))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: need 0 < min_depth < max_depth (got %g, %g)", who, (double) p->min_depth, (double) p->max_depth);
+  out->min_depth = p->min_depth; out->max_depth = p->max_depth;
+  out->band = p->band == 0.f ? truncation : p->band;
+  if (!(out->band > 0.f && out->band <= 1.f)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the band must lie in (0, 1] m (band %g)", who, (double) out->band);
+  if (p->iterations < 0 || p->iterations > MRH_TRACK_MAX_ITERATIONS)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %d iterations (1 .. %d, 0 = 10)", who, p->iterations, MRH_TRACK_MAX_ITERATIONS);
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(R0[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t0[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
   out->iterations = p->iterations ? p->iterations : 10;
   out->min_pixels = p->min_pixels ? p->min_pixels : 64u;
   return MRH_OK;

@@ -1,7 +1,7 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
 // [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
-// [_device], mrh_track.h), point queries (mrh_query_points[_device], mrh_query.h), map-to-map fusion (mrh_resample_map /
-// mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
+// [_device], mrh_track.h), render-free tracking (mrh_track_depth_sdf / _points_sdf[_device], mrh_sdftrack.h), point queries
+// (mrh_query_points[_device], mrh_query.h), map-to-map fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
 // mrh_align.h).  What they share is here once: the way in (reader_enter: null context, the feature's argument plan from
 // mrh_readerplan.h, ensure_ready; pair_enter and source_rc for the calls on two contexts), the way the blocking calls hand their
 // result planes out of pinned memory (read_planes), the scan of u64 counts with its total (scan_total), host input through the one
@@ -247,6 +247,47 @@ int track_run(mrh_ctx* c, const char* who, const mrh_track_params* p, const Trac
   return MRH_OK;
 }
 
+// mrh_track_depth_sdf / mrh_track_points_sdf and their device variants (include/mrhash_sdftrack.h, D20), beside track_run: plan,
+// the observation onto the device, the loop with the linearisation kernel of the form as its callable, the report (blocks).  No
+// render and no model buffers: the slab and the pinned sums are the context's (mrh_ctx::fit), the staging pair mrh_ctx::stage.
+// depth_form: host / dev is a depth image of the plan's rows x cols, else a cloud of n points
+int sdftrack_run(mrh_ctx* c, const char* who, const bool depth_form, const mrh_sdftrack_params* p, const float* host, const float* dev, const size_t n,
+                 const float* R0, const float* t0, float* out_R, float* out_t, mrh_track_info* out_info) {
+  mrh_plan::Sdftrack plan;
+  int e = reader_enter(c, who, [&](char* msg) {
+    return mrh_plan::sdftrack(msg, who, depth_form, p, host || dev, n, out_R && out_t, R0, t0, c->p.sdf_truncation, c->pending, c->map.shard_count, &plan);
+  });
+  if (e) return e;
+  const size_t n_obs = depth_form ? (size_t) plan.rows * (size_t) plan.cols : n;  // the lanes of a linearisation
+  const dim3 grid = depth_form ? dim3((unsigned) ((plan.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((plan.rows + kRenderTile - 1) / kRenderTile))
+                               : dim3((unsigned) ((n_obs + kSdfTrackLanes - 1) / kSdfTrackLanes));
+  const size_t n_rows = (size_t) grid.x * grid.y;  // its workgroups: one row of the partial slab each
+  mrh_track::Fit f(R0, t0);  // an empty cloud is lost: nothing is launched
+  if (n_obs) {
+    const float* d_obs = dev;
+    if (!d_obs && (e = stage_obs(c, host, depth_form ? n_obs : 3 * n_obs, &d_obs))) return e;
+    SdfTrackLin k;
+    k.ifx = plan.ifx; k.ify = plan.ify; k.cx = plan.cx; k.cy = plan.cy;
+    k.rows = plan.rows; k.cols = plan.cols; k.n = depth_form ? 0u : (uint32_t) n_obs;
+    k.min_depth = plan.min_depth; k.max_depth = plan.max_depth; k.band = plan.band;
+    k.s_a = mrh_track::angle_scale(plan.max_depth);
+    k.bound = (float) (1 << 20) * c->map.vs;
+    e = mrh_track::fit_run(f, plan.iterations, k.s_a, plan.min_pixels, [&](const float* R, const float* t, int64_t* sums) {
+      for (int i = 0; i < 9; i++) k.R[i] = R[i];
+      for (int i = 0; i < 3; i++) k.t[i] = t[i];
+      return linearise_sums(c, n_rows, [&](i64* slab) {
+        if (depth_form) k_sdftrack_depth_linearise<<<grid, kSdfTrackLanes, 0, c->stream>>>(c->map, c->tab, k, d_obs, slab);
+        else k_sdftrack_points_linearise<<<grid, kSdfTrackLanes, 0, c->stream>>>(c->map, c->tab, k, d_obs, slab);
+      }, sums);
+    });
+    if (e < 0) return e;
+  }
+  mrh_track::fit_report(f, out_R, out_t, out_info, &mrh_track_info::pixels);
+  return MRH_OK;
+}
+static_assert(kSdfTrackLanes == kRenderTile * kRenderTile, "the depth form's tile is one workgroup of track_reduce_store");
+static_assert((size_t) MRH_RAYCAST_MAX_SIDE * MRH_RAYCAST_MAX_SIDE <= (size_t) MRH_SDFTRACK_MAX_POINTS, "an image has no more samples than a cloud may: the sums' bounds");
+
 // ---- point queries (include/mrhash_query.h) ------------------------------------------------------------------------------------
 
 // the four outputs, device pointers (dist and state always; grad / rgbw nullptr = not produced)
@@ -460,6 +501,26 @@ int mrh_track_scan(mrh_ctx* c, const mrh_track_params* p, const float* points_ho
 int mrh_track_scan_device(mrh_ctx* c, const mrh_track_params* p, const float* d_points, size_t n, const float R_init[9], const float t_init[3],
                           float out_R[9], float out_t[3], mrh_track_info* out_info) {
   return track_run(c, "mrh_track_scan_device", p, TrackObs{MRH_CAMERA_SPHERICAL, nullptr, d_points, n}, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_depth_sdf(mrh_ctx* c, const mrh_sdftrack_params* p, const float* depth_host, const float R_init[9], const float t_init[3], float out_R[9],
+                        float out_t[3], mrh_track_info* out_info) {
+  return sdftrack_run(c, "mrh_track_depth_sdf", true, p, depth_host, nullptr, 0, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_depth_sdf_device(mrh_ctx* c, const mrh_sdftrack_params* p, const float* d_depth, const float R_init[9], const float t_init[3], float out_R[9],
+                               float out_t[3], mrh_track_info* out_info) {
+  return sdftrack_run(c, "mrh_track_depth_sdf_device", true, p, nullptr, d_depth, 0, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_points_sdf(mrh_ctx* c, const mrh_sdftrack_params* p, const float* points_host, size_t n, const float R_init[9], const float t_init[3],
+                         float out_R[9], float out_t[3], mrh_track_info* out_info) {
+  return sdftrack_run(c, "mrh_track_points_sdf", false, p, points_host, nullptr, n, R_init, t_init, out_R, out_t, out_info);
+}
+
+int mrh_track_points_sdf_device(mrh_ctx* c, const mrh_sdftrack_params* p, const float* d_points, size_t n, const float R_init[9], const float t_init[3],
+                                float out_R[9], float out_t[3], mrh_track_info* out_info) {
+  return sdftrack_run(c, "mrh_track_points_sdf_device", false, p, nullptr, d_points, n, R_init, t_init, out_R, out_t, out_info);
 }
 
 int mrh_query_points(mrh_ctx* c, const mrh_query_params* p, const float* xyz_host, uint64_t n, const float R_row_major[9], const float t[3],

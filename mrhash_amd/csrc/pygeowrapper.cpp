@@ -305,6 +305,28 @@ PYBIND11_MODULE(pygeowrapper, m) {
       return track_tuple(g.trackPointCloud(pts.data(), (size_t) pts.shape(0), {t->data()[0], t->data()[1], t->data()[2]},
                                            {q->data()[0], q->data()[1], q->data()[2], q->data()[3]}));
     }, py::arg("points"), py::arg("t") = py::none(), py::arg("q") = py::none())
+    // not part of the reference binding: the two tracking calls without the render — the image's pixels, or the cloud's
+    // points, against the map's own distance field; same arguments and result.  trackPointCloudSDF accepts either camera model
+    .def("trackDepthImageSDF", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> depth,
+                                  std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                                  std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> q) {
+      if (depth.ndim() != 2) throw std::runtime_error("GeoWrapper::trackDepthImageSDF|input should be a 2D numpy array");
+      if (t.has_value() != q.has_value()) throw std::runtime_error("GeoWrapper::trackDepthImageSDF|give both t and q, or neither");
+      if (!t) return track_tuple(g.trackDepthImageSDF(depth.data(), (size_t) depth.shape(0), (size_t) depth.shape(1)));
+      if (t->size() != 3 || q->size() != 4) throw std::runtime_error("GeoWrapper::trackDepthImageSDF|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+      return track_tuple(g.trackDepthImageSDF(depth.data(), (size_t) depth.shape(0), (size_t) depth.shape(1), {t->data()[0], t->data()[1], t->data()[2]},
+                                              {q->data()[0], q->data()[1], q->data()[2], q->data()[3]}));
+    }, py::arg("depth"), py::arg("t") = py::none(), py::arg("q") = py::none())
+    .def("trackPointCloudSDF", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> pts,
+                                  std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                                  std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> q) {
+      if (pts.ndim() != 2 || pts.shape(1) != 3) throw std::runtime_error("GeoWrapper::trackPointCloudSDF|input should be a 2D numpy array with 3 columns");
+      if (t.has_value() != q.has_value()) throw std::runtime_error("GeoWrapper::trackPointCloudSDF|give both t and q, or neither");
+      if (!t) return track_tuple(g.trackPointCloudSDF(pts.data(), (size_t) pts.shape(0)));
+      if (t->size() != 3 || q->size() != 4) throw std::runtime_error("GeoWrapper::trackPointCloudSDF|expected a 3-vector and a 4-vector (qx,qy,qz,qw)");
+      return track_tuple(g.trackPointCloudSDF(pts.data(), (size_t) pts.shape(0), {t->data()[0], t->data()[1], t->data()[2]},
+                                              {q->data()[0], q->data()[1], q->data()[2], q->data()[3]}));
+    }, py::arg("points"), py::arg("t") = py::none(), py::arg("q") = py::none())
     .def("clearBuffers", &GeoWrapper::clearBuffers)
     .def("serializeData", &GeoWrapper::serializeData, py::arg("filename_hash") = "./data/hash_points.ply",
          py::arg("filename_voxel") = "./data/voxel_points.ply")
