@@ -65,12 +65,17 @@ class Raycaster:
         t = self.cam.t
         return (F(t[0] + F(F(z) * d[0])), F(t[1] + F(F(z) * d[1])), F(t[2] + F(F(z) * d[2])))
 
-    def present(self, d) -> np.ndarray:
-        """Rule 3's block test for every sample of the rays d [n, 3]: [n, K] bool."""
+    def sample_blocks(self, d) -> np.ndarray:
+        """The block of every sample of the rays d [n, 3]: [n, K, 3] int64."""
         P = (self.cam.t[None, None, :] + self.z[None, :, None] * d[:, None, :]).astype(F)
         b = ind.voxel_to_block(ind.world_to_voxel(self.m.vs, P.reshape(-1, 3)), self.m.vs).astype(np.int64)
+        return b.reshape(len(d), len(self.z), 3)
+
+    def present(self, d) -> np.ndarray:
+        """Rule 3's block test for every sample of the rays d [n, 3]: [n, K] bool."""
+        b = self.sample_blocks(d)
         inside = np.all((b >= -(1 << 20)) & (b < (1 << 20)), axis=-1)
-        return (inside & np.isin(self._key(b), self.keys)).reshape(len(d), len(self.z))
+        return inside & np.isin(self._key(b), self.keys)
 
     def refine(self, d, a, ad, b, bd):  # findIntersectionBisection (vds.cu:348-383); None: the crossing is rejected
         c = a
@@ -85,7 +90,7 @@ class Raycaster:
                 b, bd = c, cd
         return c
 
-    def normal(self, P):
+    def gradient(self, P):  # the central differences over one voxel of the local size; None: a trilinear of the stencil failed
         h = self.m.voxel_size_at(P) if self.multi else self.m.vs
         g = np.zeros(3, F)
         for a in range(3):
@@ -94,21 +99,31 @@ class Raycaster:
             okp, dp = self.m.trilinear(pp)
             okm, dm = self.m.trilinear(pm)
             if not (okp and okm):
-                return np.zeros(3, F)
+                return None
             g[a] = F(dp - dm)
-        if F(F(g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]) == 0:
+        return g
+
+    def normal(self, P):
+        g = self.gradient(P)
+        if g is None or F(F(g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]) == 0:
             return np.zeros(3, F)
         return ind._normalize(g)
+
+    def sample(self, k, ok, D, prev_valid, prev_d, gap):
+        """Called by cast for every sample k in a present block, before rule 4 looks at it: its trilinear (ok, D), the state it
+        meets, and whether absent samples lie between it and the previous present one.  Nothing here; tests/ray_fields.py counts."""
 
     def cast(self, d, present_row):
         """(depth, normal[3], rgb[3]) of one ray."""
         prev_valid, prev_d, prev_z, last = False, F(0), F(0), -2
         for k in np.flatnonzero(present_row):
-            if k != last + 1:
+            gap = k != last + 1
+            if gap:
                 prev_valid = False
             last = k
             z = self.z[k]
             ok, D = self.m.trilinear(self.point(d, z))
+            self.sample(k, ok, D, prev_valid, prev_d, gap)
             if ok and prev_valid and prev_d > 0 and D <= 0:
                 c = self.refine(d, prev_z, prev_d, z, D)
                 if c is not None:

@@ -1,6 +1,7 @@
 """GPU half of the raycast (mrh_raycast.h, include/mrhash_raycast.h): bit-exact against the restatement of
 tests/raycast_ref.py on fused single- and multi-resolution maps, accurate against the analytic scenes, free of side effects
-on the frame path, and reachable through the device variant and the GeoWrapper facade."""
+on the frame path, and reachable through the device variant and the GeoWrapper facade.
+The branch-level cases (the empty-space jump, rule 4's state machine, rule 5's zeros, launch shapes) are in tests/test_ray_fields_gpu.py."""
 import numpy as np
 import pytest
 
