@@ -163,6 +163,26 @@ class MrhQueryParams(C.Structure):
     _fields_ = [("field", C.c_int32), ("outputs", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+# every symbol include/mrhash_rays.h declares (the HIP library only: the oracle has no ray query)
+RAYS_SYMBOLS = ("mrh_cast_rays mrh_cast_rays_device").split()
+RAYS_NORMALS, RAYS_COLORS, RAYS_COUNTS = 1, 2, 4
+RAY_HIT, RAY_UNKNOWN, RAY_INSIDE, RAY_BAD = 1, 2, 4, 0x80
+RAYS_MAX_RAYS = 1 << 24
+
+
+class MrhRaysParams(C.Structure):
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("step", C.c_float), ("outputs", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+def normalize_directions(directions) -> np.ndarray:
+    """d / len per ray in float32, len = sqrt((dx * dx + dy * dy) + dz * dz): what cast_rays(normalize=True) does on the host (a zero
+    direction becomes NaN and is a bad ray)."""
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
+        return (d / ln[:, None]).astype(np.float32)
+
+
 # every symbol include/mrhash_remap.h declares (the HIP library only: the oracle has no map-to-map fusion)
 REMAP_SYMBOLS = ("mrh_resample_map mrh_fuse_map").split()
 
@@ -352,6 +372,11 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_query_points_device.argtypes = [C.c_void_p, P(MrhQueryParams), C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
         for name in QUERY_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_cast_rays"):  # include/mrhash_rays.h
+        lib.mrh_cast_rays.argtypes = [C.c_void_p, P(MrhRaysParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float)] + [P(C.c_void_p)] * 6
+        lib.mrh_cast_rays_device.argtypes = [C.c_void_p, P(MrhRaysParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float)] + [C.c_void_p] * 6
+        for name in RAYS_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_resample_map"):  # include/mrhash_remap.h
         lib.mrh_resample_map.argtypes = [C.c_void_p, P(MrhRemapParams), P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_uint64), P(MrhRemapInfo)]
@@ -942,6 +967,71 @@ class Engine:
         p, pR, pt, _keep = self._query_args(R, t, smooth, bool(d_grad), bool(d_rgbw))
         self._check(self.lib.mrh_query_points_device(self._ctx, C.byref(p), d_points or None, int(n), pR, pt, d_dist or None, d_grad or None,
                                                      d_rgbw or None, d_state or None))
+
+    # -- ray queries (include/mrhash_rays.h) ----------------------------------------------------------
+    def _rays_args(self, max_range, min_range, step, R, t, normals, colors, counts):
+        if (R is None) != (t is None):
+            raise ValueError("cast_rays: give both R and t, or neither")
+        p = MrhRaysParams(float(min_range), float(max_range), float(step), (RAYS_NORMALS if normals else 0) | (RAYS_COLORS if colors else 0) | (RAYS_COUNTS if counts else 0))
+        if R is None:
+            return p, None, None, None
+        pR, pt, keep = self._pose_args(R, t)
+        return p, pR, pt, keep
+
+    def cast_rays(self, origins, directions, max_range, min_range=0.0, step=0.0, tmax=None, R=None, t=None, normals=True, colors=True, counts=True,
+                  normalize=True):
+        """Casts the rays origins [n, 3], directions [n, 3] through the map (mrh_cast_rays): world-frame rays, or with
+        (R, t) sensor-frame rays and their sensor-to-world pose.  Samples lie at min_range + k * step (step 0 = half the truncation)
+        up to max_range and, with tmax [n], up to each ray's own end.  normalize = True divides every direction on the host, in
+        float32, by len = sqrt((dx * dx + dy * dy) + dz * dz) (normalize_directions), so ranges are metres; the C ABI never
+        normalises: with normalize = False a range counts multiples of the direction.  Neighbouring rays of the list share a
+        wave: order them so that neighbours are close in space.  Returns a dict of numpy copies: range f32 [n], status u8 [n]
+        (RAY_HIT | RAY_UNKNOWN | RAY_INSIDE | RAY_BAD; 0 = every sample was observed free space), normals f32 [n, 3], rgb u8
+        [n, 3], counts u32 [n, 2] = (n_free, n_unknown), first_unknown f32 [n]; an output that was not asked for is None."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        n = len(o)
+        if len(d) != n:
+            raise ValueError("cast_rays: %d origins, %d directions" % (n, len(d)))
+        if normalize:
+            d = normalize_directions(d)
+        tm = None
+        if tmax is not None:
+            tm = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+            if len(tm) != n:
+                raise ValueError("cast_rays: %d rays, %d ends" % (n, len(tm)))
+        p, pR, pt, _keep = self._rays_args(max_range, min_range, step, R, t, normals, colors, counts)
+        pr, ps, pn, pc, pk, pf = (C.c_void_p() for _ in range(6))
+        self._check(self.lib.mrh_cast_rays(self._ctx, C.byref(p), o.ctypes.data if n else None, d.ctypes.data if n else None,
+                                           tm.ctypes.data if tm is not None and n else None, n, pR, pt, C.byref(pr), C.byref(ps), C.byref(pn) if normals else None,
+                                           C.byref(pc) if colors else None, C.byref(pk) if counts else None, C.byref(pf) if counts else None))
+        return {"range": _copy_out(pr, n, np.float32, (n,)), "status": _copy_out(ps, n, np.uint8, (n,)),
+                "normals": _copy_out(pn, 3 * n, np.float32, (n, 3)) if normals else None, "rgb": _copy_out(pc, 3 * n, np.uint8, (n, 3)) if colors else None,
+                "counts": _copy_out(pk, 2 * n, np.uint32, (n, 2)) if counts else None, "first_unknown": _copy_out(pf, n, np.float32, (n,)) if counts else None}
+
+    def cast_rays_device(self, d_origins, d_directions, n, max_range, min_range=0.0, step=0.0, d_tmax=0, R=None, t=None, d_range=0, d_status=0, d_normals=0,
+                         d_rgb=0, d_counts=0, d_first_unknown=0):
+        """mrh_cast_rays_device: enqueues the cast of n rays at d_origins, d_directions ([n, 3] f32; d_tmax [n] f32 or 0) into caller
+        device buffers (integer pointers, e.g. hipmem.DeviceBuffer.ptr: [n] f32, [n] u8, [n, 3] f32, [n, 3] u8, [n, 2] u32, [n] f32;
+        d_range and d_status are required, 0 = skip for the others).  Directions are used as given.  Ordered on the context's
+        stream; finished by sync() or any blocking call."""
+        p, pR, pt, _keep = self._rays_args(max_range, min_range, step, R, t, bool(d_normals), bool(d_rgb), bool(d_counts or d_first_unknown))
+        self._check(self.lib.mrh_cast_rays_device(self._ctx, C.byref(p), d_origins or None, d_directions or None, d_tmax or None, int(n), pR, pt, d_range or None,
+                                                  d_status or None, d_normals or None, d_rgb or None, d_counts or None, d_first_unknown or None))
+
+    def line_of_sight(self, a, b, step=0.0):
+        """bool [n]: the segment a[i] -> b[i] ([n, 3] each, world frame) is free of surfaces AND of unobserved space.  One cast_rays
+        with o = a, the unit direction towards b, tmax = |b - a| (float32, the norm of normalize_directions), min_range = 0, and
+        the test status == 0.  A segment of length 0 has no direction: it is a bad ray, hence False."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        d = (np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3) - a).astype(np.float32)
+        ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
+        if len(a) == 0:
+            return np.zeros(0, bool)
+        finite = ln[np.isfinite(ln)]
+        reach = float(finite.max()) if len(finite) else 0.0
+        out = self.cast_rays(a, d, max_range=reach, min_range=0.0, step=step, tmax=ln, normals=False, colors=False, counts=False, normalize=True)
+        return out["status"] == 0
 
     # -- map-to-map fusion (include/mrhash_remap.h) ----------------------------------------------------
     @staticmethod

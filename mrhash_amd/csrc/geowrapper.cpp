@@ -652,6 +652,40 @@ GeoWrapper::PointQuery GeoWrapper::queryPoints(const float* pts, const size_t n,
   return out;
 }
 
+GeoWrapper::RayCast GeoWrapper::castRays(const float* origins, const float* directions, const size_t n, const float max_range, const float min_range, const float step,
+                                         const float* tmax, const bool sensor_frame, const bool normalize) {
+  mrh_rays_params p;
+  std::memset(&p, 0, sizeof p);
+  p.min_range = min_range; p.max_range = max_range; p.step = step;
+  p.outputs = MRH_RAYS_NORMALS | MRH_RAYS_COLORS | MRH_RAYS_COUNTS;
+  std::vector<float> unit;
+  if (normalize && n) {  // binary32, no contraction (the file is built with -ffp-contract=off): a zero direction becomes NaN, a bad ray
+    unit.resize(3 * n);
+    for (size_t i = 0; i < n; i++) {
+      const float dx = directions[3 * i], dy = directions[3 * i + 1], dz = directions[3 * i + 2];
+      const float len = std::sqrt((dx * dx + dy * dy) + dz * dz);
+      unit[3 * i] = dx / len; unit[3 * i + 1] = dy / len; unit[3 * i + 2] = dz / len;
+    }
+    directions = unit.data();
+  }
+  const PoseRt at = split_pose(pose_);
+  const float *range = nullptr, *normals = nullptr, *first = nullptr;
+  const uint8_t *status = nullptr, *rgb = nullptr;
+  const uint32_t* counts = nullptr;
+  check(mrh_cast_rays(ctx_, &p, origins, directions, tmax, (uint64_t) n, sensor_frame ? at.R : nullptr, sensor_frame ? at.t : nullptr, &range, &status, &normals, &rgb,
+                      &counts, &first), "castRays");
+  RayCast out;
+  if (n) {
+    out.range.assign(range, range + n);
+    out.status.assign(status, status + n);
+    out.normals.assign(normals, normals + 3 * n);
+    out.rgb.assign(rgb, rgb + 3 * n);
+    out.counts.assign(counts, counts + 2 * n);
+    out.first_unknown.assign(first, first + n);
+  }
+  return out;
+}
+
 mrh_remap_info GeoWrapper::fuseMap(GeoWrapper& other, const std::array<float, 3>& t, const std::array<float, 4>& q, const uint32_t min_weight) {
   mrh_remap_params p;
   std::memset(&p, 0, sizeof p);

@@ -15,6 +15,7 @@
 #include "mrhash_raycast.h"
 #include "mrhash_esdf.h"
 #include "mrhash_query.h"
+#include "mrhash_rays.h"
 #include "mrhash_remap.h"
 #include "mrhash_align.h"
 #include "mrhash_track.h"
@@ -146,6 +147,21 @@ public:
     std::vector<uint8_t> rgbw, state;
   };
   PointQuery queryPoints(const float* pts, size_t n, bool smooth = false, bool sensor_frame = false);
+
+  // ---- ray queries (include/mrhash_rays.h; no reference counterpart): n rays, each with its own origin [n * 3],
+  // direction [n * 3] and, with tmax [n] (nullptr: none), its own end, cast through the map: samples at min_range + k * step
+  // (step 0 = half the truncation) up to max_range.  normalize = true divides every direction here, on the host, in binary32:
+  // len = sqrtf((dx * dx + dy * dy) + dz * dz), d / len per component — ranges are metres then; false: the directions as given,
+  // ranges count multiples of them.  sensor_frame as in queryPoints.  Neighbouring rays share a wave: order them so that
+  // neighbours are close in space.  range [n], status [n] (MRH_RAY_* bits; 0 = every sample was observed free space), normals
+  // [n * 3], rgb [n * 3], counts [n * 2] = n_free, n_unknown, first_unknown [n].
+  struct RayCast {
+    std::vector<float> range, normals, first_unknown;
+    std::vector<uint8_t> status, rgb;
+    std::vector<uint32_t> counts;
+  };
+  RayCast castRays(const float* origins, const float* directions, size_t n, float max_range, float min_range = 0.f, float step = 0.f, const float* tmax = nullptr,
+                   bool sensor_frame = false, bool normalize = true);
 
   // ---- map-to-map fusion (include/mrhash_remap.h; no reference counterpart): the map of `other`, whose frame lies
   // at the pose (t, q) — as setCurrPose takes it — in this map's world, resampled at this map's voxel size and merged into it

@@ -5,7 +5,7 @@
 // mrh_integrate_resume, sync and stats; the free-block calls, the peeks and the self-test.
 // The context and its lifetime: mrh_context.h; the copy pool: mrh_hostcopy.h; uploads, frame marks, peeks: mrh_upload.h; the
 // host side of a depth frame: mrh_frame.h; extraction, scans and their normals, block I/O, splat seeding, RCCL: mrh_extract.h,
-// mrh_points.h, mrh_blocks.h, mrh_seeds.h, mrh_comm.h; raycast, distance fields, tracking (rendered and render-free), point queries,
+// mrh_points.h, mrh_blocks.h, mrh_seeds.h, mrh_comm.h; raycast, distance fields, tracking (rendered and render-free), point and ray queries,
 // map-to-map fusion and registration: mrh_readers.h, their argument plans:
 // mrh_readerplan.h.  One translation unit.
 // There is NO CPU fallback in this file: without a HIP device mrh_create fails with MRH_ERR_NO_DEVICE.
@@ -31,6 +31,7 @@
 #include "../../include/mrhash_raycast.h"
 #include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_query.h"
+#include "../../include/mrhash_rays.h"
 #include "../../include/mrhash_track.h"
 #include "../../include/mrhash_align.h"
 #include "../../include/mrhash_sdftrack.h"
@@ -40,6 +41,7 @@
 #include "mrh_raycast.h"
 #include "mrh_esdf.h"
 #include "mrh_query.h"
+#include "mrh_rays.h"
 #include "mrh_remap.h"
 #include "mrh_track.h"
 #include "mrh_align.h"

@@ -439,6 +439,13 @@ struct mrh_ctx {
     char* d_out = nullptr; size_t cap = 0;
     char* h_out = nullptr; size_t h_cap = 0;
   } query;
+  // ray queries (mrh_readers.h, kernel in mrh_rays.h), grow-only, in rays — the results of mrh_cast_rays on the device and in the
+  // pinned copy the caller reads, both [range f32 | normals 3 x f32 | counts 2 x u32 | first_unknown f32 | rgb 3 x u8 | status u8],
+  // each plane contiguous.  The rays themselves come through `stage`
+  struct Rays {
+    char* d_out = nullptr; size_t cap = 0;
+    char* h_out = nullptr; size_t h_cap = 0;
+  } rays;
   // map-to-map fusion (mrh_readers.h, kernels in mrh_remap.h), grow-only — per candidate slot the two (key, value) pairs of the
   // sort, the marks and positions of the scans, with them the sort's histogram and the scans' tile sums; one counter (valid
   // voxels); the records of the last call (bytes)
@@ -464,7 +471,8 @@ struct mrh_ctx {
   // sums k_track_finish leaves for the host.  One per context is enough: its users run on this context's stream and block
   struct Fit { long long* d_slab = nullptr; size_t slab_cap = 0; long long* h_sums = nullptr; } fit;
   // host input staged onto the device (mrh_readers.h: stage_obs), one pair of buffers, pinned and device, grow-only, in floats.
-  // Three users: the depth image of mrh_track_depth, the cloud of mrh_track_scan and the points of mrh_query_points.  Each
+  // Four users: the depth image of mrh_track_depth, the cloud of mrh_track_scan, the points of mrh_query_points and the rays of
+  // mrh_cast_rays.  Each
   // overwrites what the last one left, which is safe because every user blocks before it returns: nothing reads the pair then
   struct Stage { float* h = nullptr; size_t h_cap = 0; float* d = nullptr; size_t d_cap = 0; } stage;
   int* d_keep = nullptr;  // the frame path's CTR_COMPACT while a reader borrows the compact list (mrh_blocks.h: borrow_live_blocks)

@@ -21,11 +21,21 @@ constexpr int kRenderTile = 16;                 // pixels per side of a workgrou
 constexpr int kRayBisections = 3;               // n_iteration_bisection (params.h:26)
 constexpr float kRaySkipReachVoxels = 65000.f;  // rays that stay within this many voxels of the origin may jump (see ray_skip_absent)
 
+// What the march helpers below take of a ray besides its direction: where it starts and how it is sampled.  The renders build it
+// from the camera (one origin for the image: uniform values), k_cast_rays (mrh_rays.h) per lane, with the ray's own origin and
+// its own number of samples
+struct RayLine {
+  f3 o;             // origin, world frame
+  float z0, step;   // z_k = z0 + k * step
+  u32 n_samples;    // samples of THIS ray: a jump never runs past n_samples - 1
+};
+__device__ __forceinline__ RayLine ray_line(const RayCam& rc) { return RayLine{mk3(rc.t[0], rc.t[1], rc.t[2]), rc.min_depth, rc.step, rc.n_samples}; }
+
 // z_k, computed afresh for every k (never accumulated)
-__device__ __forceinline__ float ray_z(const RayCam& rc, const u32 k) { return rc.min_depth + (float) k * rc.step; }
-// P(z) = t + z d_w (vds.cu:368: world_cam_pos + c * world_dir)
-__device__ __forceinline__ f3 ray_point(const RayCam& rc, const f3 d, const float z) {
-  return mk3(rc.t[0] + z * d.x, rc.t[1] + z * d.y, rc.t[2] + z * d.z);
+__device__ __forceinline__ float ray_z(const RayLine& rl, const u32 k) { return rl.z0 + (float) k * rl.step; }
+// P(z) = o + z d_w (vds.cu:368: world_cam_pos + c * world_dir)
+__device__ __forceinline__ f3 ray_point(const RayLine& rl, const f3 d, const float z) {
+  return mk3(rl.o.x + z * d.x, rl.o.y + z * d.y, rl.o.z + z * d.z);
 }
 
 // Sample k lies in the ABSENT block b.  Returns the next sample that has to be looked at: k + 1, or one past the last sample
@@ -43,8 +53,8 @@ __device__ __forceinline__ f3 ray_point(const RayCam& rc, const f3 d, const floa
 // 1e-5 epsilon.  So P / vs stays within 0.07 voxel of [8 b - 0.25, 8 b + 7.25], rounds to a voxel in [8 b, 8 b + 7] per axis,
 // and that voxel's block is b (shift).  Samples before the ray enters the shrunk box (z_k < z_in: the current sample sits in
 // the quarter-voxel rim) are not jumped; they get the literal test like every other sample that is not skipped.
-__device__ __forceinline__ u32 ray_skip_absent(const RayCam& rc, const f3 d, const float vs, const i3 b, const u32 k, const float z) {
-  const float ob[3] = {rc.t[0], rc.t[1], rc.t[2]};
+__device__ __forceinline__ u32 ray_skip_absent(const RayLine& rl, const f3 d, const float vs, const i3 b, const u32 k, const float z) {
+  const float ob[3] = {rl.o.x, rl.o.y, rl.o.z};
   const float db[3] = {d.x, d.y, d.z};
   const int bb[3] = {b.x, b.y, b.z};
   float z_in = -INFINITY, z_out = INFINITY;
@@ -63,26 +73,26 @@ __device__ __forceinline__ u32 ray_skip_absent(const RayCam& rc, const f3 d, con
     }
   }
   if (!(z >= z_in)) return k + 1;  // the current sample is in the rim (or NaN): no jump
-  const float kf = floorf((z_out - rc.min_depth) / rc.step);
+  const float kf = floorf((z_out - rl.z0) / rl.step);
   if (!(kf >= (float) (k + 1))) return k + 1;
-  u32 last = kf >= (float) (rc.n_samples - 1) ? rc.n_samples - 1 : (u32) kf;
-  if (!(ray_z(rc, last) <= z_out)) {  // kf may be one too high; z_k itself decides
+  u32 last = kf >= (float) (rl.n_samples - 1) ? rl.n_samples - 1 : (u32) kf;
+  if (!(ray_z(rl, last) <= z_out)) {  // kf may be one too high; z_k itself decides
     last--;
-    if (last <= k || !(ray_z(rc, last) <= z_out)) return k + 1;
+    if (last <= k || !(ray_z(rl, last) <= z_out)) return k + 1;
   }
   return last + 1;
 }
 
 // findIntersectionBisection (vds.cu:348-383): a = z_{k-1} (D > 0), b = z_k (D <= 0).  False: a trilinear inside the
 // refinement failed and the crossing is rejected.
-__device__ __forceinline__ bool ray_refine(const Map& m, const Tab& t, const Neigh& nb, const RayCam& rc, const f3 d, float a, float ad, float b,
+__device__ __forceinline__ bool ray_refine(const Map& m, const Tab& t, const Neigh& nb, const RayLine& rl, const f3 d, float a, float ad, float b,
                                            float bd, float& out) {
   float c = a;
 #pragma unroll 1
   for (int i = 0; i < kRayBisections; ++i) {
     c = a + (ad / (ad - bd)) * (b - a);
     float cd;
-    if (!trilinear(m, t, nb, ray_point(rc, d, c), cd)) return false;
+    if (!trilinear(m, t, nb, ray_point(rl, d, c), cd)) return false;
     if (ad * cd > 0.f) {
       a = c; ad = cd;
     } else {
@@ -129,6 +139,7 @@ __global__ __launch_bounds__(256) void k_raycast(const Map m, const Tab t, const
   // (ray_skip_absent's rounding argument); the margin to 2^16 covers the rounding of this estimate and the block corners
   const float reach = fmaxf(fmaxf(fabsf(rc.t[0]), fabsf(rc.t[1])), fabsf(rc.t[2])) + rc.max_depth * fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z));
   const bool may_skip = reach < kRaySkipReachVoxels * m.vs;
+  const RayLine rl = ray_line(rc);
 
   // the march: the lane remembers the last block it probed (position, present or absent)
   bool cached = false, present = false;
@@ -138,8 +149,8 @@ __global__ __launch_bounds__(256) void k_raycast(const Map m, const Tab t, const
   bool hit = false;
   float depth = 0.f;
   for (u32 k = 0; k < rc.n_samples;) {
-    const float z = ray_z(rc, k);
-    const f3 P = ray_point(rc, d, z);
+    const float z = ray_z(rl, k);
+    const f3 P = ray_point(rl, d, z);
     const i3 v = world_to_voxel(m.vs, P);
     const int ax = v.x < 0 ? -v.x : v.x, ay = v.y < 0 ? -v.y : v.y, az = v.z < 0 ? -v.z : v.z;
     const bool shift = (u32) (ax | ay | az) < (u32) m.block_shift_limit;  // voxel -> block is the shift below the limit (mrh_device.h)
@@ -153,12 +164,12 @@ __global__ __launch_bounds__(256) void k_raycast(const Map m, const Tab t, const
       prev_valid = false;
       const int m0 = b.x * kBlockSide, m1 = b.y * kBlockSide, m2 = b.z * kBlockSide;
       const int bmax = max(max(max(abs(m0), abs(m0 + kBlockSide - 1)), max(abs(m1), abs(m1 + kBlockSide - 1))), max(abs(m2), abs(m2 + kBlockSide - 1)));
-      k = (may_skip && bmax < m.block_shift_limit) ? ray_skip_absent(rc, d, m.vs, b, k, z) : k + 1;
+      k = (may_skip && bmax < m.block_shift_limit) ? ray_skip_absent(rl, d, m.vs, b, k, z) : k + 1;
       continue;
     }
     float D;
     const bool ok = trilinear(m, t, nb, P, D);
-    if (ok && prev_valid && prev_d > 0.f && D <= 0.f && ray_refine(m, t, nb, rc, d, prev_z, prev_d, z, D, depth)) {
+    if (ok && prev_valid && prev_d > 0.f && D <= 0.f && ray_refine(m, t, nb, rl, d, prev_z, prev_d, z, D, depth)) {
       hit = true;
       break;
     }
@@ -171,7 +182,7 @@ __global__ __launch_bounds__(256) void k_raycast(const Map m, const Tab t, const
   float n[3] = {0.f, 0.f, 0.f};
   u32 rgbw = 0;
   if (hit) {
-    const f3 P = ray_point(rc, d, depth);
+    const f3 P = ray_point(rl, d, depth);
     if (out_normals) {  // central difference over one voxel of the local size, normalised as cuda_math.cuh:1075-1078
       const float h = get_voxel_size_f(m, t, nb, P);
       float g[3];

@@ -1,5 +1,5 @@
 // mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking,
-// render-free tracking, point queries, map-to-map fusion and registration)
+// render-free tracking, point queries, ray queries, map-to-map fusion and registration)
 // and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
 // parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
 // the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
@@ -20,6 +20,7 @@
 #include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_normals.h"
 #include "../../include/mrhash_query.h"
+#include "../../include/mrhash_rays.h"
 #include "../../include/mrhash_remap.h"
 #include "../../include/mrhash_sdftrack.h"
 #include "../../include/mrhash_track.h"
@@ -51,6 +52,17 @@ struct QueryArgs {
   bool smooth, posed;  // the field; the points are in the sensor frame
   uint32_t outputs;    // MRH_QUERY_* bits
   float R[9], t[3];    // sensor in world (row-major R); identity and 0 when !posed
+};
+
+// what k_cast_rays takes (mrh_rays.h): the ray count, the samples of the batch, the refusal bound and the sensor-to-world pose
+struct RaysArgs {
+  uint32_t n;           // rays, 1 .. 2^24 when the kernel runs
+  float min_range, max_range, step;
+  uint32_t n_samples;   // samples z_k <= max_range, validated on the host: 1 .. 2^20
+  float bound;          // (float) (1 << 20) * vs: a ray is bad unless |o_w,a| < bound on every axis
+  bool posed;           // the rays are in the sensor frame
+  uint32_t outputs;     // MRH_RAYS_* bits
+  float R[9], t[3];     // sensor in world (row-major R); identity and 0 when !posed
 };
 
 // what the map-to-map kernels take (mrh_remap.h): the pose of the source frame in the destination's world, the destination
@@ -130,6 +142,28 @@ inline int whole_map(char* msg, const char* who, const char* lacks, const int pe
 
 inline float ray_z_host(const float min_depth, const float step, const uint32_t k) { return min_depth + (float) k * step; }  // = ray_z (mrh_raycast.h)
 
+// samples z_k <= z_max of a march that starts at z_0 = z_min <= z_max: z_k is monotone in k (two monotone roundings), so the count is
+// found by bisection on k.  0: more than 2^20
+inline uint32_t ray_sample_count(const float z_min, const float z_max, const float step) {
+  if (ray_z_host(z_min, step, MRH_RAYCAST_MAX_SAMPLES) <= z_max) return 0;
+  uint32_t lo = 0, hi = MRH_RAYCAST_MAX_SAMPLES;  // z(lo) <= z_max < z(hi)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (ray_z_host(z_min, step, mid) <= z_max) lo = mid;
+    else hi = mid;
+  }
+  return hi;
+}
+
+// a pose (R, t) whose twelve numbers are finite
+inline int finite_pose(char* msg, const char* who, const float* R, const float* t) {
+  for (int i = 0; i < 9; i++)
+    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  return MRH_OK;
+}
+
 // the arguments every raycast entry point shares (and tracking, through its model render); fills the kernel's camera.
 // model: MRH_CAMERA_*; truncation: the context's sdf_truncation, for the default step
 inline int raycast(char* msg, const char* who, const int model, const mrh_raycast_params* p, const float* R, const float* t, const float truncation,
@@ -146,20 +180,11 @@ inline int raycast(char* msg, const char* who, const int model, const mrh_raycas
   if (p->outputs & ~known) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
   const float step = p->step == 0.f ? 0.5f * truncation : p->step;
   if (!(step > 0.f) || !std::isfinite(step)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
-  for (int i = 0; i < 9; i++)
-    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
-  for (int i = 0; i < 3; i++)
-    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
-  // samples z_k <= max_depth: z_k is monotone in k (two monotone roundings), so the count is found by bisection on k
-  if (ray_z_host(p->min_depth, step, MRH_RAYCAST_MAX_SAMPLES) <= p->max_depth)
+  if (const int e = finite_pose(msg, who, R, t)) return e;
+  const uint32_t n_samples = ray_sample_count(p->min_depth, p->max_depth, step);
+  if (!n_samples)
     return refuse(msg, MRH_ERR_INVALID_ARG, "%s: more than 2^20 samples per ray (min_depth %g, max_depth %g, step %g)", who, (double) p->min_depth,
                   (double) p->max_depth, (double) step);
-  uint32_t lo = 0, hi = MRH_RAYCAST_MAX_SAMPLES;  // z(lo) <= max_depth < z(hi)
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (ray_z_host(p->min_depth, step, mid) <= p->max_depth) lo = mid;
-    else hi = mid;
-  }
   rc->ifx = 1.0f / p->fx;
   rc->ify = 1.0f / p->fy;
   rc->cx = p->cx; rc->cy = p->cy;
@@ -175,7 +200,7 @@ inline int raycast(char* msg, const char* who, const int model, const mrh_raycas
                     (double) worst, (double) MRH_SM_SINCOS_MAX);
   }
   rc->min_depth = p->min_depth; rc->max_depth = p->max_depth; rc->step = step;
-  rc->n_samples = hi;
+  rc->n_samples = n_samples;
   for (int i = 0; i < 9; i++) rc->R[i] = R[i];
   for (int i = 0; i < 3; i++) rc->t[i] = t[i];
   return MRH_OK;
@@ -310,6 +335,41 @@ inline int query(char* msg, const char* who, const mrh_query_params* p, const bo
   return MRH_OK;
 }
 
+// the arguments both ray-query entry points share (include/mrhash_rays.h); fills the kernel's arguments.  have_rays:
+// origins and directions were given (n == 0 needs none); have_out: the required outputs were (the blocking call has none: true);
+// truncation: the context's sdf_truncation, for the default step; voxel_size: its virtual_voxel_size, for the refusal bound.  The
+// sample count and the pose test are the render's (ray_sample_count, finite_pose).  The order: null argument -> pending, sharded
+// -> reserved words -> output bits -> range -> step -> samples -> n -> R/t pairing -> the pose
+inline int rays(char* msg, const char* who, const mrh_rays_params* p, const bool have_rays, const bool have_out, const uint64_t n, const float* R,
+                const float* t, const float truncation, const float voxel_size, const int pending, const int shard_count, mrh::RaysArgs* out) {
+  if (!p || (!have_rays && n != 0) || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = whole_map(msg, who, "take no ray queries", pending, shard_count)) return e;
+  if (p->reserved[0] || p->reserved[1] || p->reserved[2] || p->reserved[3]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  if (p->outputs & ~(MRH_RAYS_NORMALS | MRH_RAYS_COLORS | MRH_RAYS_COUNTS)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: unknown output bits 0x%x", who, p->outputs);
+  if (!(p->min_range >= 0.f) || !(p->max_range >= p->min_range) || !std::isfinite(p->max_range))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: need 0 <= min_range <= max_range (got %g, %g)", who, (double) p->min_range, (double) p->max_range);
+  const float step = p->step == 0.f ? 0.5f * truncation : p->step;
+  if (!(step > 0.f) || !std::isfinite(step)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
+  const uint32_t n_samples = ray_sample_count(p->min_range, p->max_range, step);
+  if (!n_samples)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: more than 2^20 samples per ray (min_range %g, max_range %g, step %g)", who, (double) p->min_range,
+                  (double) p->max_range, (double) step);
+  if (n > MRH_RAYS_MAX_RAYS) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %llu rays in one call (limit 2^24)", who, (unsigned long long) n);
+  if ((R != nullptr) != (t != nullptr)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: R and t are both null or both set", who);
+  out->posed = R != nullptr;
+  if (out->posed)
+    if (const int e = finite_pose(msg, who, R, t)) return e;
+  for (int i = 0; i < 9; i++) out->R[i] = out->posed ? R[i] : (i % 4 == 0 ? 1.f : 0.f);
+  for (int i = 0; i < 3; i++) out->t[i] = out->posed ? t[i] : 0.f;
+  out->n = (uint32_t) n;
+  out->min_range = p->min_range; out->max_range = p->max_range; out->step = step;
+  out->n_samples = n_samples;
+  out->bound = (float) (1 << 20) * voxel_size;
+  out->outputs = p->outputs;
+  return MRH_OK;
+}
+static_assert(MRH_RAYS_MAX_SAMPLES == MRH_RAYCAST_MAX_SAMPLES, "one sample count serves the render and the ray queries");
+
 // ---- map-to-map fusion (include/mrhash_remap.h) ----
 
 constexpr uint64_t kRemapMaxEntries = 0x7FFFFFFFull;  // candidate slots and records of one call: what mrh_unpack_blocks takes, and 32-bit indices
@@ -318,10 +378,7 @@ constexpr double kRemapRotationTol = 1.0 / 1024.0;    // |R R^T - I| per entry
 
 // a pose (R, t) that is finite and whose R is a rotation or a reflection: |R R^T - I| <= 2^-10 in every entry
 inline int rigid_pose(char* msg, const char* who, const float* R, const float* t) {
-  for (int i = 0; i < 9; i++)
-    if (!std::isfinite(R[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
-  for (int i = 0; i < 3; i++)
-    if (!std::isfinite(t[i])) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: pose is not finite", who);
+  if (const int e = finite_pose(msg, who, R, t)) return e;
   double worst = 0.0;
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) {

@@ -1,13 +1,13 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
 // [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
 // [_device], mrh_track.h), render-free tracking (mrh_track_depth_sdf / _points_sdf[_device], mrh_sdftrack.h), point queries
-// (mrh_query_points[_device], mrh_query.h), map-to-map fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
+// (mrh_query_points[_device], mrh_query.h), ray queries (mrh_cast_rays[_device], mrh_rays.h), map-to-map fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
 // mrh_align.h).  What they share is here once: the way in (reader_enter: null context, the feature's argument plan from
 // mrh_readerplan.h, ensure_ready; pair_enter and source_rc for the calls on two contexts), the way the blocking calls hand their
 // result planes out of pinned memory (read_planes), the scan of u64 counts with its total (scan_total), host input through the one
 // staging pair (stage_obs) and the two pose fits' reduction (linearise_sums) under the loop, the solve, the update and the
 // report of mrh_tracksolve.h; the live-block list of the readers that walk the whole map is mrh_blocks.h's borrow_live_blocks.
-// The state is mrh_ctx::ray, ::esdf, ::trk, ::query, ::remap, ::align, ::fit and ::stage.  Included by mrh_capi.hip, same translation
+// The state is mrh_ctx::ray, ::esdf, ::trk, ::query, ::rays, ::remap, ::align, ::fit and ::stage.  Included by mrh_capi.hip, same translation
 // unit: it needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
 #pragma once
 
@@ -313,6 +313,48 @@ int launch_query(mrh_ctx* c, const QueryArgs& q, const float* d_xyz, const Query
 }
 static_assert((size_t) kQueryLanes * kQuerySlice * sizeof(u32) <= 65536, "the lane-private slices fit the static LDS limit");
 
+// ---- ray queries (include/mrhash_rays.h) ---------------------------------------------------------------------------------------
+
+// the rays of one call, device pointers (tmax nullptr: every ray ends at max_range)
+struct RaysIn {
+  const float* origins; const float* dirs; const float* tmax;
+};
+// the six outputs, device pointers (range and status always; the others nullptr = not produced)
+struct RaysOut {
+  float* range; uint8_t* status; float* normals; uint8_t* rgb; u32* counts; float* first_unknown;
+};
+
+// have_rays / have_out: origins and directions, and the required outputs, were given (mrh_plan::rays)
+int rays_enter(mrh_ctx* c, const char* who, const mrh_rays_params* p, const bool have_rays, const bool have_out, const uint64_t n, const float* R, const float* t,
+               RaysArgs* a) {
+  return reader_enter(c, who, [&](char* msg) {
+    return mrh_plan::rays(msg, who, p, have_rays, have_out, n, R, t, c->p.sdf_truncation, c->p.virtual_voxel_size, c->pending, c->map.shard_count, a);
+  });
+}
+
+// one launch for a.n >= 1 rays; the optional outputs are already nullptr where they are not wanted
+int launch_rays(mrh_ctx* c, const RaysArgs& a, const RaysIn& in, const RaysOut& o) {
+  const unsigned grid = (unsigned) (((size_t) a.n + kRaysLanes - 1) / kRaysLanes);
+  k_cast_rays<<<grid, kRaysLanes, 0, c->stream>>>(c->map, c->tab, a, in.origins, in.dirs, in.tmax, o.range, o.status, o.normals, o.rgb, o.counts, o.first_unknown);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+
+// Host rays through the context's one staging pair (stage_obs's, see mrh_ctx::Stage): [origins 3n | directions 3n | tmax n] floats
+int stage_rays(mrh_ctx* c, const float* origins, const float* dirs, const float* tmax, const size_t n, RaysIn* in) {
+  mrh_ctx::Stage& S = c->stage;
+  const size_t floats = (tmax ? 7 : 6) * n;
+  int e = regrow_pinned(c, S.h, S.h_cap, floats, floats * sizeof(float));
+  if (!e) e = regrow(c, S.d, S.d_cap, floats, floats * sizeof(float), false);
+  if (e) return e;
+  memcpy(S.h, origins, 3 * n * sizeof(float));
+  memcpy(S.h + 3 * n, dirs, 3 * n * sizeof(float));
+  if (tmax) memcpy(S.h + 6 * n, tmax, n * sizeof(float));
+  HIP_TRY(c, hipMemcpyAsync(S.d, S.h, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  *in = RaysIn{S.d, S.d + 3 * n, tmax ? S.d + 6 * n : nullptr};
+  return MRH_OK;
+}
+
 // ---- map-to-map fusion (include/mrhash_remap.h) --------------------------------------------------------------------------------
 
 // the argument plan of both calls (mrh_plan::remap); dst: the destination of mrh_fuse_map, nullptr for mrh_resample_map
@@ -561,6 +603,59 @@ int mrh_query_points_device(mrh_ctx* c, const mrh_query_params* p, const float* 
   const int rc = query_enter(c, "mrh_query_points_device", p, d_xyz != nullptr, d_dist && d_state, n, R_row_major, t, &q);
   if (rc || n == 0) return rc;
   return launch_query(c, q, d_xyz, QueryOut{d_dist, (p->outputs & MRH_QUERY_GRADIENT) ? d_grad : nullptr, (p->outputs & MRH_QUERY_COLOUR) ? d_rgbw : nullptr, d_state});
+}
+
+int mrh_cast_rays(mrh_ctx* c, const mrh_rays_params* p, const float* origins_host, const float* dirs_host, const float* tmax_host, uint64_t n,
+                  const float R_row_major[9], const float t[3], const float** out_range, const uint8_t** out_status, const float** out_normals,
+                  const uint8_t** out_rgb, const uint32_t** out_counts, const float** out_first_unknown) {
+  RaysArgs a;
+  int rc = rays_enter(c, "mrh_cast_rays", p, origins_host && dirs_host, true, n, R_row_major, t, &a);
+  if (rc) return rc;
+  if (out_range) *out_range = nullptr;
+  if (out_status) *out_status = nullptr;
+  if (out_normals) *out_normals = nullptr;
+  if (out_rgb) *out_rgb = nullptr;
+  if (out_counts) *out_counts = nullptr;
+  if (out_first_unknown) *out_first_unknown = nullptr;
+  if (n == 0) return MRH_OK;
+  mrh_ctx::Rays& Y = c->rays;
+  // per ray [range f32 | normals 3 x f32 | counts 2 x u32 | first_unknown f32 | rgb 3 x u8 | status u8], each plane contiguous, on the
+  // device as in the pinned copy
+  const size_t nr = (size_t) n, f = sizeof(float), bytes = nr * (7 * f + 3 + 1);
+  if ((rc = regrow(c, Y.d_out, Y.cap, nr, bytes, false))) return rc;  // the previous mrh_cast_rays has finished (it blocked): nothing reads the old buffer
+  if ((rc = regrow_pinned(c, Y.h_out, Y.h_cap, nr, bytes))) return rc;
+  RaysIn in;
+  if ((rc = stage_rays(c, origins_host, dirs_host, tmax_host, nr, &in))) return rc;
+  auto plane = [&](const size_t off, const size_t size, const bool wanted) { return Plane{off, size, Y.d_out + off, wanted}; };
+  const bool counts = (p->outputs & MRH_RAYS_COUNTS) != 0;
+  enum { RANGE, NORMALS, COUNTS, FIRST, RGB, STATUS };
+  Plane pl[6] = {plane(0, nr * f, out_range != nullptr), plane(nr * f, nr * 3 * f, out_normals && (p->outputs & MRH_RAYS_NORMALS)),
+                 plane(nr * 4 * f, nr * 2 * f, out_counts && counts), plane(nr * 6 * f, nr * f, out_first_unknown && counts),
+                 plane(nr * 7 * f, nr * 3, out_rgb && (p->outputs & MRH_RAYS_COLORS)), plane(nr * 7 * f + nr * 3, nr, out_status != nullptr)};
+  // range and status are always computed: a NULL out-pointer only saves the copy
+  const RaysOut o = {(float*) pl[RANGE].dev, (uint8_t*) pl[STATUS].dev, (float*) pl[NORMALS].device(), (uint8_t*) pl[RGB].device(), (u32*) pl[COUNTS].device(),
+                     (float*) pl[FIRST].device()};
+  if ((rc = launch_rays(c, a, in, o))) return rc;
+  if ((rc = read_planes(c, Y.h_out, pl))) return rc;
+  if (out_range) *out_range = (const float*) pl[RANGE].host;
+  if (out_status) *out_status = (const uint8_t*) pl[STATUS].host;
+  if (out_normals) *out_normals = (const float*) pl[NORMALS].host;
+  if (out_rgb) *out_rgb = (const uint8_t*) pl[RGB].host;
+  if (out_counts) *out_counts = (const uint32_t*) pl[COUNTS].host;
+  if (out_first_unknown) *out_first_unknown = (const float*) pl[FIRST].host;
+  return MRH_OK;
+}
+
+int mrh_cast_rays_device(mrh_ctx* c, const mrh_rays_params* p, const float* d_origins, const float* d_dirs, const float* d_tmax, uint64_t n,
+                         const float R_row_major[9], const float t[3], float* d_range, uint8_t* d_status, float* d_normals, uint8_t* d_rgb,
+                         uint32_t* d_counts, float* d_first_unknown) {
+  RaysArgs a;
+  const int rc = rays_enter(c, "mrh_cast_rays_device", p, d_origins && d_dirs, d_range && d_status, n, R_row_major, t, &a);
+  if (rc || n == 0) return rc;
+  const bool counts = (p->outputs & MRH_RAYS_COUNTS) != 0;
+  return launch_rays(c, a, RaysIn{d_origins, d_dirs, d_tmax},
+                     RaysOut{d_range, d_status, (p->outputs & MRH_RAYS_NORMALS) ? d_normals : nullptr, (p->outputs & MRH_RAYS_COLORS) ? d_rgb : nullptr,
+                             counts ? (u32*) d_counts : nullptr, counts ? d_first_unknown : nullptr});
 }
 
 int mrh_resample_map(mrh_ctx* src, const mrh_remap_params* p, const float R_row_major[9], const float t[3], const mrh_block_record** out_records, uint64_t* out_n,

@@ -245,6 +245,42 @@ PYBIND11_MODULE(pygeowrapper, m) {
       }
       return py::make_tuple(dist, grad, rgbw, state);
     }, py::arg("points"), py::arg("smooth") = false, py::arg("sensor_frame") = false)
+    // not part of the reference binding: rays cast through the map — origins [n, 3], directions [n, 3], tmax [n] or
+    // None; world rays, or with sensor_frame = True rays in the sensor frame at the pose of the last setCurrPose.  normalize = True
+    // divides each direction on the host in float32 by sqrt((dx * dx + dy * dy) + dz * dz).  Returns (range [n] f32, status [n] u8 of
+    // MRH_RAY_* bits, normals [n, 3] f32, rgb [n, 3] u8, counts [n, 2] u32 = n_free, n_unknown, first_unknown [n] f32)
+    .def("castRays", [](GeoWrapper& g, py::array_t<float, py::array::c_style | py::array::forcecast> origins,
+                        py::array_t<float, py::array::c_style | py::array::forcecast> directions, float max_range, float min_range, float step, py::object tmax,
+                        bool sensor_frame, bool normalize) {
+      auto rays_of = [](const py::array_t<float, py::array::c_style | py::array::forcecast>& a) {
+        return (a.ndim() == 2 && a.shape(1) == 3) || (a.ndim() == 1 && a.size() % 3 == 0);
+      };
+      if (!rays_of(origins) || !rays_of(directions) || origins.size() != directions.size())
+        throw std::runtime_error("GeoWrapper::castRays|expected origins and directions of shape [n, 3]");
+      const size_t n = (size_t) origins.size() / 3;
+      py::array_t<float, py::array::c_style | py::array::forcecast> ends;
+      if (!tmax.is_none()) {
+        ends = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(tmax);
+        if (!ends || (size_t) ends.size() != n) throw std::runtime_error("GeoWrapper::castRays|expected tmax of shape [n]");
+      }
+      const GeoWrapper::RayCast r = g.castRays(origins.data(), directions.data(), n, max_range, min_range, step, tmax.is_none() ? nullptr : ends.data(), sensor_frame, normalize);
+      py::array_t<float> range({n});
+      py::array_t<uint8_t> status({n});
+      py::array_t<float> normals({n, (size_t) 3});
+      py::array_t<uint8_t> rgb({n, (size_t) 3});
+      py::array_t<uint32_t> counts({n, (size_t) 2});
+      py::array_t<float> first({n});
+      if (n) {
+        std::memcpy(range.mutable_data(), r.range.data(), r.range.size() * sizeof(float));
+        std::memcpy(status.mutable_data(), r.status.data(), r.status.size());
+        std::memcpy(normals.mutable_data(), r.normals.data(), r.normals.size() * sizeof(float));
+        std::memcpy(rgb.mutable_data(), r.rgb.data(), r.rgb.size());
+        std::memcpy(counts.mutable_data(), r.counts.data(), r.counts.size() * sizeof(uint32_t));
+        std::memcpy(first.mutable_data(), r.first_unknown.data(), r.first_unknown.size() * sizeof(float));
+      }
+      return py::make_tuple(range, status, normals, rgb, counts, first);
+    }, py::arg("origins"), py::arg("directions"), py::arg("max_range"), py::arg("min_range") = 0.f, py::arg("step") = 0.f, py::arg("tmax") = py::none(),
+       py::arg("sensor_frame") = false, py::arg("normalize") = true)
     // not part of the reference binding: the map of `other`, whose frame lies at the pose (t, q) in this map's world, resampled at
     // this map's voxel size and merged into it.  Returns the counts of mrh_remap_info as a dict.  Blocks paged out to
     // either wrapper's host chunk grid take no part
