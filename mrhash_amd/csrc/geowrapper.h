@@ -5,7 +5,6 @@
 #pragma once
 
 #include <array>
-#include <map>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -22,6 +21,9 @@
 #include "mrhash_sdftrack.h"
 #include "mrhash_normals.h"
 
+#include "gw_chunks.h"
+#include "gw_pose.h"
+
 namespace pygeowrapper {
 
 class GeoWrapper {
@@ -36,30 +38,18 @@ public:
   GeoWrapper& operator=(const GeoWrapper&) = delete;
 
   // getters / setters: like the reference they only touch the cached host copy (geowrapper.h:80-109)
-  int getHashNumBuckets() const { return hash_num_buckets_; }
-  int getNumSdfBlocks() const { return num_sdf_blocks_; }
-  int getHashBucketSize() const { return hash_bucket_size_; }
-  float getSdfTruncation() const { return sdf_truncation_; }
-  float getSdfTruncationScale() const { return sdf_truncation_scale_; }
-  int getIntegrationWeightSample() const { return integration_weight_sample_; }
-  int getIntegrationWeightMax() const { return integration_weight_max_; }
-  float getVirtualVoxelSize() const { return virtual_voxel_size_; }
-  int getLinkedListSize() const { return linked_list_size_; }
-  int getNFramesInvalidateVoxels() const { return n_frames_invalidate_voxels_; }
-  int getMaxNumSdfBlockIntegrateFromGlobalHash() const { return max_num_sdf_block_integrate_from_global_hash_; }
-  int getVoxelExtentsScale() const { return voxel_extents_scale_; }
-  void setHashNumBuckets(int v) { hash_num_buckets_ = v; }
-  void setNumSdfBlocks(int v) { num_sdf_blocks_ = v; }
-  void setHashBucketSize(int v) { hash_bucket_size_ = v; }
-  void setSdfTruncation(float v) { sdf_truncation_ = v; }
-  void setSdfTruncationScale(float v) { sdf_truncation_scale_ = v; }
-  void setIntegrationWeightSample(int v) { integration_weight_sample_ = v; }
-  void setIntegrationWeightMax(int v) { integration_weight_max_ = v; }
-  void setVirtualVoxelSize(float v) { virtual_voxel_size_ = v; }
-  void setLinkedListSize(int v) { linked_list_size_ = v; }
-  void setNFramesInvalidateVoxels(int v) { n_frames_invalidate_voxels_ = v; }
-  void setMaxNumSdfBlockIntegrateFromGlobalHash(int v) { max_num_sdf_block_integrate_from_global_hash_ = v; }
-  void setVoxelExtentsScale(int v) { voxel_extents_scale_ = v; }
+  int getHashNumBuckets() const { return set_.hash_num_buckets; }  void setHashNumBuckets(int v) { set_.hash_num_buckets = v; }
+  int getNumSdfBlocks() const { return set_.num_sdf_blocks; }  void setNumSdfBlocks(int v) { set_.num_sdf_blocks = v; }
+  int getHashBucketSize() const { return set_.hash_bucket_size; }  void setHashBucketSize(int v) { set_.hash_bucket_size = v; }
+  float getSdfTruncation() const { return set_.sdf_truncation; }  void setSdfTruncation(float v) { set_.sdf_truncation = v; }
+  float getSdfTruncationScale() const { return set_.sdf_truncation_scale; }  void setSdfTruncationScale(float v) { set_.sdf_truncation_scale = v; }
+  int getIntegrationWeightSample() const { return set_.integration_weight_sample; }  void setIntegrationWeightSample(int v) { set_.integration_weight_sample = v; }
+  int getIntegrationWeightMax() const { return set_.integration_weight_max; }  void setIntegrationWeightMax(int v) { set_.integration_weight_max = v; }
+  float getVirtualVoxelSize() const { return set_.virtual_voxel_size; }  void setVirtualVoxelSize(float v) { set_.virtual_voxel_size = v; }
+  int getLinkedListSize() const { return set_.linked_list_size; }  void setLinkedListSize(int v) { set_.linked_list_size = v; }
+  int getNFramesInvalidateVoxels() const { return set_.n_frames_invalidate_voxels; }  void setNFramesInvalidateVoxels(int v) { set_.n_frames_invalidate_voxels = v; }
+  int getMaxNumSdfBlockIntegrateFromGlobalHash() const { return set_.max_num_sdf_block_integrate_from_global_hash; }  void setMaxNumSdfBlockIntegrateFromGlobalHash(int v) { set_.max_num_sdf_block_integrate_from_global_hash = v; }
+  int getVoxelExtentsScale() const { return set_.voxel_extents_scale; }  void setVoxelExtentsScale(int v) { set_.voxel_extents_scale = v; }
 
   // translation <tx,ty,tz>, quaternion <qx,qy,qz,qw> (geowrapper.cpp:86-92)
   void setCurrPose(const std::array<float, 3>& t, const std::array<float, 4>& q);
@@ -82,17 +72,17 @@ public:
   // V / F / C of the last extractMesh.  The library keeps them (until the next extraction); the copies the getters hand out are
   // made on first use — extractMesh itself formats the PLY straight from the library's buffers (83 MB of copies, a third
   // of the call, when nobody asks for the arrays).
-  const std::vector<double>& vertices() const { cacheMesh(); return V_; }
-  const std::vector<int32_t>& faces() const { cacheMesh(); return F_; }
-  const std::vector<double>& colors() const { cacheMesh(); return C_; }
+  const std::vector<double>& vertices() const { cacheMesh(); return mesh_.V; }
+  const std::vector<int32_t>& faces() const { cacheMesh(); return mesh_.F; }
+  const std::vector<double>& colors() const { cacheMesh(); return mesh_.C; }
 
   void streamAllOut();
   // Streamer::stream (streamer.cpp:333-354): blocks farther than `radius` from `camera_position` leave the device for the
   // host chunk grid, chunks inside the sphere come back.  compute() calls it when the pool runs low (geowrapper.cpp:137-138).
   void stream(const std::array<float, 3>& camera_position, float radius);
-  size_t hostGridBlocks() const;
+  size_t hostGridBlocks() const { return grid_.blocks(); }  // blocks currently held by the host chunk grid
   void setSyncCompute(bool on) { sync_compute_ = on; }
-  uint32_t lastComputeFlags() const { return last_compute_flags_; }  // sync mode: flags the last compute() raised (1 pool, 2 table, 4 key range)  // blocks currently held by the host chunk grid
+  uint32_t lastComputeFlags() const { return last_compute_flags_; }  // sync mode: flags the last compute() raised (1 pool, 2 table, 4 key range)
   void clearBuffers();
   void serializeData(const std::string& filename_hash, const std::string& filename_voxel);
   void serializeGrid(const std::string& filename);
@@ -111,8 +101,8 @@ public:
     std::vector<float> depth, normals;
     std::vector<uint8_t> colors;
   };
-  RaycastImages raycast();
-  RaycastImages raycast(const std::array<float, 3>& t, const std::array<float, 4>& q);
+  RaycastImages raycast() { return raycastPose(pose_); }
+  RaycastImages raycast(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastPose(gw::pose_from(t, q)); }
   // The same for the spherical camera of the last setCamera (LiDAR scans, range images): range [rows * cols] (metres along the
   // ray) instead of depth, and the crossings as sensor-frame points [rows * cols * 3] — an organised scan of `cols` points per
   // row with (0, 0, 0) for a ray without a hit, which setPointCloud takes as it is.  A pinhole camera throws std::runtime_error.
@@ -121,8 +111,8 @@ public:
     std::vector<float> range, normals, points;
     std::vector<uint8_t> colors;
   };
-  RaycastScan raycastScan();
-  RaycastScan raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q);
+  RaycastScan raycastScan() { return raycastScanPose(pose_); }
+  RaycastScan raycastScan(const std::array<float, 3>& t, const std::array<float, 4>& q) { return raycastScanPose(gw::pose_from(t, q)); }
 
   // ---- distance fields (include/mrhash_esdf.h; no reference counterpart): the Euclidean signed distance to the
   // nearest surface for every finest voxel of the world box [lo, hi] (metres), exact up to max_distance.  Per axis the box is
@@ -191,23 +181,23 @@ public:
     std::array<float, 4> q;  // qx, qy, qz, qw
     mrh_track_info info;
   };
-  TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols);
-  TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q);
+  TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols) { return trackDepthPose(depth, rows, cols, pose_); }
+  TrackResult trackDepthImage(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) { return trackDepthPose(depth, rows, cols, gw::pose_from(t, q)); }
   // The same for a LiDAR scan: n sensor-frame points [n * 3], organised or not, (0, 0, 0) = no return, against one
   // spherical render of the map with the camera of the last setCamera(..., model = 1).  The loop is trackPointCloud -> setCurrPose
   // -> setPointCloud -> compute; the cloud given to setPointCloud is neither read nor replaced.  A pinhole camera throws
   // std::runtime_error.  The map must render the ground for the height to be observable: a truncation of 4 voxels does (D15).
-  TrackResult trackPointCloud(const float* pts, size_t n);
-  TrackResult trackPointCloud(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q);
+  TrackResult trackPointCloud(const float* pts, size_t n) { return trackCloudPose(pts, n, pose_); }
+  TrackResult trackPointCloud(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q) { return trackCloudPose(pts, n, gw::pose_from(t, q)); }
   // ---- render-free tracking (include/mrhash_sdftrack.h; no reference counterpart): the same two calls without the
   // render — the image's back-projected pixels, or the cloud's points, are registered against the map's own distance field.
   // Intrinsics and depth limits are those of the last setCamera; band, iterations and min_pixels at their defaults.  The depth
   // form needs a pinhole camera; the points form reads the depth limits only and accepts either camera model: no field of view,
   // no azimuth seam, and no ground that has to render.  A point further than the truncation from the surface gives no row.
-  TrackResult trackDepthImageSDF(const float* depth, size_t rows, size_t cols);
-  TrackResult trackDepthImageSDF(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q);
-  TrackResult trackPointCloudSDF(const float* pts, size_t n);
-  TrackResult trackPointCloudSDF(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q);
+  TrackResult trackDepthImageSDF(const float* depth, size_t rows, size_t cols) { return trackSdfPose("trackDepthImageSDF", depth, rows, cols, nullptr, 0, pose_); }
+  TrackResult trackDepthImageSDF(const float* depth, size_t rows, size_t cols, const std::array<float, 3>& t, const std::array<float, 4>& q) { return trackSdfPose("trackDepthImageSDF", depth, rows, cols, nullptr, 0, gw::pose_from(t, q)); }
+  TrackResult trackPointCloudSDF(const float* pts, size_t n) { return trackSdfPose("trackPointCloudSDF", nullptr, 0, 0, pts, n, pose_); }
+  TrackResult trackPointCloudSDF(const float* pts, size_t n, const std::array<float, 3>& t, const std::array<float, 4>& q) { return trackSdfPose("trackPointCloudSDF", nullptr, 0, 0, pts, n, gw::pose_from(t, q)); }
 
   // ---- multi-GPU (include/mrhash_comm.h; no reference counterpart): one GeoWrapper per process / GPU.
   // commUniqueId() on one rank, the 128 bytes handed to the others by the launcher, then commInit on every rank.
@@ -220,82 +210,89 @@ public:
   static std::array<uint8_t, MRH_COMM_ID_BYTES> commUniqueId();
   void commInit(const std::array<uint8_t, MRH_COMM_ID_BYTES>& id, int rank, int world, int chunk_log2 = 3, bool tile_sharded = true);
   void mergeSubmaps();
-  int commRank() const { return comm_rank_; }
-  int commWorld() const { return comm_world_; }
+  int commRank() const { return comm_.rank; }
+  int commWorld() const { return comm_.world; }
 
   mrh_ctx* ctx() { return ctx_; }
 
 private:
   void check(int rc, const char* what) const;
-  // host side of the streamer (streamer.cuh:40-80, :251-352): chunk grid of streamed-out blocks
-  struct HostBlock {
-    mrh_block_desc desc;
-    std::vector<mrh_voxel> voxels;  // 512, reference layout
-  };
-  std::array<int, 3> worldToChunks(const std::array<float, 3>& pw) const;
-  float chunkRadius() const;
-  bool chunkTouchesSphere(const std::array<int, 3>& chunk, const std::array<float, 3>& center, float radius) const;
-  void streamOutToGrid(const std::array<float, 3>& center, float radius);
-  void streamInFromGrid(const std::array<float, 3>* center, float radius);  // center == nullptr: everything
-  // the chunk loop of extractMesh (geowrapper.cpp:162-188): the reference's own sphere test and stream-in
-  bool chunkInSphereRef(const std::array<int, 3>& chunk, const std::array<float, 3>& center, float radius) const;
-  uint64_t streamInSphereRef(const std::array<float, 3>& center, float radius);
-  std::map<std::array<int, 3>, std::vector<HostBlock>> grid_;
-  bool streaming_enabled_ = true;  // MRHASH_STREAM=0 turns the per-frame test off
-  bool sync_compute_ = false;      // MRH_SYNC_COMPUTE=1: compute() blocks and reports its own frame's flags (the reference's contract)
-  uint32_t flags_announced_ = 0, last_compute_flags_ = 0;
-  float max_depth_ = 0.f;
+
+  // ---- the reference's cached settings (geowrapper.h:80-109): host copies behind the getters and setters
+  struct Settings {
+    int hash_num_buckets = 0, num_sdf_blocks = 0, hash_bucket_size = 10, linked_list_size = 7, max_num_sdf_block_integrate_from_global_hash = 0;
+    int integration_weight_sample, integration_weight_max = 255, n_frames_invalidate_voxels, voxel_extents_scale;
+    float sdf_truncation, sdf_truncation_scale, virtual_voxel_size, sdf_var_threshold, vertices_merging_threshold;
+    uint8_t min_weight_threshold;
+  } set_;
+  std::array<float, 16> pose_;
+  std::array<float, 16> camera_in_lidar_;
+
+  // ---- the camera of the last setCamera, for the renders and the tracking calls
+  struct Camera {
+    bool set = false;
+    int model = MRH_CAMERA_PINHOLE, rows = 0, cols = 0;
+    float fx = 0.f, fy = 0.f, cx = 0.f, cy = 0.f, min_depth = 0.f, max_depth = 0.f;
+    float reach = 0.f;  // farthest distance from the camera centre at which a frame can touch a block
+  } cam_;
+  template <typename Params> Params cameraParams() const;    // intrinsics, shape and depth range of the last setCamera; the rest 0
+  void requireCamera(const char* method, int model) const;   // throws unless setCamera was called with that camera model
   RaycastImages raycastPose(const std::array<float, 16>& pose);
   RaycastScan raycastScanPose(const std::array<float, 16>& pose);
   TrackResult trackDepthPose(const float* depth, size_t rows, size_t cols, const std::array<float, 16>& pose);
   TrackResult trackCloudPose(const float* pts, size_t n, const std::array<float, 16>& pose);
   TrackResult trackPose(const char* who, const float* depth, const float* pts, size_t n, const std::array<float, 16>& pose);
   TrackResult trackSdfPose(const char* who, const float* depth, size_t rows, size_t cols, const float* pts, size_t n, const std::array<float, 16>& pose);
-  template <typename Params> Params cameraParams() const;    // intrinsics, shape and depth range of the last setCamera; the rest 0
-  mrh_raycast_params raycastParams(uint32_t outputs) const;  // the camera of the last setCamera, step = half the truncation
-  void requireCamera(const char* method, int model) const;   // throws unless setCamera was called with that camera model
-  bool has_camera_ = false;  // the camera of the last setCamera, for raycast()
-  int camera_model_ = MRH_CAMERA_PINHOLE, camera_rows_ = 0, camera_cols_ = 0;
-  float camera_fx_ = 0.f, camera_fy_ = 0.f, camera_cx_ = 0.f, camera_cy_ = 0.f, camera_min_depth_ = 0.f;
-  float reach_ = 0.f;  // farthest distance from the camera centre at which a frame can touch a block (set by setCamera)
 
-  int hash_num_buckets_ = 0, num_sdf_blocks_ = 0, hash_bucket_size_ = 10;
-  float sdf_truncation_, sdf_truncation_scale_;
-  int integration_weight_sample_, integration_weight_max_ = 255;
-  float virtual_voxel_size_;
-  int linked_list_size_ = 7;
-  int n_frames_invalidate_voxels_;
-  int max_num_sdf_block_integrate_from_global_hash_ = 0;
-  int voxel_extents_scale_;
-  uint8_t min_weight_threshold_;
-  float sdf_var_threshold_, vertices_merging_threshold_;
-  std::array<float, 16> pose_;
-  std::array<float, 16> camera_in_lidar_;
+  // ---- inputs of compute()
   bool have_depth_ = false, have_rgb_ = false;  // the images themselves live in the library (pinned staging + device slots)
-  std::vector<uint8_t> rgb_;
-  size_t depth_rows_ = 0, depth_cols_ = 0, rgb_rows_ = 0, rgb_cols_ = 0;
   std::vector<float> point_cloud_;
   mutable std::vector<float> normals_;
   bool estimate_normals_ = false;           // setPointCloud(..., compute_normals = true): compute() estimates on the device
   mutable bool normals_on_device_ = false;  // ... and did: normals_ is filled by the first normals() after it
+  bool sync_compute_ = false;               // MRH_SYNC_COMPUTE=1: compute() blocks and reports its own frame's flags (the reference's contract)
+  uint32_t flags_announced_ = 0, last_compute_flags_ = 0;
+
+  // ---- host side of the streamer (gw_chunks.h): the chunk grid of streamed-out blocks
+  gw::ChunkGrid grid_;
+  bool streaming_enabled_ = true;  // MRHASH_STREAM=0 turns the per-frame test off
+  float chunkExt() const { return (float) set_.voxel_extents_scale; }  // chunk edge in metres (geowrapper.cpp:56)
+  void streamOutToGrid(const std::array<float, 3>& center, float radius);
+  void streamInGathered(const char* what, const gw::ChunkGrid::Gathered& g);  // gather -> import -> erase only after the import succeeded
+  void streamInSphere(const std::array<float, 3>& center, float radius);      // every chunk that touches the sphere
+  struct Blocks {
+    std::vector<mrh_block_desc> descs;  // at least one element long, as voxels: data() is never null
+    std::vector<mrh_voxel> voxels;
+    uint64_t n = 0;
+  };
+  Blocks dumpBlocks(const char* what, bool with_voxels);  // the device-resident blocks (mrh_dump_blocks: count, then fill)
+
+  // ---- the mesh of the last extractMesh: a view of the library's buffers (mrh_extract_mesh), copied on the first getter
+  struct MeshView {
+    std::vector<double> V, C;
+    std::vector<int32_t> F;
+    bool cached = true;
+    const double *v = nullptr, *c = nullptr;
+    const int32_t* f = nullptr;
+    uint64_t nv = 0, nf = 0;
+  };
+  mutable MeshView mesh_;
   void cacheMesh() const;
   void writeMesh(const std::string& filename, double t0);
-  mutable std::vector<double> V_, C_;
-  mutable std::vector<int32_t> F_;
-  mutable bool mesh_cached_ = true;
-  const double *mesh_v_ = nullptr, *mesh_c_ = nullptr;  // the library's buffers (mrh_extract_mesh)
-  const int32_t* mesh_f_ = nullptr;
-  uint64_t mesh_nv_ = 0, mesh_nf_ = 0;
-  // 3DGS initialisation: on when a gs_optimization_param_path was given
+
+  // ---- 3DGS initialisation: on when a gs_optimization_param_path was given
   bool gs_enabled_ = false;
   float qtree_thresh_ = 0.1f;
   int qtree_min_pixel_size_ = 1;
   std::vector<mrh_splat_seed> seeds_;
+
   mrh_ctx* ctx_ = nullptr;
-  mrh_comm* comm_ = nullptr;
-  int comm_rank_ = 0, comm_world_ = 1, comm_chunk_log2_ = 3;
-  bool tile_sharded_ = false;
   int device_id_ = 0;
+  struct Comm {
+    mrh_comm* comm = nullptr;
+    int rank = 0, world = 1, chunk_log2 = 3;
+    bool tile_sharded = false;
+  } comm_;
 };
 
 }  // namespace pygeowrapper
