@@ -81,7 +81,7 @@ def build_pybind(force: bool = False, verbose: bool = True) -> str:
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(ROOT, "mrhash_amd", "pygeowrapper" + ext)
     srcs = [os.path.join(CSRC, f) for f in ("geowrapper.cpp", "geowrapper.h", "gw_pose.h", "gw_chunks.h", "gw_files.h", "pygeowrapper.cpp")]
-    srcs += [os.path.join(ROOT, "include", h) for h in ("mrhash_hip.h", "mrhash_raycast.h", "mrhash_normals.h", "mrhash_track.h", "mrhash_esdf.h", "mrhash_query.h", "mrhash_rays.h", "mrhash_remap.h", "mrhash_align.h", "mrhash_sdftrack.h")]
+    srcs += [os.path.join(ROOT, "include", h) for h in ("mrhash_hip.h", "mrhash_raycast.h", "mrhash_normals.h", "mrhash_track.h", "mrhash_esdf.h", "mrhash_query.h", "mrhash_rays.h", "mrhash_freespace.h", "mrhash_remap.h", "mrhash_align.h", "mrhash_sdftrack.h")]
     srcs.append(HIP_LIB)
     if not all(os.path.exists(s) for s in srcs):
         return ""

@@ -174,6 +174,27 @@ class MrhRaysParams(C.Structure):
     _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("step", C.c_float), ("outputs", C.c_uint32), ("reserved", C.c_uint32 * 4)]
 
 
+# every symbol include/mrhash_freespace.h declares (the HIP library only: the oracle has no free-space layer)
+FREESPACE_SYMBOLS = ("mrh_freespace_create mrh_freespace_clear mrh_freespace_destroy mrh_freespace_carve_depth mrh_freespace_carve_depth_device "
+                     "mrh_freespace_carve_points mrh_freespace_carve_points_device mrh_freespace_box mrh_freespace_box_device mrh_freespace_segments "
+                     "mrh_freespace_segments_device").split()
+FREE_FREE, FREE_OBSERVED, FREE_OCCUPIED, FREE_FRONTIER = 1, 2, 4, 8
+FREE_SEG_UNKNOWN, FREE_SEG_BAD = 1, 0x80
+
+
+class MrhFreespaceParams(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("cell_shift", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class MrhCarveParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("min_depth", C.c_float), ("max_depth", C.c_float), ("step", C.c_float), ("margin", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class MrhFreespaceBoxParams(C.Structure):
+    _fields_ = [("origin", C.c_int32 * 3), ("dims", C.c_int32 * 3), ("min_weight", C.c_int32), ("surface_band", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 def normalize_directions(directions) -> np.ndarray:
     """d / len per ray in float32, len = sqrt((dx * dx + dy * dy) + dz * dz): what cast_rays(normalize=True) does on the host (a zero
     direction becomes NaN and is a bad ray)."""
@@ -377,6 +398,21 @@ def _declare(lib: C.CDLL) -> C.CDLL:
         lib.mrh_cast_rays.argtypes = [C.c_void_p, P(MrhRaysParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float)] + [P(C.c_void_p)] * 6
         lib.mrh_cast_rays_device.argtypes = [C.c_void_p, P(MrhRaysParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, P(C.c_float), P(C.c_float)] + [C.c_void_p] * 6
         for name in RAYS_SYMBOLS:
+            getattr(lib, name).restype = C.c_int
+    if hasattr(lib, "mrh_freespace_create"):  # include/mrhash_freespace.h
+        F = P(C.c_float)
+        lib.mrh_freespace_create.argtypes = [C.c_void_p, P(MrhFreespaceParams)]
+        lib.mrh_freespace_clear.argtypes = [C.c_void_p]
+        lib.mrh_freespace_destroy.argtypes = [C.c_void_p]
+        lib.mrh_freespace_carve_depth.argtypes = [C.c_void_p, P(MrhCarveParams), C.c_void_p, F, F]
+        lib.mrh_freespace_carve_depth_device.argtypes = lib.mrh_freespace_carve_depth.argtypes
+        lib.mrh_freespace_carve_points.argtypes = [C.c_void_p, P(MrhCarveParams), C.c_void_p, C.c_uint64, F, F]
+        lib.mrh_freespace_carve_points_device.argtypes = lib.mrh_freespace_carve_points.argtypes
+        lib.mrh_freespace_box.argtypes = [C.c_void_p, P(MrhFreespaceBoxParams), P(C.c_void_p)]
+        lib.mrh_freespace_box_device.argtypes = [C.c_void_p, P(MrhFreespaceBoxParams), C.c_void_p]
+        lib.mrh_freespace_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, P(C.c_void_p), P(C.c_void_p)]
+        lib.mrh_freespace_segments_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p]
+        for name in FREESPACE_SYMBOLS:
             getattr(lib, name).restype = C.c_int
     if hasattr(lib, "mrh_resample_map"):  # include/mrhash_remap.h
         lib.mrh_resample_map.argtypes = [C.c_void_p, P(MrhRemapParams), P(C.c_float), P(C.c_float), P(C.c_void_p), P(C.c_uint64), P(MrhRemapInfo)]
@@ -1032,6 +1068,116 @@ class Engine:
         reach = float(finite.max()) if len(finite) else 0.0
         out = self.cast_rays(a, d, max_range=reach, min_range=0.0, step=step, tmax=ln, normals=False, colors=False, counts=False, normalize=True)
         return out["status"] == 0
+
+    # -- the free-space layer (include/mrhash_freespace.h) ----------------------------------------------
+    def freespace_create(self, origin, dims, cell_shift=3):
+        """mrh_freespace_create: an empty layer over the box of cells origin + [0, dims) (x, y, z); a cell is
+        2^cell_shift finest voxels per side.  Replaces an existing layer."""
+        o, n = [int(x) for x in origin], [int(x) for x in dims]
+        if len(o) != 3 or len(n) != 3:
+            raise ValueError("freespace_create: origin and dims are triples (x, y, z)")
+        p = MrhFreespaceParams((C.c_int32 * 3)(*o), (C.c_int32 * 3)(*n), int(cell_shift), 0)
+        self._check(self.lib.mrh_freespace_create(self._ctx, C.byref(p)))
+
+    def freespace_clear(self):
+        """Every bit of the layer 0; the box stays."""
+        self._check(self.lib.mrh_freespace_clear(self._ctx))
+
+    def freespace_destroy(self):
+        """The context has no layer afterwards."""
+        self._check(self.lib.mrh_freespace_destroy(self._ctx))
+
+    @staticmethod
+    def _carve_params(fx, fy, cx, cy, rows, cols, min_depth, max_depth, step, margin):
+        return MrhCarveParams(float(fx), float(fy), float(cx), float(cy), int(rows), int(cols), float(min_depth), float(max_depth), float(step), float(margin))
+
+    def freespace_carve_depth(self, depth, fx, fy, cx, cy, R, t, min_depth, max_depth, step=0.0, margin=0.0):
+        """Carves the depth image [rows, cols] f32 seen from the camera-to-world pose (R, t) into the layer (mrh_freespace_carve_depth):
+        every pixel's ray sets the cells of its samples min_depth + k * step (step 0 = half a cell) up to depth - margin, or up to
+        max_depth where the pixel saw nothing nearer.  Blocks; does not flush kept-back or pipelined frames."""
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if d.ndim != 2:
+            raise ValueError("freespace_carve_depth: the image is a 2D array")
+        p = self._carve_params(fx, fy, cx, cy, d.shape[0], d.shape[1], min_depth, max_depth, step, margin)
+        pR, pt, _keep = self._pose_args(R, t)
+        self._check(self.lib.mrh_freespace_carve_depth(self._ctx, C.byref(p), d.ctypes.data, pR, pt))
+
+    def freespace_carve_depth_device(self, d_depth, fx, fy, cx, cy, rows, cols, R, t, min_depth, max_depth, step=0.0, margin=0.0):
+        """mrh_freespace_carve_depth_device: the same from a device image [rows, cols] f32 (an integer pointer).  Enqueues on the
+        context's stream; the image must stay valid until sync() or a blocking call."""
+        p = self._carve_params(fx, fy, cx, cy, rows, cols, min_depth, max_depth, step, margin)
+        pR, pt, _keep = self._pose_args(R, t)
+        self._check(self.lib.mrh_freespace_carve_depth_device(self._ctx, C.byref(p), d_depth or None, pR, pt))
+
+    def freespace_carve_points(self, points, R, t, min_depth, max_depth, step=0.0, margin=0.0):
+        """Carves the sensor-frame points [n, 3] f32 seen from the sensor-to-world pose (R, t) (mrh_freespace_carve_points): every
+        point's ray from the sensor sets the cells of its samples up to min(range, max_depth) - margin.  Blocks."""
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        p = self._carve_params(0, 0, 0, 0, 0, 0, min_depth, max_depth, step, margin)
+        pR, pt, _keep = self._pose_args(R, t)
+        self._check(self.lib.mrh_freespace_carve_points(self._ctx, C.byref(p), pts.ctypes.data if len(pts) else None, len(pts), pR, pt))
+
+    def freespace_carve_points_device(self, d_points, n, R, t, min_depth, max_depth, step=0.0, margin=0.0):
+        """mrh_freespace_carve_points_device: the same from a device list [n, 3] f32 (an integer pointer).  Enqueues."""
+        p = self._carve_params(0, 0, 0, 0, 0, 0, min_depth, max_depth, step, margin)
+        pR, pt, _keep = self._pose_args(R, t)
+        self._check(self.lib.mrh_freespace_carve_points_device(self._ctx, C.byref(p), d_points or None, int(n), pR, pt))
+
+    @staticmethod
+    def _freespace_box_params(origin, dims, min_weight, surface_band):
+        o, n = [int(x) for x in origin], [int(x) for x in dims]
+        if len(o) != 3 or len(n) != 3:
+            raise ValueError("freespace_box: origin and dims are triples (x, y, z)")
+        return MrhFreespaceBoxParams((C.c_int32 * 3)(*o), (C.c_int32 * 3)(*n), int(min_weight), float(surface_band))
+
+    def freespace_box(self, origin, dims, min_weight=0, surface_band=0.0):
+        """The state byte of every cell of the box origin + [0, dims) of cells (mrh_freespace_box): a numpy copy [nz, ny, nx] u8 of
+        FREE_FREE | FREE_OBSERVED | FREE_OCCUPIED | FREE_FRONTIER.  The frontier looks at neighbours inside the box only: pad by one
+        cell.  The box may extend beyond the layer."""
+        p = self._freespace_box_params(origin, dims, min_weight, surface_band)
+        ps = C.c_void_p()
+        self._check(self.lib.mrh_freespace_box(self._ctx, C.byref(p), C.byref(ps)))
+        nx, ny, nz = (int(x) for x in dims)
+        return _copy_out(ps, nx * ny * nz, np.uint8, (nz, ny, nx))
+
+    def freespace_box_device(self, origin, dims, d_state, min_weight=0, surface_band=0.0):
+        """mrh_freespace_box_device: enqueues the box into the caller's device buffer of nx * ny * nz bytes (an integer pointer)."""
+        p = self._freespace_box_params(origin, dims, min_weight, surface_band)
+        self._check(self.lib.mrh_freespace_box_device(self._ctx, C.byref(p), d_state or None))
+
+    def freespace_segments(self, a, b, step=0.0):
+        """The segments a[i] -> b[i] ([n, 3] each, world frame) against the layer (mrh_freespace_segments): samples every `step`
+        (0 = half a cell) from a.  Returns numpy copies (status u8 [n]: 0 = every sample lies in a free cell, FREE_SEG_UNKNOWN,
+        FREE_SEG_BAD; counts u32 [n, 2] = (n_samples, n_free))."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+        n = len(a)
+        if len(b) != n:
+            raise ValueError("freespace_segments: %d starts, %d ends" % (n, len(b)))
+        ps, pc = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.mrh_freespace_segments(self._ctx, a.ctypes.data if n else None, b.ctypes.data if n else None, n, float(step), C.byref(ps), C.byref(pc)))
+        return _copy_out(ps, n, np.uint8, (n,)), _copy_out(pc, 2 * n, np.uint32, (n, 2))
+
+    def freespace_segments_device(self, d_a, d_b, n, d_status, d_counts=0, step=0.0):
+        """mrh_freespace_segments_device: n segments from device lists into caller device buffers ([n] u8 required, [n, 2] u32 or 0;
+        integer pointers).  Enqueues."""
+        self._check(self.lib.mrh_freespace_segments_device(self._ctx, d_a or None, d_b or None, int(n), float(step), d_status or None, d_counts or None))
+
+    def line_of_sight_free(self, a, b, step=0.0):
+        """bool [n]: the segment a[i] -> b[i] crosses no surface (cast_rays: status & (RAY_HIT | RAY_INSIDE) == 0, with
+        line_of_sight's ray) AND every sample of it lies in a carved cell (freespace_segments: status 0).  Where line_of_sight
+        asks the map for observed free space, which it only knows near surfaces, this asks the free-space layer."""
+        a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3)
+        b = np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 3)
+        if len(a) == 0:
+            return np.zeros(0, bool)
+        d = (b - a).astype(np.float32)
+        ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
+        finite = ln[np.isfinite(ln)]
+        reach = float(finite.max()) if len(finite) else 0.0
+        cast = self.cast_rays(a, d, max_range=reach, min_range=0.0, step=0.0, tmax=ln, normals=False, colors=False, counts=False, normalize=True)["status"]
+        seg, _ = self.freespace_segments(a, b, step)
+        return ((cast & (RAY_HIT | RAY_INSIDE)) == 0) & (seg == 0)  # a == b is a bad ray and a one-sample segment: the point's cell decides
 
     # -- map-to-map fusion (include/mrhash_remap.h) ----------------------------------------------------
     @staticmethod

@@ -32,6 +32,7 @@
 #include "../../include/mrhash_esdf.h"
 #include "../../include/mrhash_query.h"
 #include "../../include/mrhash_rays.h"
+#include "../../include/mrhash_freespace.h"
 #include "../../include/mrhash_track.h"
 #include "../../include/mrhash_align.h"
 #include "../../include/mrhash_sdftrack.h"
@@ -42,6 +43,7 @@
 #include "mrh_esdf.h"
 #include "mrh_query.h"
 #include "mrh_rays.h"
+#include "mrh_freespace.h"
 #include "mrh_remap.h"
 #include "mrh_track.h"
 #include "mrh_align.h"
@@ -296,6 +298,7 @@ int mrh_reset(mrh_ctx* c) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   rc = drain_events(c);
   if (rc) return rc;
+  if (c->free.on) HIP_TRY(c, hipMemsetAsync(c->free.d_words, 0, (size_t) c->free.L.n_words * sizeof(u32), c->stream));  // the bits go, the box stays
   return init_buffers(c);
 }
 

@@ -446,6 +446,20 @@ struct mrh_ctx {
     char* d_out = nullptr; size_t cap = 0;
     char* h_out = nullptr; size_t h_cap = 0;
   } rays;
+  // the free-space layer (mrh_readers.h, kernels in mrh_freespace.h): `on` and the box once mrh_freespace_create has run, the
+  // words (capacity in words, grow-only; `L.n_words` of them are the layer).  Scratch and results of mrh_freespace_box, grow-only,
+  // in cells: the classified bytes, the finished bytes, their pinned copy.  Results of mrh_freespace_segments, grow-only, in
+  // segments: [counts 2 x u32 | status u8] on the device and pinned.  The carves' and the segments' host input comes through `stage`
+  struct Free {
+    bool on = false;
+    mrh::FreeLayer L = {};
+    u32* d_words = nullptr; size_t cap = 0;
+    uint8_t* d_cls = nullptr; size_t cls_cap = 0;
+    uint8_t* d_state = nullptr; size_t state_cap = 0;
+    uint8_t* h_state = nullptr; size_t h_cap = 0;
+    char* d_seg = nullptr; size_t seg_cap = 0;
+    char* h_seg = nullptr; size_t h_seg_cap = 0;
+  } free;
   // map-to-map fusion (mrh_readers.h, kernels in mrh_remap.h), grow-only — per candidate slot the two (key, value) pairs of the
   // sort, the marks and positions of the scans, with them the sort's histogram and the scans' tile sums; one counter (valid
   // voxels); the records of the last call (bytes)
@@ -471,8 +485,8 @@ struct mrh_ctx {
   // sums k_track_finish leaves for the host.  One per context is enough: its users run on this context's stream and block
   struct Fit { long long* d_slab = nullptr; size_t slab_cap = 0; long long* h_sums = nullptr; } fit;
   // host input staged onto the device (mrh_readers.h: stage_obs), one pair of buffers, pinned and device, grow-only, in floats.
-  // Four users: the depth image of mrh_track_depth, the cloud of mrh_track_scan, the points of mrh_query_points and the rays of
-  // mrh_cast_rays.  Each
+  // Its users: the depth image of mrh_track_depth, the cloud of mrh_track_scan, the points of mrh_query_points, the rays of
+  // mrh_cast_rays, and the images, clouds and segments of the free-space calls.  Each
   // overwrites what the last one left, which is safe because every user blocks before it returns: nothing reads the pair then
   struct Stage { float* h = nullptr; size_t h_cap = 0; float* d = nullptr; size_t d_cap = 0; } stage;
   int* d_keep = nullptr;  // the frame path's CTR_COMPACT while a reader borrows the compact list (mrh_blocks.h: borrow_live_blocks)

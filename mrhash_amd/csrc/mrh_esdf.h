@@ -38,49 +38,69 @@ __device__ __forceinline__ u32 esdf_classify(const Map& m, const EsdfBox& bx, co
   return st;
 }
 
-// One workgroup per 8^3 brick of voxel space the box touches (grid: bricks per axis), two cells per lane.  Where voxel -> block
-// is the arithmetic shift for the whole brick, the brick IS one map block: it is resolved once and its planes are read
-// directly (a coarse block's 64 voxels each answer for the 2^3 cells they cover); elsewhere every cell takes get_voxel_i.
+// One 8^3 brick of voxel space as a workgroup of 256 lanes reads it (k_esdf_classify here, k_freespace_classify in
+// mrh_freespace.h).  Where voxel -> block is the arithmetic shift for the whole brick, the brick IS one map block: it is resolved
+// once and its planes are read directly (a coarse block's 64 voxels each answer for the 2^3 cells they cover); elsewhere every
+// voxel takes get_voxel_i.
+struct EsdfBrick {
+  i3 v0;        // the brick's first voxel
+  bool direct;  // uniform
+  u32 val;      // direct: the block's table value (kNbAbsent: no block)
+  Neigh nb;
+};
+// brick b, by the whole workgroup: s_val is one word of LDS, and the call holds a barrier when the brick is direct (uniform)
+__device__ __forceinline__ EsdfBrick esdf_brick(const Map& m, const Tab& t, const i3 b, u32* s_val) {
+  EsdfBrick br;
+  br.v0 = mki3(b.x * kBlockSide, b.y * kBlockSide, b.z * kBlockSide);
+  const i3 v0 = br.v0;
+  // |coordinate| of every cell of the brick is at most this (|v0| <= 2^23 + 8: no overflow)
+  const int amax = max(max(max(abs(v0.x), abs(v0.x + kBlockSide - 1)), max(abs(v0.y), abs(v0.y + kBlockSide - 1))), max(abs(v0.z), abs(v0.z + kBlockSide - 1)));
+  br.direct = amax < m.block_shift_limit;  // uniform
+  br.nb = neigh_none();
+  br.nb.shift_limit = m.block_shift_limit;
+  if (br.direct) {
+    if (threadIdx.x == 0) *s_val = block_val(t, br.nb, b);
+    __syncthreads();
+  }
+  br.val = br.direct ? *s_val : kNbAbsent;
+  return br;
+}
+// the D16 state of the brick's voxel (lx, ly, lz) under bx's two gates, and its sdf
+__device__ __forceinline__ u32 esdf_brick_voxel(const Map& m, const Tab& t, const EsdfBox& bx, const EsdfBrick& br, const int lx, const int ly, const int lz,
+                                                float& sdf) {
+  sdf = 0.f;
+  u32 rgbw = 0;
+  int res = 0;
+  bool found = false;
+  if (br.direct) {
+    if (br.val != kNbAbsent) {
+      found = true;
+      res = (br.val & kValCoarseBit) ? 1 : 0;
+      const VoxPtr vp = vox_ptr(t, br.val);
+      const int idx = res ? (lz >> 1) * 16 + (ly >> 1) * 4 + (lx >> 1) : lz * 64 + ly * 8 + lx;
+      sdf = vp.sdf[idx];
+      rgbw = vp.rgbw[idx];
+    }
+  } else {
+    const VoxSample s = get_voxel_i(m, t, br.nb, mki3(br.v0.x + lx, br.v0.y + ly, br.v0.z + lz));
+    found = s.found; res = s.res; sdf = s.sdf; rgbw = s.rgbw;
+  }
+  return esdf_classify(m, bx, found, res, sdf, rgbw);
+}
+
+// One workgroup per 8^3 brick of voxel space the box touches (grid: bricks per axis), two cells per lane
 __global__ __launch_bounds__(256) void k_esdf_classify(const Map m, const Tab t, const EsdfBox bx, uint8_t* __restrict__ state,
                                                        float* __restrict__ dist) {
   __shared__ u32 s_val;
-  const i3 b = mki3((bx.ox >> 3) + (int) blockIdx.x, (bx.oy >> 3) + (int) blockIdx.y, (bx.oz >> 3) + (int) blockIdx.z);
-  const i3 v0 = mki3(b.x * kBlockSide, b.y * kBlockSide, b.z * kBlockSide);
-  // |coordinate| of every cell of the brick is at most this (|v0| <= 2^23 + 8: no overflow)
-  const int amax = max(max(max(abs(v0.x), abs(v0.x + kBlockSide - 1)), max(abs(v0.y), abs(v0.y + kBlockSide - 1))), max(abs(v0.z), abs(v0.z + kBlockSide - 1)));
-  const bool direct = amax < m.block_shift_limit;  // uniform
-  Neigh nb = neigh_none();
-  nb.shift_limit = m.block_shift_limit;
-  if (direct) {
-    if (threadIdx.x == 0) s_val = block_val(t, nb, b);
-    __syncthreads();
-  }
-  const u32 val = direct ? s_val : kNbAbsent;
+  const EsdfBrick br = esdf_brick(m, t, mki3((bx.ox >> 3) + (int) blockIdx.x, (bx.oy >> 3) + (int) blockIdx.y, (bx.oz >> 3) + (int) blockIdx.z), &s_val);
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int li = (int) threadIdx.x + 256 * h;
     const int lx = li & 7, ly = (li >> 3) & 7, lz = li >> 6;
-    const i3 v = mki3(v0.x + lx, v0.y + ly, v0.z + lz);
-    const int i = v.x - bx.ox, j = v.y - bx.oy, k = v.z - bx.oz;
+    const int i = br.v0.x + lx - bx.ox, j = br.v0.y + ly - bx.oy, k = br.v0.z + lz - bx.oz;
     if ((u32) i >= (u32) bx.nx || (u32) j >= (u32) bx.ny || (u32) k >= (u32) bx.nz) continue;
-    float sdf = 0.f;
-    u32 rgbw = 0;
-    int res = 0;
-    bool found = false;
-    if (direct) {
-      if (val != kNbAbsent) {
-        found = true;
-        res = (val & kValCoarseBit) ? 1 : 0;
-        const VoxPtr vp = vox_ptr(t, val);
-        const int idx = res ? (lz >> 1) * 16 + (ly >> 1) * 4 + (lx >> 1) : li;
-        sdf = vp.sdf[idx];
-        rgbw = vp.rgbw[idx];
-      }
-    } else {
-      const VoxSample s = get_voxel_i(m, t, nb, v);
-      found = s.found; res = s.res; sdf = s.sdf; rgbw = s.rgbw;
-    }
-    const u32 st = esdf_classify(m, bx, found, res, sdf, rgbw);
+    float sdf;
+    const u32 st = esdf_brick_voxel(m, t, bx, br, lx, ly, lz, sdf);
     const size_t cell = esdf_cell(bx, i, j, k);
     state[cell] = (uint8_t) st;
     if (st & ESDF_SITE) dist[cell] = sdf;

@@ -1,5 +1,5 @@
 // mrh_readerplan.h — the argument plans of the features that only read the map (mrh_readers.h: raycast, distance field, tracking,
-// render-free tracking, point queries, ray queries, map-to-map fusion and registration)
+// render-free tracking, point queries, ray queries, the free-space layer, map-to-map fusion and registration)
 // and of the scan normals (mrh_points.h): the plain structs their kernels take, and per feature one function that turns the caller's
 // parameter block plus the few context values it depends on — each passed by value — into that struct, or into an error code and
 // the message the C ABI reports for it.  Plain host C++17, no HIP header, no mrh_ctx: the kernel headers include it for the
@@ -18,6 +18,7 @@
 #include "../../include/mrh_softmath.h"
 #include "../../include/mrhash_align.h"
 #include "../../include/mrhash_esdf.h"
+#include "../../include/mrhash_freespace.h"
 #include "../../include/mrhash_normals.h"
 #include "../../include/mrhash_query.h"
 #include "../../include/mrhash_rays.h"
@@ -106,6 +107,40 @@ struct SdfTrackLin {
   float s_a;               // mrh_track::angle_scale(max_depth)
   float bound;             // (float) (1 << 20) * vs: a sample is rejected unless |W_a| < bound on every axis
   float R[9], t[3];        // R32 and t32
+};
+
+// the free-space layer (mrh_freespace.h, include/mrhash_freespace.h): its box of cells and the shape of its words.  A word is a
+// 4 x 4 x 2 brick of cells (bit = x & 3 | (y & 3) << 2 | (z & 1) << 4), bricks x fastest
+struct FreeLayer {
+  int ox, oy, oz;       // origin, cells
+  int nx, ny, nz;       // 1 .. 1024 each
+  int shift;            // s: a cell is 2^s finest voxels per side
+  int nbx, nby;         // bricks along x and y: (nx + 3) / 4, (ny + 3) / 4
+  uint32_t n_words;     // nbx * nby * ((nz + 1) / 2)
+};
+
+// what k_freespace_carve takes: the camera (the points form uses its samples and pose alone), the ray count of the points form,
+// the margin and the refusal bound
+struct CarveArgs {
+  RayCam cam;           // n_samples: samples z_k <= max_depth; step: the default filled in
+  uint32_t n;           // points form: points, 1 .. 2^24
+  float margin;
+  float bound;          // (float) (1 << 20) * vs: a sample sets nothing unless |P_a| < bound on every axis
+};
+
+// what k_freespace_classify and k_freespace_frontier take: the box in cells, and the same box in finest voxels with the two gates
+// of D16 as esdf_classify reads them (vox.reach is unused)
+struct FreeBox {
+  int ox, oy, oz;       // origin, cells
+  int nx, ny, nz;       // 1 .. 512 each
+  EsdfBox vox;          // origin << s, dims << s, w_min, band
+};
+
+// what k_freespace_segments takes
+struct SegArgs {
+  uint32_t n;           // segments, 1 .. 2^24
+  float step;           // the default filled in
+  float bound;          // (float) (1 << 20) * vs
 };
 
 // the parameters of the normal-estimation kernels (mrh_normals.h), defaults filled in
@@ -369,6 +404,131 @@ inline int rays(char* msg, const char* who, const mrh_rays_params* p, const bool
   return MRH_OK;
 }
 static_assert(MRH_RAYS_MAX_SAMPLES == MRH_RAYCAST_MAX_SAMPLES, "one sample count serves the render and the ray queries");
+
+// ---- the free-space layer (include/mrhash_freespace.h) ----
+
+// what every free-space call but the create needs after whole_map: a layer
+inline int freespace_layer(char* msg, const char* who, const bool have_layer, const int pending, const int shard_count) {
+  if (const int e = whole_map(msg, who, "have no free-space layer", pending, shard_count)) return e;
+  if (!have_layer) return refuse(msg, MRH_ERR_STATE, "%s: the context has no free-space layer (call mrh_freespace_create)", who);
+  return MRH_OK;
+}
+
+// half a cell: the default sample spacing of the carves and of the segments
+inline float freespace_half_cell(const float voxel_size, const int shift) { return 0.5f * (voxel_size * (float) (1 << shift)); }
+
+// mrh_freespace_create; fills the layer's box and word shape.  The order: null argument -> pending, sharded -> reserved word ->
+// cell_shift -> dims per axis -> the cell count -> the voxel span per axis
+inline int freespace_create(char* msg, const char* who, const mrh_freespace_params* p, const int pending, const int shard_count, mrh::FreeLayer* out) {
+  if (!p) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = whole_map(msg, who, "have no free-space layer", pending, shard_count)) return e;
+  if (p->reserved) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  if (p->cell_shift < 0 || p->cell_shift > MRH_FREESPACE_MAX_SHIFT) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: cell_shift %d (0 .. %d)", who, p->cell_shift, MRH_FREESPACE_MAX_SHIFT);
+  for (int a = 0; a < 3; a++)
+    if (p->dims[a] < 1 || p->dims[a] > MRH_FREESPACE_MAX_SIDE)
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: layer of %d x %d x %d cells (1 .. %d per side)", who, p->dims[0], p->dims[1], p->dims[2], MRH_FREESPACE_MAX_SIDE);
+  const uint64_t cells = (uint64_t) p->dims[0] * (uint64_t) p->dims[1] * (uint64_t) p->dims[2];
+  if (cells > (uint64_t) MRH_FREESPACE_MAX_CELLS)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: layer of %llu cells (limit 2^28)", who, (unsigned long long) cells);
+  for (int a = 0; a < 3; a++) {
+    const int64_t lo = (int64_t) p->origin[a] * (1ll << p->cell_shift), hi = ((int64_t) p->origin[a] + p->dims[a]) * (1ll << p->cell_shift) - 1;
+    if (lo < -(1ll << 23) || hi >= (1ll << 23))
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: axis %d of the layer spans voxels %lld .. %lld, outside [-2^23, 2^23)", who, a, (long long) lo, (long long) hi);
+  }
+  out->ox = p->origin[0]; out->oy = p->origin[1]; out->oz = p->origin[2];
+  out->nx = p->dims[0]; out->ny = p->dims[1]; out->nz = p->dims[2];
+  out->shift = p->cell_shift;
+  out->nbx = (out->nx + 3) / 4; out->nby = (out->ny + 3) / 4;
+  out->n_words = (uint32_t) out->nbx * (uint32_t) out->nby * (uint32_t) ((out->nz + 1) / 2);  // <= 256 * 256 * 512
+  return MRH_OK;
+}
+
+// the arguments the four carves share; fills the kernel's arguments.  depth_form: a depth image of p->rows x p->cols pixels, else
+// a cloud of n points; have_obs: the image or the cloud was given (an empty cloud needs none); voxel_size and shift: the default
+// step and the bound.  The sample count and the pose test are the render's.  The order: null argument -> more than 2^24 points ->
+// pending, sharded, no layer -> reserved words -> (depth form) image shape, intrinsics -> depth range -> margin -> step -> the
+// pose -> samples
+inline int freespace_carve(char* msg, const char* who, const bool depth_form, const mrh_carve_params* p, const bool have_obs, const uint64_t n, const float* R,
+                           const float* t, const bool have_layer, const float voxel_size, const int shift, const int pending, const int shard_count,
+                           mrh::CarveArgs* out) {
+  if (!p || (!have_obs && (depth_form || n != 0)) || !R || !t) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (!depth_form && n > (uint64_t) MRH_FREESPACE_MAX_POINTS) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %llu points in one call (limit 2^24)", who, (unsigned long long) n);
+  if (const int e = freespace_layer(msg, who, have_layer, pending, shard_count)) return e;
+  if (p->reserved[0] || p->reserved[1]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  mrh::RayCam& rc = out->cam;
+  rc.ifx = rc.ify = rc.cx = rc.cy = 0.f;
+  rc.rows = rc.cols = 0;
+  if (depth_form) {
+    if (p->rows < 1 || p->rows > MRH_RAYCAST_MAX_SIDE || p->cols < 1 || p->cols > MRH_RAYCAST_MAX_SIDE)
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: image of %d x %d pixels (1 .. %d per side)", who, p->rows, p->cols, MRH_RAYCAST_MAX_SIDE);
+    if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || p->fx == 0.f || p->fy == 0.f || !std::isfinite(p->cx) || !std::isfinite(p->cy))
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: bad intrinsics", who);
+    rc.ifx = 1.0f / p->fx; rc.ify = 1.0f / p->fy;
+    rc.cx = p->cx; rc.cy = p->cy;
+    rc.rows = p->rows; rc.cols = p->cols;
+  }
+  if (!(p->min_depth >= 0.f) || !(p->max_depth > p->min_depth) || !std::isfinite(p->max_depth))
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: need 0 <= min_depth < max_depth (got %g, %g)", who, (double) p->min_depth, (double) p->max_depth);
+  if (!(p->margin >= 0.f) || !std::isfinite(p->margin)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: margin %g", who, (double) p->margin);
+  const float step = p->step == 0.f ? freespace_half_cell(voxel_size, shift) : p->step;
+  if (!(step > 0.f) || !std::isfinite(step)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
+  if (const int e = finite_pose(msg, who, R, t)) return e;
+  const uint32_t n_samples = ray_sample_count(p->min_depth, p->max_depth, step);
+  if (!n_samples)
+    return refuse(msg, MRH_ERR_INVALID_ARG, "%s: more than 2^20 samples per ray (min_depth %g, max_depth %g, step %g)", who, (double) p->min_depth,
+                  (double) p->max_depth, (double) step);
+  rc.min_depth = p->min_depth; rc.max_depth = p->max_depth; rc.step = step;
+  rc.n_samples = n_samples;
+  for (int i = 0; i < 9; i++) rc.R[i] = R[i];
+  for (int i = 0; i < 3; i++) rc.t[i] = t[i];
+  out->n = depth_form ? 0u : (uint32_t) n;
+  out->margin = p->margin;
+  out->bound = (float) (1 << 20) * voxel_size;
+  return MRH_OK;
+}
+static_assert(MRH_FREESPACE_MAX_SAMPLES == MRH_RAYCAST_MAX_SAMPLES, "one sample count serves the render and the carves");
+
+// the arguments both box readers share; fills the kernels' box.  have_out: the required output was given.  The order: null argument
+// -> pending, sharded, no layer -> reserved words -> dims per axis, the voxel span per axis -> surface_band -> min_weight
+inline int freespace_box(char* msg, const char* who, const mrh_freespace_box_params* p, const bool have_out, const bool have_layer, const int shift,
+                         const int min_weight_threshold, const int pending, const int shard_count, mrh::FreeBox* out) {
+  if (!p || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = freespace_layer(msg, who, have_layer, pending, shard_count)) return e;
+  if (p->reserved[0] || p->reserved[1]) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: a reserved word is not 0", who);
+  for (int a = 0; a < 3; a++) {
+    if (p->dims[a] < 1 || p->dims[a] > MRH_FREESPACE_BOX_MAX_SIDE)
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: box of %d x %d x %d cells (1 .. %d per side)", who, p->dims[0], p->dims[1], p->dims[2], MRH_FREESPACE_BOX_MAX_SIDE);
+    const int64_t lo = (int64_t) p->origin[a] * (1ll << shift), hi = ((int64_t) p->origin[a] + p->dims[a]) * (1ll << shift) - 1;
+    if (lo < -(1ll << 23) || hi >= (1ll << 23))
+      return refuse(msg, MRH_ERR_INVALID_ARG, "%s: axis %d of the box spans voxels %lld .. %lld, outside [-2^23, 2^23)", who, a, (long long) lo, (long long) hi);
+  }
+  if (!std::isfinite(p->surface_band) || p->surface_band < 0.f) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: surface_band %g", who, (double) p->surface_band);
+  if (p->min_weight < 0) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: min_weight %d", who, p->min_weight);
+  out->ox = p->origin[0]; out->oy = p->origin[1]; out->oz = p->origin[2];
+  out->nx = p->dims[0]; out->ny = p->dims[1]; out->nz = p->dims[2];
+  mrh::EsdfBox& v = out->vox;
+  v.ox = p->origin[0] * (1 << shift); v.oy = p->origin[1] * (1 << shift); v.oz = p->origin[2] * (1 << shift);
+  v.nx = p->dims[0] << shift; v.ny = p->dims[1] << shift; v.nz = p->dims[2] << shift;
+  v.reach = 0;
+  v.w_min = std::max(1, p->min_weight ? p->min_weight : min_weight_threshold);
+  v.band = p->surface_band;
+  return MRH_OK;
+}
+
+// the arguments both segment calls share.  have_in: both endpoint lists were given (n == 0 needs none); have_out: the required
+// output was (the blocking call has none: true).  The order: null argument -> pending, sharded, no layer -> n -> step
+inline int freespace_segments(char* msg, const char* who, const bool have_in, const bool have_out, const uint64_t n, const float step_in, const bool have_layer,
+                              const float voxel_size, const int shift, const int pending, const int shard_count, mrh::SegArgs* out) {
+  if ((!have_in && n != 0) || !have_out) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: null argument", who);
+  if (const int e = freespace_layer(msg, who, have_layer, pending, shard_count)) return e;
+  if (n > (uint64_t) MRH_FREESPACE_MAX_POINTS) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: %llu segments in one call (limit 2^24)", who, (unsigned long long) n);
+  const float step = step_in == 0.f ? freespace_half_cell(voxel_size, shift) : step_in;
+  if (!(step > 0.f) || !std::isfinite(step)) return refuse(msg, MRH_ERR_INVALID_ARG, "%s: the sample spacing must be > 0 (step %g)", who, (double) step);
+  out->n = (uint32_t) n;
+  out->step = step;
+  out->bound = (float) (1 << 20) * voxel_size;
+  return MRH_OK;
+}
 
 // ---- map-to-map fusion (include/mrhash_remap.h) ----
 

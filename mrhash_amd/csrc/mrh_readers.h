@@ -1,13 +1,15 @@
 // mrh_readers.h — the host side of the features that only read the map, behind the C ABI: raycasting (mrh_raycast[_spherical]
 // [_device], kernels in mrh_raycast.h), distance fields (mrh_esdf[_device], mrh_esdf.h), tracking (mrh_track_depth / _scan
 // [_device], mrh_track.h), render-free tracking (mrh_track_depth_sdf / _points_sdf[_device], mrh_sdftrack.h), point queries
-// (mrh_query_points[_device], mrh_query.h), ray queries (mrh_cast_rays[_device], mrh_rays.h), map-to-map fusion (mrh_resample_map / mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
+// (mrh_query_points[_device], mrh_query.h), ray queries (mrh_cast_rays[_device], mrh_rays.h), the free-space layer (mrh_freespace_*,
+// mrh_freespace.h; its carves and segments do not read the map and come in through free_enter), map-to-map fusion (mrh_resample_map /
+// mrh_fuse_map, mrh_remap.h; the merge itself is mrh_blocks.h's unpack_records) and map-to-map registration (mrh_align_map,
 // mrh_align.h).  What they share is here once: the way in (reader_enter: null context, the feature's argument plan from
 // mrh_readerplan.h, ensure_ready; pair_enter and source_rc for the calls on two contexts), the way the blocking calls hand their
 // result planes out of pinned memory (read_planes), the scan of u64 counts with its total (scan_total), host input through the one
 // staging pair (stage_obs) and the two pose fits' reduction (linearise_sums) under the loop, the solve, the update and the
 // report of mrh_tracksolve.h; the live-block list of the readers that walk the whole map is mrh_blocks.h's borrow_live_blocks.
-// The state is mrh_ctx::ray, ::esdf, ::trk, ::query, ::rays, ::remap, ::align, ::fit and ::stage.  Included by mrh_capi.hip, same translation
+// The state is mrh_ctx::ray, ::esdf, ::trk, ::query, ::rays, ::free, ::remap, ::align, ::fit and ::stage.  Included by mrh_capi.hip, same translation
 // unit: it needs the context's internals (mrh_ctx, HIP_TRY, fail, regrow / regrow_all / regrow_pinned, pinned_alloc, ensure_ready).
 #pragma once
 
@@ -355,6 +357,84 @@ int stage_rays(mrh_ctx* c, const float* origins, const float* dirs, const float*
   return MRH_OK;
 }
 
+// ---- the free-space layer (include/mrhash_freespace.h) -------------------------------------------------------------------------
+
+// The way in of the calls that neither read nor change the map — create, clear, destroy, the carves, the segments: a null context,
+// what plan(msg) refuses, the device.  No ensure_ready: a frame mrh_integrate kept back stays kept back and pipelined frames stay
+// in flight (D22).  That is safe because these calls touch mrh_ctx::free and mrh_ctx::stage alone, which the frame path never
+// does, and enqueue on the context's stream, where they are ordered with the readers of the layer
+template <typename PlanFn>
+int free_enter(mrh_ctx* c, const char* who, PlanFn&& plan) {
+  if (!c) return MRH_ERR_INVALID_ARG;
+  char msg[mrh_plan::kMsgBytes];
+  const int rc = plan(msg);
+  return rc ? fail(c, rc, "%s", msg) : ensure_device(c, who);
+}
+
+int free_layer_enter(mrh_ctx* c, const char* who) {
+  return free_enter(c, who, [&](char* msg) { return mrh_plan::freespace_layer(msg, who, c->free.on, c->pending, c->map.shard_count); });
+}
+
+// the four carves: plan, host input through the staging pair, one launch; the host forms block
+int carve_run(mrh_ctx* c, const char* who, const bool depth_form, const mrh_carve_params* p, const float* host, const float* dev, const uint64_t n, const float* R,
+              const float* t) {
+  CarveArgs a;
+  int rc = free_enter(c, who, [&](char* msg) {
+    return mrh_plan::freespace_carve(msg, who, depth_form, p, host || dev, n, R, t, c->free.on, c->map.vs, c->free.L.shift, c->pending, c->map.shard_count, &a);
+  });
+  if (rc) return rc;
+  const size_t n_obs = depth_form ? (size_t) a.cam.rows * (size_t) a.cam.cols : (size_t) n;
+  if (n_obs == 0) return MRH_OK;
+  const mrh_ctx::Free& F = c->free;
+  const float* d_obs = dev;
+  if (!d_obs && (rc = stage_obs(c, host, depth_form ? n_obs : 3 * n_obs, &d_obs))) return rc;
+  if (depth_form) {
+    const dim3 grid((unsigned) ((a.cam.cols + kRenderTile - 1) / kRenderTile), (unsigned) ((a.cam.rows + kRenderTile - 1) / kRenderTile));
+    k_freespace_carve<true><<<grid, kFreeLanes, 0, c->stream>>>(c->map.vs, F.L, F.d_words, a, d_obs);
+  } else {
+    k_freespace_carve<false><<<(unsigned) ((n_obs + kFreeLanes - 1) / kFreeLanes), kFreeLanes, 0, c->stream>>>(c->map.vs, F.L, F.d_words, a, d_obs);
+  }
+  HIP_TRY(c, hipGetLastError());
+  if (!dev) HIP_TRY(c, hipStreamSynchronize(c->stream));  // the staging pair is free again
+  return MRH_OK;
+}
+static_assert(kFreeLanes == kRenderTile * kRenderTile, "the depth form's workgroup is one 16 x 16 tile");
+
+// have_out: the required output was given (mrh_freespace_box hands out its own: true).  Reads the map: enters like every reader
+int freebox_enter(mrh_ctx* c, const char* who, const mrh_freespace_box_params* p, const bool have_out, FreeBox* bx) {
+  return reader_enter(c, who, [&](char* msg) {
+    return mrh_plan::freespace_box(msg, who, p, have_out, c->free.on, c->free.L.shift, c->map.min_weight_threshold, c->pending, c->map.shard_count, bx);
+  });
+}
+
+// the two launches: the classified bytes into the context's scratch, the finished bytes into `out`
+int launch_freebox(mrh_ctx* c, const FreeBox& bx, uint8_t* out) {
+  mrh_ctx::Free& F = c->free;
+  const size_t n = (size_t) bx.nx * (size_t) bx.ny * (size_t) bx.nz;
+  if (const int rc = regrow(c, F.d_cls, F.cls_cap, n, n)) return rc;  // an earlier mrh_freespace_box_device may still read the old scratch: the stream drains
+  const auto bricks = [](const int o, const int len) { return (unsigned) (((o + len - 1) >> 3) - (o >> 3) + 1); };
+  const EsdfBox& v = bx.vox;
+  k_freespace_classify<<<dim3(bricks(v.ox, v.nx), bricks(v.oy, v.ny), bricks(v.oz, v.nz)), 256, 0, c->stream>>>(c->map, c->tab, F.L, F.d_words, bx, F.d_cls);
+  k_freespace_frontier<<<(unsigned) ((n + kFreeLanes - 1) / kFreeLanes), kFreeLanes, 0, c->stream>>>(bx, F.d_cls, out);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+static_assert(MRH_FREESPACE_BOX_MAX_SIDE + 1 <= 65535, "the bricks of a box (at most one per cell, plus one) fit a grid dimension");
+
+int segments_enter(mrh_ctx* c, const char* who, const bool have_in, const bool have_out, const uint64_t n, const float step, SegArgs* a) {
+  return free_enter(c, who, [&](char* msg) {
+    return mrh_plan::freespace_segments(msg, who, have_in, have_out, n, step, c->free.on, c->map.vs, c->free.L.shift, c->pending, c->map.shard_count, a);
+  });
+}
+
+// one launch for a.n >= 1 segments; counts may be nullptr
+int launch_segments(mrh_ctx* c, const SegArgs& a, const float* d_a, const float* d_b, uint8_t* status, u32* counts) {
+  const mrh_ctx::Free& F = c->free;
+  k_freespace_segments<<<(unsigned) (((size_t) a.n + kFreeLanes - 1) / kFreeLanes), kFreeLanes, 0, c->stream>>>(c->map.vs, F.L, F.d_words, a, d_a, d_b, status, counts);
+  HIP_TRY(c, hipGetLastError());
+  return MRH_OK;
+}
+
 // ---- map-to-map fusion (include/mrhash_remap.h) --------------------------------------------------------------------------------
 
 // the argument plan of both calls (mrh_plan::remap); dst: the destination of mrh_fuse_map, nullptr for mrh_resample_map
@@ -656,6 +736,106 @@ int mrh_cast_rays_device(mrh_ctx* c, const mrh_rays_params* p, const float* d_or
   return launch_rays(c, a, RaysIn{d_origins, d_dirs, d_tmax},
                      RaysOut{d_range, d_status, (p->outputs & MRH_RAYS_NORMALS) ? d_normals : nullptr, (p->outputs & MRH_RAYS_COLORS) ? d_rgb : nullptr,
                              counts ? (u32*) d_counts : nullptr, counts ? d_first_unknown : nullptr});
+}
+
+int mrh_freespace_create(mrh_ctx* c, const mrh_freespace_params* p) {
+  const char* who = "mrh_freespace_create";
+  FreeLayer L;
+  int rc = free_enter(c, who, [&](char* msg) { return mrh_plan::freespace_create(msg, who, p, c->pending, c->map.shard_count, &L); });
+  if (rc) return rc;
+  mrh_ctx::Free& F = c->free;
+  F.on = false;
+  const size_t words = L.n_words;
+  if ((rc = regrow(c, F.d_words, F.cap, words, words * sizeof(u32)))) return rc;  // a carve in flight writes the old words: the stream drains
+  HIP_TRY(c, hipMemsetAsync(F.d_words, 0, words * sizeof(u32), c->stream));       // behind whatever still uses the old layer
+  F.L = L;
+  F.on = true;
+  return MRH_OK;
+}
+
+int mrh_freespace_clear(mrh_ctx* c) {
+  const int rc = free_layer_enter(c, "mrh_freespace_clear");
+  if (rc) return rc;
+  HIP_TRY(c, hipMemsetAsync(c->free.d_words, 0, (size_t) c->free.L.n_words * sizeof(u32), c->stream));
+  return MRH_OK;
+}
+
+int mrh_freespace_destroy(mrh_ctx* c) {
+  const int rc = free_layer_enter(c, "mrh_freespace_destroy");
+  if (rc) return rc;
+  mrh_ctx::Free& F = c->free;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // nothing uses the words any more
+  F.on = false;
+  F.cap = 0;
+  HIP_TRY(c, dev_free(c, F.d_words));
+  return MRH_OK;
+}
+
+int mrh_freespace_carve_depth(mrh_ctx* c, const mrh_carve_params* p, const float* depth_host, const float R_row_major[9], const float t[3]) {
+  return carve_run(c, "mrh_freespace_carve_depth", true, p, depth_host, nullptr, 0, R_row_major, t);
+}
+
+int mrh_freespace_carve_depth_device(mrh_ctx* c, const mrh_carve_params* p, const float* d_depth, const float R_row_major[9], const float t[3]) {
+  return carve_run(c, "mrh_freespace_carve_depth_device", true, p, nullptr, d_depth, 0, R_row_major, t);
+}
+
+int mrh_freespace_carve_points(mrh_ctx* c, const mrh_carve_params* p, const float* points_host, uint64_t n, const float R_row_major[9], const float t[3]) {
+  return carve_run(c, "mrh_freespace_carve_points", false, p, points_host, nullptr, n, R_row_major, t);
+}
+
+int mrh_freespace_carve_points_device(mrh_ctx* c, const mrh_carve_params* p, const float* d_points, uint64_t n, const float R_row_major[9], const float t[3]) {
+  return carve_run(c, "mrh_freespace_carve_points_device", false, p, nullptr, d_points, n, R_row_major, t);
+}
+
+int mrh_freespace_box(mrh_ctx* c, const mrh_freespace_box_params* p, const uint8_t** out_state) {
+  FreeBox bx;
+  int rc = freebox_enter(c, "mrh_freespace_box", p, out_state != nullptr, &bx);
+  if (rc) return rc;
+  mrh_ctx::Free& F = c->free;
+  const size_t n = (size_t) bx.nx * (size_t) bx.ny * (size_t) bx.nz;
+  if ((rc = regrow(c, F.d_state, F.state_cap, n, n, false))) return rc;  // the previous mrh_freespace_box has finished (it blocked)
+  if ((rc = regrow_pinned(c, F.h_state, F.h_cap, n, n))) return rc;
+  if ((rc = launch_freebox(c, bx, F.d_state))) return rc;
+  Plane pl[1] = {{0, n, F.d_state, true}};
+  if ((rc = read_planes(c, (char*) F.h_state, pl))) return rc;
+  *out_state = (const uint8_t*) pl[0].host;
+  return MRH_OK;
+}
+
+int mrh_freespace_box_device(mrh_ctx* c, const mrh_freespace_box_params* p, uint8_t* d_state) {
+  FreeBox bx;
+  const int rc = freebox_enter(c, "mrh_freespace_box_device", p, d_state != nullptr, &bx);
+  return rc ? rc : launch_freebox(c, bx, d_state);
+}
+
+int mrh_freespace_segments(mrh_ctx* c, const float* a_host, const float* b_host, uint64_t n, float step, const uint8_t** out_status, const uint32_t** out_counts) {
+  SegArgs a;
+  int rc = segments_enter(c, "mrh_freespace_segments", a_host && b_host, true, n, step, &a);
+  if (rc) return rc;
+  if (out_status) *out_status = nullptr;
+  if (out_counts) *out_counts = nullptr;
+  if (n == 0) return MRH_OK;
+  mrh_ctx::Free& F = c->free;
+  // per segment [counts 2 x u32 | status u8], each plane contiguous, on the device as in the pinned copy
+  const size_t ns = (size_t) n, bytes = ns * (2 * sizeof(u32) + 1);
+  if ((rc = regrow(c, F.d_seg, F.seg_cap, ns, bytes, false))) return rc;  // the previous mrh_freespace_segments has finished (it blocked)
+  if ((rc = regrow_pinned(c, F.h_seg, F.h_seg_cap, ns, bytes))) return rc;
+  RaysIn in;  // the two endpoint lists through the staging pair, as the ray queries stage origins and directions
+  if ((rc = stage_rays(c, a_host, b_host, nullptr, ns, &in))) return rc;
+  enum { COUNTS, STATUS };
+  Plane pl[2] = {{0, ns * 2 * sizeof(u32), F.d_seg, out_counts != nullptr}, {ns * 2 * sizeof(u32), ns, F.d_seg + ns * 2 * sizeof(u32), out_status != nullptr}};
+  if ((rc = launch_segments(c, a, in.origins, in.dirs, (uint8_t*) pl[STATUS].dev, (u32*) pl[COUNTS].device()))) return rc;
+  if ((rc = read_planes(c, F.h_seg, pl))) return rc;  // blocks also when nothing is wanted: the staging pair is free again
+  if (out_status) *out_status = (const uint8_t*) pl[STATUS].host;
+  if (out_counts) *out_counts = (const uint32_t*) pl[COUNTS].host;
+  return MRH_OK;
+}
+
+int mrh_freespace_segments_device(mrh_ctx* c, const float* d_a, const float* d_b, uint64_t n, float step, uint8_t* d_status, uint32_t* d_counts) {
+  SegArgs a;
+  const int rc = segments_enter(c, "mrh_freespace_segments_device", d_a && d_b, d_status != nullptr, n, step, &a);
+  if (rc || n == 0) return rc;
+  return launch_segments(c, a, d_a, d_b, d_status, (u32*) d_counts);
 }
 
 int mrh_resample_map(mrh_ctx* src, const mrh_remap_params* p, const float R_row_major[9], const float t[3], const mrh_block_record** out_records, uint64_t* out_n,
