@@ -47,7 +47,7 @@ void process_triangles(mrh_ctx* c) {
       std::array<uint64_t, 3> key;
       for (int a = 0; a < 3; a++) {
         if (eps == 0.0) memcpy(&key[a], &p[a], 8);
-        else key[a] = (uint64_t) (uint32_t) (int32_t) std::floor(p[a] * inv_eps);
+        else key[a] = (uint64_t) (uint32_t) mesh_cell(std::floor(p[a] * inv_eps));
       }
       const bool has_nan = p[0] != p[0] || p[1] != p[1] || p[2] != p[2];  // never equal to anything (Vector3dEqual)
       auto it = has_nan ? vmap.end() : vmap.find(key);

@@ -24,6 +24,7 @@
 
 
 #include "mrh_device.h"
+#include "mrh_meshkey.h"
 
 namespace mrh {
 
@@ -38,14 +39,15 @@ __device__ __forceinline__ u32 key_hash(const Key96 k) {
   return (u32) h;
 }
 // soup vertex i = corner (i % 3) of triangle (i / 3); mrh_triangle = 3 x {p[3], c[3]} floats.
-// Key: the position's bit pattern ((double) p is injective on it, -0 and +0 stay apart), or the eps cell (mesh_extractor.cpp:196-203)
+// Key: the position's bit pattern ((double) p is injective on it, -0 and +0 stay apart), or the eps cell (mesh_extractor.cpp:230-232;
+// mesh_cell: out of the int range, +-inf included, is INT32_MIN as on the reference's x86-64, not v_cvt_i32_f64's saturation)
 __device__ __forceinline__ Key96 vertex_key(const float* __restrict__ soup, const u32 i, const double eps, const double inv_eps, bool& has_nan) {
   const float* v = soup + (size_t) i * 6;
   const float p0 = v[0], p1 = v[1], p2 = v[2];
   has_nan = p0 != p0 || p1 != p1 || p2 != p2;
   Key96 k;
   if (eps == 0.0) { k.a = __float_as_uint(p0); k.b = __float_as_uint(p1); k.c = __float_as_uint(p2); }
-  else { k.a = (u32) (int) floor((double) p0 * inv_eps); k.b = (u32) (int) floor((double) p1 * inv_eps); k.c = (u32) (int) floor((double) p2 * inv_eps); }
+  else { k.a = (u32) mesh_cell(floor((double) p0 * inv_eps)); k.b = (u32) mesh_cell(floor((double) p1 * inv_eps)); k.c = (u32) mesh_cell(floor((double) p2 * inv_eps)); }
   return k;
 }
 __device__ __forceinline__ Key96 face_key(const u32* __restrict__ corner, const u32 t) {

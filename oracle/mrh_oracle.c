@@ -1164,6 +1164,10 @@ static void extract_iso_surface(mrh_ctx* c) {
 typedef struct { uint64_t k[3]; int idx; int used; } VSlot;
 typedef struct { int32_t f[3]; int used; } FSlot;
 
+/* The eps cell of a floored coordinate (mesh_extractor.cpp:232 .cast<int>()): outside the int range, +-inf and NaN included, the
+ * conversion is undefined in C; the reference's x86-64 build answers INT_MIN there.  Spelled out (mrhash_amd/csrc/mrh_meshkey.h). */
+static int32_t mesh_cell(const double x) { return x >= -2147483648.0 && x < 2147483648.0 ? (int32_t) x : INT32_MIN; }
+
 static uint64_t mix64(uint64_t x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33; return x; }
 
 /* Exported so the mesh post-process can be tested on hand-made inputs exactly like
@@ -1180,7 +1184,7 @@ int64_t orc_remove_duplicate_vertices(const double* in_v, int64_t n, const int32
     uint64_t k[3];
     for (int a = 0; a < 3; a++) {
       if (epsilon == 0.0) memcpy(&k[a], &in_v[i * 3 + a], 8); /* D4 */
-      else { const int32_t q = (int32_t) floor(in_v[i * 3 + a] * inv_eps); k[a] = (uint64_t) (uint32_t) q; }
+      else { const int32_t q = mesh_cell(floor(in_v[i * 3 + a] * inv_eps)); k[a] = (uint64_t) (uint32_t) q; }
     }
     size_t h = (size_t) (mix64(k[0] ^ mix64(k[1] ^ mix64(k[2]))) & (cap - 1));
     /* a vertex with a NaN coordinate never compares equal (Vector3dEqual uses ==): always a new vertex */
